@@ -10,7 +10,7 @@ own: one exchange step of one 64-sample batch ("bs=64").  At N GPUs the global m
 every exchange step of the sharded game advances N such batches, so value = N * loop iterations / wall time
 (the whole-job aggregate; identical to the 1-GPU definition at N = 1).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1: one rank per GPU; the global minibatch is 64*N (weak scaling), sharded along the batch axis
   (multimodalgame_amd/dist.py).  Either the caller launches the ranks (torch.distributed.run sets WORLD_SIZE / RANK /
   LOCAL_RANK) or -- plain `python bench.py --gpus N` -- this script re-executes itself under
@@ -44,6 +44,7 @@ WORKLOADS = {
     "c5": (dict(C2, use_binary=False, fixed_exchange=True, n_classes=1000), 256,
            "configs[4]: 1000 classes, continuous messages, global batch 2048 = 256 per GPU on 8 GPUs (256 samples per GPU: one workgroup per sample; the sample-tile MFMA kernels take over from 1024 samples per GPU, --scaling strong at N=1)"),
 }
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32 matrix peak
 
@@ -283,8 +284,29 @@ def collective_us(dp, eng, dev, n=100):
     return out
 
 
-def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True):
-    """Times `steps` training minibatches of one workload (repeated until MIN_TIMED_SECONDS); returns a dict."""
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every array of `outputs` as out_dir/<name>.npy, float64 kept, everything else float32.  When they hold
+    more than `limit` bytes in all, each array keeps the same share of its flat entries: a sorted sample drawn with a fixed
+    seed, i.e. the same entries in every run.  Returns {name: entries written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32).reshape(-1)
+            for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    budget = limit - 4096 * len(arrs)                     # (room for the .npy headers)
+    written = {}
+    for name in sorted(arrs):
+        a = arrs[name]
+        if total > budget:
+            keep = int(a.size * (budget / total))
+            a = a[np.sort(np.random.RandomState(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
+
+
+def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False):
+    """Times `steps` training minibatches of one workload (repeated until MIN_TIMED_SECONDS); returns a dict.
+    outputs: res["outputs"] = host copies of what a caller of the timed path holds after its last step."""
     from multimodalgame_amd.engine import Engine
     from multimodalgame_amd.dist import DataParallel
     from multimodalgame_amd.agents import init_state_dicts
@@ -337,6 +359,13 @@ def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=
         first_elapsed = float(tt.item())
     totals_first = eng.tape["totals"].cpu().numpy().copy()
     first_steps = float(totals_first[0] - totals_before[0])
+    timed_outputs = None
+    if outputs:
+        # the state train_step leaves after the last timed minibatch (before the passes below train further): parameters,
+        # their gradients, the RMSprop state and the loss tape (nll, the five REINFORCE / baseline losses, n_steps, hits)
+        timed_outputs = {k: v.detach().cpu().numpy().copy() for k, v in (
+            ("params", eng.flat_params), ("grads", eng.flat_grads[:eng.n_params]), ("opt_state", eng.opt_state),
+            ("losses", eng.tape["losses"]))}
     done = steps
     # ---- per-kernel durations at THIS point of the trajectory (right after the first pass, before the window trains the agents
     # further): HIP events on the launch stream (library hook mmg_set_profiling; rank 0 records, every rank runs the steps:
@@ -398,7 +427,7 @@ def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=
                first_pass_ms_per_minibatch=1e3 * first_elapsed / steps, first_pass_steps_per_minibatch=first_steps / steps,
                first_pass_ex_steps=first_steps, first_pass_seconds=first_elapsed,
                first_pass_sample_steps=float(totals_first[3] - totals_before[3]), window_live_rows_per_sample=tstar_window,
-               degraded=eng.degraded(), dist_world=(dist.get_world_size() if world > 1 else 1))
+               degraded=eng.degraded(), dist_world=(dist.get_world_size() if world > 1 else 1), outputs=timed_outputs)
     if want_roofline and rank == 0:
         avg = {k: float(np.mean(v)) for k, v in kern_ms.items()}           # ms per minibatch, HIP events (raw brackets)
         n_params = sum(e["rows"] * max(e["cols"], 1) for e in eng.param_entries)
@@ -617,7 +646,12 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="strong (c3 / c5 only): the GLOBAL minibatch is fixed (512 / 2048 samples) and sharded over the ranks; "
                          "value = global-batch exchange steps per second (SURVEY.md 8d)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (parameters, gradients, optimizer state, "
+                         "losses) as DIR/<name>.npy; the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.scaling == "strong" and args.workload not in STRONG_GLOBAL_BATCH:
         ap.error("--scaling strong needs --workload c3 or c5 (the configs BASELINE.json defines with a global batch)")
     if args.gpus < 1:
@@ -644,7 +678,10 @@ def main():
         # "nccl" is RCCL on ROCm; MMG_BENCH_BACKEND=gloo only exists to smoke-test this code path on a 1-GPU box
         dist.init_process_group(os.environ.get("MMG_BENCH_BACKEND", "nccl"), rank=rank, world_size=world)
     strong = args.scaling == "strong"
-    r = run_workload(args.workload, args.steps, args.warmup, args.seed, rank, world, local_rank, strong=strong)
+    r = run_workload(args.workload, args.steps, args.warmup, args.seed, rank, world, local_rank, strong=strong,
+                     **(dict(outputs=True) if args.dump_outputs else {}))
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(r["outputs"], args.dump_outputs)
     if rank == 0:
         per_mb = r["elapsed"] / r["minibatches"]
         unit_batch = r["Bg"] if strong else WORKLOADS[args.workload][1]
@@ -684,6 +721,8 @@ def main():
                            "; a global minibatch of %d*N samples advances N of them per iteration" % unit_batch)},
             "roofline": r["roofline"],
         }
+        if args.dump_outputs:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "entries": dumped}
         if world == 1 and args.workload == "c2" and not args.no_other_configs:
             # the other BASELINE.json configs on this GPU (short runs; parity-test cases, not the metric)
             other = {}

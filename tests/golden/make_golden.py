@@ -5,7 +5,9 @@ Run in the build container only (needs /root/reference; the GPU box never runs
 this).  Nothing from the reference is copied into the repo: ``model.py`` is read
 as text, 15 semantics-restoring substitutions are applied
 in memory so the Python-2.7 / PyTorch-0.1.12 code executes on Python 3.10 /
-torch 2.10, and only NUMBERS (inputs' seeds, outputs) are written out.
+torch 2.10, and only NUMBERS (inputs' seeds, outputs) are written out.  It runs in
+oracle.PORTABLE_FP_ENV, the CPU floating-point environment tests/test_oracle_golden.py
+re-runs the oracle in.
 
 The harness drives the reference's ``Sender/Receiver/Baseline/exchange/
 get_rec_outp/multistep_loss_*`` exactly as ``run()`` does at model.py:1219-1330
@@ -21,16 +23,21 @@ import sys
 import types
 import warnings
 
-import numpy as np
-import torch
-import torch.nn as nn
-import torch.nn.functional as F
-import torch.optim as optim
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
+from oracle import PORTABLE_FP_ENV  # noqa: E402
+os.environ.update(PORTABLE_FP_ENV)       # before torch loads: the same rounding on every host (tests/test_oracle_golden.py)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+import torch.optim as optim  # noqa: E402
+
 from oracle import cpu_ref  # noqa: E402  (fillers only; the oracle is NOT what generates outputs)
+
+torch.set_num_threads(1)                 # (PORTABLE_FP_ENV's one thread, also where the environment asks for more)
 
 warnings.filterwarnings("ignore")
 

@@ -172,3 +172,55 @@ def test_n_gt_1_line_shape_under_gloo(tmp_path):
     assert sc["c5s"]["global_batch"] == 2048 and sc["c5s"]["per_gpu_batch"] == 1024
     assert sc["c5s"]["value_window"] == 30 * 100 * 8.0 / 2.0 and abs(sc["c5s"]["value"] - 1e5) < 1e-3 and "collective_us" in sc["c5s"]
     assert "other_configs" not in d and "cpu_baseline" not in d
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else becomes float32; past the byte limit every array keeps the same
+    seeded sample of its entries, identical from run to run."""
+    import numpy as np
+    outs = {"a": np.arange(1000, dtype=np.float32), "b": np.linspace(0, 1, 3000), "c": np.arange(6, dtype=np.int32).reshape(2, 3)}
+    n = bench.dump_outputs(outs, str(tmp_path / "full"))
+    assert n == {"a": 1000, "b": 3000, "c": 6}
+    a, b, c = (np.load(tmp_path / "full" / (k + ".npy")) for k in "abc")
+    assert a.dtype == np.float32 and b.dtype == np.float64 and c.dtype == np.float32
+    assert np.array_equal(a, outs["a"]) and np.array_equal(b, outs["b"]) and np.array_equal(c, np.arange(6))
+    limit = 3 * 4096 + 8000                  # (the helper keeps 4096 bytes per array for the .npy header)
+    n1 = bench.dump_outputs(outs, str(tmp_path / "s1"), limit=limit)
+    n2 = bench.dump_outputs(outs, str(tmp_path / "s2"), limit=limit)
+    assert n1 == n2 and 0 < n1["a"] < 1000 and 0 < n1["b"] < 3000
+    assert sum(os.path.getsize(p) for p in (tmp_path / "s1").iterdir()) <= limit
+    for k in "abc":
+        x, y = np.load(tmp_path / "s1" / (k + ".npy")), np.load(tmp_path / "s2" / (k + ".npy"))
+        assert np.array_equal(x, y)
+    sa = np.load(tmp_path / "s1" / "a.npy")
+    assert np.all(np.diff(sa) > 0) and set(sa.tolist()) <= set(outs["a"].tolist())     # a sorted subset of the entries
+
+
+def test_dump_outputs_flag_writes_what_the_timed_steps_returned(tmp_path, monkeypatch, capsys):
+    """`bench.py --steps K --dump-outputs DIR`: run_workload is asked for the outputs of exactly K timed steps, they land in DIR,
+    and the line keeps ms_per_step = the timed seconds / K."""
+    import numpy as np
+    seen = []
+
+    def stub(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False):
+        seen.append((workload, steps, warmup, outputs))
+        CFG, B, label = bench.WORKLOADS[workload]
+        return dict(workload=workload, label=label, B=B, Bg=B, elapsed=2.0, minibatches=steps * 10, ex_steps=steps * 80.0,
+                    sample_steps=1.0, cfg=CFG, roofline=None, collective="none (single rank)", collective_us=None,
+                    first_pass_ms_per_minibatch=0.05, first_pass_steps_per_minibatch=7.0, first_pass_ex_steps=steps * 7.0,
+                    first_pass_seconds=steps * 5e-5, dist_world=1,
+                    outputs={"params": np.ones(5, np.float32), "losses": np.arange(8, dtype=np.float32)} if outputs else None)
+
+    monkeypatch.setattr(bench, "run_workload", stub)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    out = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2", "--no-other-configs", "--no-cli",
+                                      "--no-cpu-baseline", "--dump-outputs", str(out)])
+    bench.main()
+    assert seen == [("c2", 7, 2, True)]
+    d = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert d["steps"] == 7 and abs(d["ms_per_step"] - 0.05) < 1e-9
+    assert d["dump_outputs"]["entries"] == {"losses": 8, "params": 5}
+    assert np.array_equal(np.load(out / "losses.npy"), np.arange(8, dtype=np.float32))
+    assert np.array_equal(np.load(out / "params.npy"), np.ones(5, np.float32))
