@@ -198,8 +198,8 @@ int mmg_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, in
  * mmg_clip_step on the reduced gradient.  The collectives are RCCL's
  *     ncclAllReduce(sendbuff, recvbuff, count, datatype, op, comm, stream)
  * called through the ADDRESS the caller registers (libmmg does not link RCCL) on the caller's communicator, in place, on
- * `stream`.  reduce == 0 skips both (a one-rank job).  full_tape != 0: every sample runs all steps (run_all_steps = 1: the
- * minibatches whose log block reads the whole tape), same update.  mmg_dp_train_steps: n minibatches laid out as for
+ * `stream`.  reduce == 0 skips both (a one-rank job).  full_tape != 0: every sample runs all steps (run_all_steps = 3: the
+ * minibatches whose log block reads the whole tape; baseline scores on the live rows only), same update.  mmg_dp_train_steps: n minibatches laid out as for
  * mmg_train_steps (this rank's B rows of each). */
 int mmg_dp_set_allreduce(mmg_handle* h, void* nccl_all_reduce, void* comm);
 int mmg_dp_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,

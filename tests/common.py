@@ -504,8 +504,10 @@ def engine_result(eng, fl):
     return res
 
 
-def hip_train_case(name, meta, early_exit=False, fused=False):
-    """Run a golden train case on the GPU through the C-ABI; returns (packed dict, engine)."""
+def hip_train_case(name, meta, early_exit=False, fused=False, log_tape=False, dp_full_tape=False):
+    """Run a golden train case on the GPU through the C-ABI; returns (packed dict, engine).
+    log_tape: phased log minibatches (run_all_steps == 3, Game.train_step(full_tape=True)); dp_full_tape: the same through
+    one mmg_dp_train_step(full_tape=1, reduce=0) call."""
     fl = flags_from_meta(meta)
     eng = make_engine(meta)
     dev = eng.device
@@ -520,8 +522,10 @@ def hip_train_case(name, meta, early_exit=False, fused=False):
         uz, us, uw = [torch.from_numpy(np.ascontiguousarray(u)).to(dev) for u in (u_z, u_s[..., 0], u_w)]
         if fused:
             eng.train_step(xd, td, dd, uz, us, uw)
+        elif dp_full_tape:
+            eng.dp_train_step(xd, td, dd, uz, us, uw, full_tape=True, reduce=False)
         else:
-            eng.forward(xd, td, dd, uz, us, uw, train=True, run_all=not early_exit)
+            eng.forward(xd, td, dd, uz, us, uw, train=True, run_all=not early_exit, log_tape=log_tape)
             eng.loss_stats()
             eng.backward(xd, td, dd)
         res = engine_result(eng, fl)
@@ -535,7 +539,7 @@ def hip_train_case(name, meta, early_exit=False, fused=False):
             lo, hi = eng.agent_range[a]
             norms[a] = float(eng.flat_grads[lo:hi].double().norm())
         res["grads"], res["grad_norms"] = grads, norms
-        if not fused:
+        if not fused and not dp_full_tape:
             eng.clip_step()
         torch.cuda.synchronize()
         models = {a: _SD({k: v.detach().cpu() for k, v in eng.params[a].items()}) for a in _lib_agents()}

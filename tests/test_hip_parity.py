@@ -46,6 +46,39 @@ def test_train_case_vs_golden_and_oracle(name):
     assert not stray, "gradient entries that match this host's oracle but not the golden vectors, although the oracle does:\n" + "\n".join(stray[:25])
 
 
+# (no s_masks: the fused step stores per-step arrays on the live rows only -- a stopped sample's later mask entries keep what
+#  an earlier minibatch left, include/mmg.h: run_all_steps == 2)
+FUSED_KEEP = ("losses", "n_steps", "hits", "logs", "outp", "dist", ".g.", ".p.", "gradnorm")
+
+
+@pytest.mark.parametrize("name", common.TRAIN_CASES)
+def test_fused_train_case_vs_golden_and_oracle(name):
+    """The fused step (mmg_train_step: what training runs) on every golden train case, directly against the CPU oracle
+    (common.assert_parity) and, for the forward quantities, against the golden vectors.  The fused step keeps the live
+    (step, sample) rows only, so the per-step arrays of exchange() are left to the run-all test above; what training sees --
+    losses, outputs, step counts, gradients, updated parameters -- is compared.  g2 (config 1's agents) must run as the two launches
+    of the benchmark's metric: k_game_fast + k_wgrad<OPT>."""
+    z, meta = common.load_golden(name)
+    got, eng = common.hip_train_case(name, meta, fused=True)
+    pick = lambda d: {k: d[k] for k in (d.keys() if hasattr(d, "keys") else d.files) if any(t in k for t in FUSED_KEEP)}
+    got = pick(got)
+    flips = []
+    want = common.oracle_train_case(name, meta, flips=flips)
+    common.assert_parity(got, pick(want), flips, eng, name + "/fused-oracle", skip=_skip_keys(meta), atol=ATOL, rtol=RTOL)
+    gold = {k: v for k, v in pick(z).items() if not common.is_grad_key(k)}
+    pg = common.compare_packed(got, gold, atol=ATOL, rtol=RTOL, skip=_skip_keys(meta), shift_invariant=True, label=name + "/fused-golden")
+    assert not pg, "forward mismatch of the fused step vs golden (atol 1e-4, rtol 0):\n" + "\n".join(pg[:25])
+    if name == "g2_adaptive_c1":
+        x, target, desc, _ = common.case_inputs(meta, 0, name)
+        dev = eng.device
+        eng.set_profiling(True)
+        eng.train_step(torch.from_numpy(x).to(dev), torch.from_numpy(target).to(dev), torch.from_numpy(desc).to(dev), seed=1)
+        torch.cuda.synchronize()
+        names = [n for n, _ in eng.kernel_times()]
+        eng.set_profiling(False)
+        assert names == ["k_game", "k_wgrad"], names
+
+
 @pytest.mark.parametrize("name", ["g2_adaptive_c1", "g5_one_active", "g3_tiny_adam"])
 def test_early_exit_and_fused_step_equal_run_all(name):
     """A sample that stops computing after its own stop step (training mode) must give the same
