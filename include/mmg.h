@@ -147,6 +147,18 @@ int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64_t* d_targe
                          const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed,
                          int train, int run_all_steps, void* stream);
 
+/* Message corruption of evaluation conversations (-bit_flip -corrupt_region; the reference's eval_dev passes it to exchange(),
+ * model.py:637-638).  mask: host array of n == w_dim entries, each 0 or 1 (misc.py:388-402: build_mask(corrupt_region, W));
+ * NULL clears it.  Host only: no GPU work, the mask travels with every later launch as a kernel argument.  While it is set:
+ *   - mmg_exchange_forward(train = 0) replaces the sender's message of every step by z <- |z - m| (model.py:813-820), m
+ *     broadcast over the batch, before the receiver reads it: the tape's "z" holds the corrupted message, "pz" (the sender's
+ *     probabilities) does not change.  Binary messages: the masked bits are inverted.  Continuous messages (use_binary == 0,
+ *     z = the raw binary_layer output): EVERY entry becomes |z| and the masked ones |z - 1| -- the abs applies to all entries;
+ *   - the training entries (mmg_exchange_forward(train = 1), mmg_train_step[s], mmg_dp_train_step[s]) return an error instead
+ *     of running: the reference never corrupts a training conversation (model.py:1240).
+ * Returns 0, or negative for n != w_dim or an entry other than 0 / 1 (the mask set before stays). */
+int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, int n);
+
 /* Per-rank partial sums of every batch statistic the losses need (counts, sums and squared sums
  * of reward-minus-baseline per stream and step, ...) into the f64 tape array "stats".  With more
  * than one rank the caller all-reduces (sum) that array between this call and mmg_backward

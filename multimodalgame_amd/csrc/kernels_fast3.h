@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
             const float lz = dpp_group_sum<8>(dot4p<8>(wb, s_a + t * H + k2 * 4, 32)) + bb;
             const float ps = fsigmoid(lz);
             const float pp = binary ? ps : 0.f;
-            const float zz = binary ? (train ? ((uz < ps) ? 1.f : 0.f) : rintf(ps)) : lz;
+            const float zz = corrupt_msg(ar, m2, binary ? (train ? ((uz < ps) ? 1.f : 0.f) : rintf(ps)) : lz);
             if (k2 == 0) { s_z[t * W + m2] = zz; s_pz[t * W + m2] = pp; }
         }
         __syncthreads(); MMG_STAMP(8 + 10 * t + 1);

@@ -373,7 +373,22 @@ struct ConvArgs {
     int nprep, prep_cpb;       // k_conversation_fast3: leading workgroups that run k_prep's blocks as roles of the launch (0: k_prep ran before), classes per class block
     int nbase;                 // ... and trailing basehx tiles
     int l2_handoff;            // kernels_mc3.h / kernels_mc3p.h: the tile's members share an XCD (probed at mmg_create): pairs as plain stores, inside its L2
+    // evaluation only (mmg_set_message_corruption): z <- |z - m| on the sender's message of every step (model.py:813-820),
+    // m = bit j of corrupt[j / 32]; by value, so a wave-uniform kernel argument (0: nothing applied)
+    int corrupt_on;
+    uint32_t corrupt[MMG_BLOCK / 32];
 };
+
+// the reference's corruption of message entry j, literally |z - m_j| in fp32 (model.py:818): exact XOR for z in {0, 1}, and in
+// continuous mode the abs of every entry, masked or not.  Call it where the sender's step-t message is formed, before anything
+// (tape, LDS, a hand-off to another workgroup) reads it.  Off (every training call, an evaluation without a mask): a uniform
+// branch around nothing, so results are bit-identical to a build without it.  On: one load of a kernel-argument word (the
+// select chain over all eight words cost more registers and put k_rc_persist into scratch).
+__device__ __forceinline__ float corrupt_msg(const ConvArgs& ar, int j, float z) {
+    if (!ar.corrupt_on) return z;
+    const uint32_t w = ar.corrupt[(j >> 5) & (MMG_BLOCK / 32 - 1)];      // (j < W <= MMG_BLOCK; the mask keeps the load inside)
+    return fabsf(z - (float)((w >> (j & 31)) & 1u));
+}
 
 struct ConvSmem {
     float *hx, *a, *c, *z, *w, *lp, *ne, *h, *hn, *A, *g, *g2, *gi, *gh, *y, *yout, *dbar, *red, *misc;
@@ -491,6 +506,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                         lpv = zz * l1 + (1.f - zz) * l0;           // model.py:908-910
                         nev = p * l1 + (1.f - p) * l0;             // model.py:919-922
                     }
+                    zz = corrupt_msg(ar, n, zz);                   // model.py:813-820 (evaluation only)
                     s.z[n] = zz; s.lp[n] = lpv; s_ne[n] = nev;
                     tp.z[row * W + n] = zz;
                 }

@@ -246,6 +246,7 @@ __global__ __launch_bounds__(512, 2) void k_conversation_mc(Dims dm, Params P, T
                     zz = train ? ((s_uz[t * W + nb] < pp) ? 1.f : 0.f) : rintf(pp);
                     if (have) tp.pz[row * W + nb] = pp;
                 }
+                zz = corrupt_msg(ar, nb, zz);                   // model.py:813-820 (evaluation only)
                 s_z[nb] = zz; s_lp[nb] = pp;
                 if (have) tp.z[row * W + nb] = zz;
             }

@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256, 1) void k_conversation_mc3(Dims dm, Params P, 
         __syncthreads();
         // ===== P2 sender message (continuous: the logits themselves)
         {
-            const float lz = dpp_group_sum<8>(dot4p<8>(wb, s_a + k2 * 4, 32)) + bb;
+            const float lz = corrupt_msg(ar, m2, dpp_group_sum<8>(dot4p<8>(wb, s_a + k2 * 4, 32)) + bb);     // model.py:813-820 (evaluation only)
             if (k2 == 0) { s_z[m2] = lz; t_z[t * W + m2] = lz; }
         }
         __syncthreads();

@@ -754,6 +754,7 @@ __device__ __forceinline__ void rc_s2_role(const Dims& dm, const Params& P, cons
                 zz = ar.train ? ((uz < pp) ? 1.f : 0.f) : rintf(pp);    // model.py:227 / 229
                 if (m < nb) st_wt(&tp.pz[(rowb + b) * W + col], pp);
             }
+            zz = corrupt_msg(ar, col, zz);                                  // model.py:813-820 (evaluation only)
             if (m < nb) st_wt(&tp.z[(rowb + b) * W + col], zz);
             st_wt(&tp.rcxz[(((size_t)tile * (W >> 4) + k) * 16 + m) * 16 + c], (m < nb) ? zz : 0.f);     // the GRU slices' copy, fragment order
         }

@@ -779,6 +779,7 @@ __device__ __forceinline__ void conv_tile_body(const Dims& dm, const Params& P, 
                             } else zz = rintf(pp);                                          // model.py:229
                             if (misc[TL_LIVE + m] != 0.f) tp.pz[(rowb + b) * W + n] = pp;
                         }
+                        zz = corrupt_msg(ar, n, zz);                                      // model.py:813-820 (evaluation only)
                         s_z[m * L.ldW + n] = zz; s_pz[m * L.ldW + n] = pp;
                         if (misc[TL_LIVE + m] != 0.f) tp.z[(rowb + b) * W + n] = zz;
                     }
@@ -1374,6 +1375,7 @@ __device__ __forceinline__ void s2_role(const Dims& dm, const Params& P, const T
                         zz = (u < pp) ? 1.f : 0.f;                                          // model.py:227
                     } else zz = rintf(pp);                                                  // model.py:229
                 }
+                zz = corrupt_msg(ar, n0 + n, zz);                                           // model.py:813-820 (evaluation only)
                 s_zs[m * ldZ + n] = zz;
                 if (m < nb && s_live[m] != 0.f) {                                           // (read back by the receiver role: write-through)
                     st_wt(&tp.z[(rowb + b) * W + n0 + n], zz);
@@ -1620,6 +1622,7 @@ __device__ __forceinline__ void sb_role(const Dims& dm, const Params& P, const T
                 pp = fsigmoid(lz);
                 zz = train ? ((uz < pp) ? 1.f : 0.f) : rintf(pp);                               // model.py:227 / 229
             }
+            zz = corrupt_msg(ar, c0 + oc, zz);                                                   // model.py:813-820 (evaluation only)
             s_zs[om * ldZ + oc] = zz;
             zq = zz; pq = pp;
         }
@@ -2196,7 +2199,7 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_send_s2(Dims dm, Params P, Tape t
             } else zz = rintf(pp);
             tp.pz[(rowb + b) * W + n] = pp;
         }
-        tp.z[(rowb + b) * W + n] = zz;
+        tp.z[(rowb + b) * W + n] = corrupt_msg(ar, n, zz);        // model.py:813-820 (evaluation only)
     }
 }
 

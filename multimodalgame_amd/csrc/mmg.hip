@@ -108,6 +108,10 @@ struct mmg_handle {
     uint32_t last_code;        // the dependency word of the last recovery
     // data-parallel step inside the library (mmg_dp_set_allreduce): RCCL's ncclAllReduce by address + the caller's communicator
     void* ar_fn; void* ar_comm;
+    // mmg_set_message_corruption: the mask every evaluation conversation applies to the sender's messages (model.py:813-820);
+    // while it is set, the training entries refuse to run
+    bool corrupt_on = false;
+    uint32_t corrupt[MMG_BLOCK / 32] = {};
     mmg_handle() : params(nullptr), grads(nullptr), opt_state(nullptr), ws(nullptr), d_jt(nullptr), h_err(nullptr), d_err(nullptr),
                    no_roles(false), degraded(false), recoveries(0), last_code(0u), ar_fn(nullptr), ar_comm(nullptr) {}
     ~mmg_handle() {
@@ -965,6 +969,11 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
     if (run_all_steps == 3) run_all_steps = tape_all ? 0 : 1;
     ar.y_last_only = y_last_only; ar.lean = lean;
     ar.train = train; ar.run_all = (run_all_steps || tape_all) ? 1 : 0; ar.t_begin = 0; ar.t_end = d.T; ar.phases = 3; ar.sprod_first = 1;
+    if (h->corrupt_on) {
+        if (train) return fail("a message corruption mask is set: training conversations are not corrupted (mmg_set_message_corruption(h, NULL, 0) clears it)");
+        ar.corrupt_on = 1;
+        memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt));
+    }
     bool base_ready = false;
     h->basehx_ready = false;
     h->bas_deferred = false;
@@ -1056,10 +1065,30 @@ extern "C" int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64
                                     const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed,
                                     int train, int run_all_steps, void* stream) {
     if (!h) return fail("NULL handle");
+    if (train && h->corrupt_on) return fail("mmg_exchange_forward(train = 1): a message corruption mask is set (evaluation only; mmg_set_message_corruption(h, NULL, 0) clears it)");
     const int warn = train ? error_gate(h, (hipStream_t)stream, true) : 0;     // a training forward pass starts a minibatch
     if (warn < 0) return -1;
     const int rc = exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, train, run_all_steps, stream);
     return rc ? rc : warn;
+}
+
+// The evaluation mask of -bit_flip (include/mmg.h): host state only; exchange_forward_impl copies it into the launch arguments.
+extern "C" int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, int n) {
+    if (!h) return fail("NULL handle");
+    if (!mask) {
+        h->corrupt_on = false;
+        memset(h->corrupt, 0, sizeof(h->corrupt));
+        return 0;
+    }
+    if (n != h->dm.W) return fail("mmg_set_message_corruption: the mask has %d entries, the message %d bits", n, h->dm.W);
+    uint32_t words[MMG_BLOCK / 32] = {};
+    for (int j = 0; j < n; ++j) {
+        if (mask[j] > 1) return fail("mmg_set_message_corruption: mask[%d] = %d (0 or 1 expected)", j, (int)mask[j]);
+        words[j >> 5] |= (uint32_t)mask[j] << (j & 31);
+    }
+    memcpy(h->corrupt, words, sizeof(words));
+    h->corrupt_on = true;
+    return 0;
 }
 
 extern "C" int mmg_loss_stats(mmg_handle* h, void* stream) {
@@ -1319,6 +1348,7 @@ static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
 extern "C" int mmg_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                               const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, void* stream) {
     if (!h) return fail("NULL handle");
+    if (h->corrupt_on) return fail("mmg_train_step: a message corruption mask is set (evaluation only; mmg_set_message_corruption(h, NULL, 0) clears it)");
     if (h->cfg.global_batch != h->cfg.batch) return fail("mmg_train_step is single-GPU; with several ranks: mmg_dp_train_step, or all-reduce between the phases");
     if (!d_target) return fail("target must not be NULL");
     const int warn = error_gate(h, (hipStream_t)stream, true);
@@ -1333,6 +1363,7 @@ extern "C" int mmg_train_step(mmg_handle* h, const float* d_x, const int64_t* d_
 extern "C" int mmg_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc,
                                uint64_t seed, void* stream) {
     if (!h) return fail("NULL handle");
+    if (h->corrupt_on) return fail("mmg_train_steps: a message corruption mask is set (evaluation only; mmg_set_message_corruption(h, NULL, 0) clears it)");
     if (h->cfg.global_batch != h->cfg.batch) return fail("mmg_train_steps is single-GPU; with several ranks: mmg_dp_train_steps");
     if (!d_x || !d_target || !d_desc || n < 0) return fail("x / target / desc must not be NULL, n >= 0");
     int warn = 0;
@@ -1381,6 +1412,7 @@ static int dp_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_target
 extern "C" int mmg_dp_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                                  const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, int full_tape, int reduce, void* stream) {
     if (!h) return fail("NULL handle");
+    if (h->corrupt_on) return fail("mmg_dp_train_step: a message corruption mask is set (evaluation only; mmg_set_message_corruption(h, NULL, 0) clears it)");
     if (!d_x || !d_target || !d_desc) return fail("x / target / desc must not be NULL");
     const int warn = error_gate(h, (hipStream_t)stream, true);
     if (warn < 0) return -1;
@@ -1390,6 +1422,7 @@ extern "C" int mmg_dp_train_step(mmg_handle* h, const float* d_x, const int64_t*
 extern "C" int mmg_dp_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc,
                                   uint64_t seed, int reduce, void* stream) {
     if (!h) return fail("NULL handle");
+    if (h->corrupt_on) return fail("mmg_dp_train_steps: a message corruption mask is set (evaluation only; mmg_set_message_corruption(h, NULL, 0) clears it)");
     if (!d_x || !d_target || !d_desc || n < 0) return fail("x / target / desc must not be NULL, n >= 0");
     int warn = 0;
     for (int64_t i = 0; i < n; ++i) {

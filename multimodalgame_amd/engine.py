@@ -3,6 +3,7 @@ libmmg handle on one GPU, and exposes the phases of the reference's per-minibatc
 (model.py:1240-1339) as methods.  PyTorch is used for device memory and streams only."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -98,15 +99,44 @@ class Engine(object):
         return {a: {k: v.detach().cpu().clone() for k, v in d.items()} for a, d in self.params.items()}
 
     # ------------------------------------------------------------------ phases
-    def forward(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0, train=True, run_all=False, minimal=False, log_tape=False):
+    def forward(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0, train=True, run_all=False, minimal=False, log_tape=False,
+                corrupt_mask=None):
         """run_all: every sample runs all T steps (what exchange() returns).  minimal (training only): store just what the
         backward pass reads (include/mmg.h: run_all_steps == 2) -- what the fused mmg_train_step does.  log_tape (training
-        only): run_all for the conversation, the baselines on the live rows only (run_all_steps == 3: a log minibatch)."""
+        only): run_all for the conversation, the baselines on the live rows only (run_all_steps == 3: a log minibatch).
+        corrupt_mask (evaluation only): W entries of 0 / 1 (misc.build_mask's [W, 1] indicator does) -- the sender's message of
+        every step becomes |z - m| before the receiver reads it (model.py:813-820).  The mask is set for this call only: the
+        engine may serve a training step next."""
         f32 = torch.float32
-        _lib.check(self.lib.mmg_exchange_forward(
-            self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
-            self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed),
-            int(bool(train)), (3 if log_tape and train else 1) if run_all else (2 if minimal and train else 0), self._stream()))
+        if corrupt_mask is not None:
+            if train:
+                raise NotImplementedError("message corruption applies to evaluation conversations only (model.py:637-638)")
+            self.set_message_corruption(corrupt_mask)
+        try:
+            _lib.check(self.lib.mmg_exchange_forward(
+                self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
+                self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed),
+                int(bool(train)), (3 if log_tape and train else 1) if run_all else (2 if minimal and train else 0), self._stream()))
+        finally:
+            if corrupt_mask is not None:
+                self.set_message_corruption(None)
+
+    def set_message_corruption(self, mask):
+        """mask: W entries of 0 / 1, or None to clear (include/mmg.h: mmg_set_message_corruption; host only, no GPU work).  While a
+        mask is set the training entries raise; forward(corrupt_mask=...) sets and clears it around one call."""
+        if mask is None:
+            _lib.check(self.lib.mmg_set_message_corruption(self.handle, None, 0))
+            return
+        a = np.asarray(mask.detach().cpu() if torch.is_tensor(mask) else mask).reshape(-1)
+        key = (a.dtype.str, a.tobytes())
+        cached = getattr(self, "_corrupt_buf", None)
+        if cached is None or cached[0] != key:                # (eval_dev hands the same mask to every dev batch: convert it once)
+            if a.size != self.cfg.w_dim:
+                raise ValueError("corruption mask of %d entries for a %d-bit message" % (a.size, self.cfg.w_dim))
+            if not ((a == 0) | (a == 1)).all():
+                raise ValueError("corruption mask entries must be 0 or 1")
+            cached = self._corrupt_buf = (key, (C.c_uint8 * a.size)(*[int(v) for v in a.tolist()]))
+        _lib.check(self.lib.mmg_set_message_corruption(self.handle, cached[1], len(cached[1])))
 
     def loss_stats(self):
         _lib.check(self.lib.mmg_loss_stats(self.handle, self._stream()))

@@ -250,16 +250,26 @@ def default_flags(argv=None):
 # silently computing something else.
 # ---------------------------------------------------------------------------------------------------------------------
 UNSUPPORTED = (
-    # (flag, predicate on its value, reference lines that read it)
-    ("desc_attn", lambda v: bool(v), "model.py:344-409 (description attention)"),
-    ("sender_mix", lambda v: v not in (None, "sum"), "model.py:201-214 (prod / mou mixing of h_x and h_w)"),
-    ("flipout_sen", lambda v: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message)"),
-    ("flipout_rec", lambda v: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message)"),
-    ("ignore_receiver", lambda v: bool(v), "model.py:217-218 (sender ignores the receiver's message)"),
-    ("ignore_code", lambda v: bool(v), "model.py:219-221 (sender ignores its code input)"),
-    ("visual_attn", lambda v: bool(v), "model.py:114-191 (visual attention over layer4_2)"),
-    ("bit_flip", lambda v: bool(v), "model.py:813-824 (message corruption)"),
+    # (flag, predicate on its value and the flags object, reference lines that read it)
+    ("desc_attn", lambda v, fl: bool(v), "model.py:344-409 (description attention)"),
+    ("sender_mix", lambda v, fl: v not in (None, "sum"), "model.py:201-214 (prod / mou mixing of h_x and h_w)"),
+    ("flipout_sen", lambda v, fl: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message)"),
+    ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message)"),
+    ("ignore_receiver", lambda v, fl: bool(v), "model.py:217-218 (sender ignores the receiver's message)"),
+    ("ignore_code", lambda v, fl: bool(v), "model.py:219-221 (sender ignores its code input)"),
+    ("visual_attn", lambda v, fl: bool(v), "model.py:114-191 (visual attention over layer4_2)"),
+    # -bit_flip WITH a region corrupts every dev evaluation's messages (model.py:637-638, 813-820); without one the reference
+    # crashes at its first dev evaluation (build_mask(None, ...), misc.py:390)
+    ("bit_flip", lambda v, fl: bool(v) and not _flag(fl, "corrupt_region"),
+     "bit_flip without corrupt_region: model.py:813-820 needs the positions to corrupt (-corrupt_region, misc.py:388-402)"),
 )
+
+
+def _flag(fl, name):
+    try:
+        return getattr(fl, name)
+    except (AttributeError, KeyError, FlagsError):
+        return None
 
 
 def check_supported(flags=None):
@@ -271,7 +281,7 @@ def check_supported(flags=None):
             v = getattr(fl, name)
         except (AttributeError, KeyError, FlagsError):
             continue
-        if pred(v):
+        if pred(v, fl):
             bad.append("-%s=%s [reference: %s]" % (name, v, where))
     if bad:
         raise NotImplementedError("outside the accelerated exchange path (SURVEY.md §2): " + "; ".join(bad))

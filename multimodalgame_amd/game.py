@@ -3,6 +3,7 @@ on top of the HIP engine, with the reference's calling conventions and return st
 import torch
 
 from . import flags as _flags
+from . import misc
 from .engine import Engine
 
 
@@ -148,8 +149,11 @@ class Game(object):
         data, target, desc = exchange_args["data"], exchange_args.get("target"), exchange_args["desc"]
         train = exchange_args["train"]
         break_early = exchange_args.get("break_early", False)
-        if exchange_args.get("corrupt", False):
-            raise NotImplementedError("-bit_flip message corruption is outside the accelerated hot path")
+        corrupt_mask = None
+        if exchange_args.get("corrupt", False):                          # model.py:813-820 (eval_dev's call, model.py:637-638)
+            if train:
+                raise NotImplementedError("message corruption of training conversations is outside the accelerated hot path")
+            corrupt_mask = misc.build_mask(exchange_args.get("corrupt_region"), self.cfg["w_dim"])
         if exchange_args.get("data_context") is not None:
             raise NotImplementedError("attention context is outside the accelerated hot path")
         for k, m in self.modules.items():
@@ -162,7 +166,8 @@ class Game(object):
         desc = desc.to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
         self._call += 1
-        eng.forward(data, target, desc, seed=self.seed, train=train, run_all=True)
+        eng.forward(data, target, desc, seed=self.seed, train=train, run_all=True,
+                    **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         tp = eng.tape
         T = self.max_exchange
         n = T
@@ -186,11 +191,12 @@ class Game(object):
         self.modules["receiver"].h_w = tp["g"][n - 1]
         return s, sen_w, rec_w, y, bs, br
 
-    def eval_forward(self, data, target, desc):
+    def eval_forward(self, data, target, desc, corrupt_mask=None):
         """The eval-mode conversation of exchange() (rounded messages, cumulative-product stop bit, every sample runs all
         max_exchange steps) WITHOUT slicing / cloning the tape into the reference's per-step lists and without any host
         synchronisation: returns the engine, whose tape views (mask, s, ps, z, pz, w, pw, y, ...) stay valid until its next
-        forward pass.  eval_dev() reduces them on the device (model.py:640-691)."""
+        forward pass.  eval_dev() reduces them on the device (model.py:640-691).  corrupt_mask: misc.build_mask's [W, 1]
+        indicator (or W entries of 0 / 1): the sender's messages are corrupted as under -bit_flip (model.py:813-820)."""
         for k in ("sender", "receiver"):
             if self.modules.get(k) is not None:
                 self.modules[k].train(False)
@@ -201,7 +207,8 @@ class Game(object):
         desc = desc.to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
         self._call += 1
-        eng.forward(data, target, desc, seed=self.seed, train=False, run_all=True)
+        eng.forward(data, target, desc, seed=self.seed, train=False, run_all=True,
+                    **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         return eng
 
     # ------------------------------------------------------------------ model.py:1240-1339

@@ -473,13 +473,19 @@ from .agents import xavier_normal  # noqa: E402,F401  (one implementation: agent
 
 
 def build_mask(region_str, size):
-    """[size, 1] indicator of the positions named by a region string such as "0:4,7,10:12" (half-open ranges and single
-    positions; -corrupt_region, misc.py:388-402)."""
-    mask = torch.zeros(size, 1)
+    """[size, 1] indicator of the positions named by a region string such as "0:4,7,10:12" (-corrupt_region, misc.py:388-402).
+    A piece is `i` or `a:b`, and `a:b` is Python's range(a, b) -- not a slice: "-2:3" at size 32 names 30, 31, 0, 1, 2.  The
+    indices index the [size, 1] tensor as torch does: a negative one counts from the end, one outside [-size, size) raises
+    IndexError (where the reference's `mask[index] = 1` raises)."""
+    if not region_str:
+        raise ValueError("-bit_flip needs a -corrupt_region (the positions of the message to corrupt), got %r" % (region_str,))
+    index = []
     for piece in region_str.split(","):
-        lo, sep, hi = piece.partition(":")
-        if sep:
-            mask[int(lo):int(hi)] = 1
-        else:
-            mask[int(lo)] = 1                          # a single position, negative ones included (misc.py:398-400)
+        r = piece.split(":")
+        index.extend([int(r[0])] if len(r) == 1 else range(int(r[0]), int(r[1])))
+    mask = torch.zeros(size, 1)
+    for i in index:
+        if not -size <= i < size:
+            raise IndexError("-corrupt_region %r: position %d is outside a %d-bit message" % (region_str, i, size))
+        mask[i] = 1
     return mask

@@ -15,7 +15,7 @@ from . import flags as _flags
 from .agents import Baseline, Receiver, Sender
 from .flags import FLAGS
 from .game import Game, exchange, get_rec_outp
-from .misc import (FileLogger, VisdomLogger, cbow, embed, load_epoch, load_hdf5, read_data, torch_load, torch_save,
+from .misc import (FileLogger, VisdomLogger, build_mask, cbow, embed, load_epoch, load_hdf5, read_data, torch_load, torch_save,
                    write_synthetic_dataset)
 from .sparks import sparks
 
@@ -72,6 +72,17 @@ def _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k):
             hl.append((per_step * live).sum(1) / n.to(torch.float32))       # [NB]: mean over the executed steps (model.py:679, 684)
 
 
+def corrupt_mask_from_flags():
+    """The [W, 1] mask of -bit_flip -corrupt_region (misc.build_mask; model.py:813-820), or None without -bit_flip.  A region
+    outside the W-bit message raises ValueError here, where the reference fails at its first dev evaluation."""
+    if not FLAGS.bit_flip:
+        return None
+    try:
+        return build_mask(FLAGS.corrupt_region, FLAGS.rec_w_dim)
+    except IndexError as e:
+        raise ValueError(str(e))
+
+
 def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels, conf_mat_path, device, dump=None):
     """model.py:580-722 ON THE DEVICE: deterministic conversations on the dev set, top-k accuracy (nominal batch size in the
     denominator, line 667), confusion matrix, conversation length and Hamming statistics.
@@ -86,8 +97,11 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     lengths, the two Hamming means); the results are copied to the host ONCE.
     (Round 4 transcribed the host loop literally: numpy argsort per batch and ~20 float() syncs per batch.)
 
-    dump: optional dict that receives the last batch's engine (the dev sample dump of model.py:1463-1518 reads its tape)."""
+    dump: optional dict that receives the last batch's engine (the dev sample dump of model.py:1463-1518 reads its tape).
+    Under -bit_flip every batch's conversation runs with the sender's messages corrupted (model.py:637-638, 813-820): the
+    accuracy and the sender's Hamming statistic are those of the corrupted messages."""
     W = FLAGS.rec_w_dim
+    corrupt_mask = corrupt_mask_from_flags()
     n_cls = desc.size(0)
     T = game.max_exchange
     # ---- pass 1: one eval-mode launch per batch; what the statistics need of its tape is copied into per-batch-size stacks
@@ -102,7 +116,7 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
                            feats=(FLAGS.img_feat,), device=device):
         target, data = batch["target"], batch[FLAGS.img_feat]
         _bs = target.size(0)
-        eng = game.eval_forward(data, target, desc)
+        eng = game.eval_forward(data, target, desc, corrupt_mask=corrupt_mask)
         tp = eng.tape
         g = groups.setdefault(_bs, dict(mask=[], s=[], z=[], w=[], y=[], target=[]))
         g["mask"].append(tp["mask"].view(T + 1, _bs).clone()); g["s"].append(tp["s"].view(T, _bs).clone())
@@ -172,6 +186,7 @@ def run(stats=None):
     stats: optional dict; the training loop leaves there what bench.py --cli reports: wall seconds of the epoch loop
     (device-synchronised at both ends, eval_dev time excluded), minibatches and exchange steps (device-side count)."""
     _flags.check_supported(FLAGS)                     # unsupported reference switches fail before anything is written
+    corrupt_mask_from_flags()                         # ... and so does a -corrupt_region the message cannot hold
     rank, world, local_rank = parallel_env()
     if world > 1 and FLAGS.batch_size % world:
         raise ValueError("-batch_size %d does not divide over %d ranks" % (FLAGS.batch_size, world))
