@@ -18,6 +18,8 @@
  *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (non-attention, sender_mix=sum)
  *   mmg_receiver_forward   <- Receiver.forward              model.py:303-477 (non-desc_attn)
  *   mmg_baseline_forward   <- Baseline.forward              model.py:496-516
+ *   mmg_exchange_vjp       <- loss.backward() of ONE agent's graph for any loss built from exchange()'s outputs
+ *                             (model.py:1309, 1316, 1322, 1328; graphs split at model.py:807-811, 826-829, 835-843)
  *
  * Conventions
  *   - plain pointers and sizes; every pointer named d_* is DEVICE memory owned by the caller
@@ -252,6 +254,28 @@ int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float* d_desc, f
                          float* d_h_w, void* stream);
 int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, const float* d_binary,
                          const float* d_inp, int rows, float* d_score, void* stream);
+
+/* Vector-Jacobian product of ONE agent's graph of the last training exchange: the backward pass autograd runs for
+ * loss.backward() at model.py:1309 (receiver), 1316 (sender), 1322 (baseline_rec), 1328 (baseline_sen), but for ANY loss -- the
+ * caller hands in d loss / d output of the agent's differentiable outputs.  The four graphs are disjoint as in the reference
+ * (every input crossing between agents is detached, model.py:807-811, 826-829, 835-843), so each call is independent.
+ * Reads the tape of mmg_exchange_forward(train = 1, run_all_steps = 1) -- the caller makes sure nothing rewrote it since -- and
+ * writes ONLY `agent`'s slice of the gradient buffer (every tensor of the agent, overwritten, not accumulated).
+ *   agent:   MMG_AGENT_*; the baselines exist with binary messages only
+ *   n_steps: executed steps n (1..max_exchange); every upstream array holds n rows [n, B, .]; steps >= n get zero gradient
+ *   d_x[B,F] (sender), d_desc[D,V] (receiver): the inputs of that forward call
+ *   upstream gradients, each NULL = zero:
+ *     d_dy[n,B,D]   receiver: class logits y_t                                      model.py:433
+ *     d_dz[n,B,W]   sender:   sen_probs_t (binary) | sen_feats_t = logits (continuous) model.py:223, 238
+ *     d_dw[n,B,W]   receiver: rec_probs_t (binary) | rec_feats_t = logits (continuous) model.py:456, 474
+ *     d_dps[n,B]    receiver: s_probs_t                                              model.py:414-415
+ *     d_dbs[n,B]    baseline_sen scores bs_t                                         model.py:835
+ *     d_dbr[n,B]    baseline_rec scores br_t                                         model.py:842
+ * Not differentiated (constants, as in the reference): sampled bits, masks, data, desc, h_x, h_z and softmax(y) inside dbar
+ * (model.py:441).  fp32, deterministic (no float atomics); enqueued on `stream`. */
+int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
+                     const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
+                     void* stream);
 
 /* The log block of a minibatch (model.py:1342-1461) gathered on the device: ONE launch writes one flat float64 vector the
  * caller copies to the host (asynchronously) and formats.  Layout (mmg_log_snapshot_count() doubles):

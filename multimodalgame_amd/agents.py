@@ -7,7 +7,10 @@ each parameter's storage becomes a view into the engine's flat parameter buffer,
 kernels read and the fused optimizer updates in place.
 
 forward() is forward-only (no autograd graph): gradients are produced by the hand-written backward
-kernels through ``Game.train_step`` -- the counterpart of model.py:1243-1330.
+kernels through ``Game.train_step`` -- the counterpart of model.py:1243-1330.  For a loss of your own, a training
+``Game.exchange()`` with the autograd opt-in returns outputs with one autograd node per agent; ``backward()`` then fills
+``p.grad`` of these modules' parameters through the HIP vector-Jacobian products (``Game(..., autograd=True)``,
+INTEGRATION.md section 4b), so that ``clip_grad_norm_`` and ``torch.optim`` work as in the reference.
 """
 import math
 

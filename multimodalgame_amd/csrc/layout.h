@@ -82,6 +82,7 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
 // Symbols available in the dims: B D F H W R V K T T1(=T+1) NSTAT NPART
 // ---------------------------------------------------------------------------------------------
 #define MMG_GN_BLOCKS 128      // blocks (= partial sums) of the gradient-norm kernel
+#define MMG_VJP_TABLE_BYTES 32768   // one job table of mmg_exchange_vjp (sizeof(JobTable), checked at mmg_create)
 #define MMG_TAPE_LIST(X)                                                          \
     /* ---- forward ---- */                                                        \
     X(hx, float, 0, 2, B, H, 1)          /* image_layer(x)            model.py:195 */ \
@@ -203,7 +204,35 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
     X(ones, float, 0, 1, 256, 1, 1)      /* 1.0f: B operand of bias gradients run as K = 1 GEMM jobs (many (step, sample) rows) */ \
     X(wcnt, int32_t, 2, 1, 16384, 1, 1)  /* k_wgrad: slices of an output tile that have written their partial tile (the last one adds them up and zeroes the count) */ \
     X(wpart, float, 0, 1, NWP, 1, 1)     /* raw partial tiles of weight gradients whose rows are split over workgroups (k_wgrad) */ \
-    X(tables, uint8_t, 1, 1, 98304, 1, 1) /* GEMM / column-sum job descriptors      */
+    /* ---- vector-Jacobian products of a training exchange (mmg_exchange_vjp, kernels_vjp.h): deltas over ALL T * B rows ---- */ \
+    X(vdesc, float, 0, 2, D, V, 1)       /* copy of desc (B operand of the y1.weight[:, R:] job)           */ \
+    X(vCd, float, 0, 2, D, R, 1)         /* desc . W_y1[:, R:]^T + b_y1, formed by the VJP                 */ \
+    X(vdC, float, 0, 2, D, R, 1)         /* dL/d Cd over the (t < n, b) rows                               */ \
+    X(vPy2, float, 0, 2, D, R, 1)        /* per-class partials of dL/d w_y2                                */ \
+    X(vdbar, float, 0, 3, T, B, V)       /* softmax(y_t) . desc, formed by the VJP                         */ \
+    X(vdys, float, 0, 2, T, B, 1)        /* sum_d dy_t[b, d] (y2.bias)                                     */ \
+    X(vg, float, 0, 3, T, B, R)          /* receiver.h_w, formed by the VJP                                */ \
+    X(vA, float, 0, 3, T, B, R)          /* A_t = W_y1[:, :R] h_{t+1}, formed by the VJP                   */ \
+    X(vdA, float, 0, 3, T, B, R)         /* dL/d A_t at every step                                         */ \
+    X(vdlw, float, 0, 3, T, B, W)                                                  \
+    X(vdls, float, 0, 2, T, B, 1)                                                  \
+    X(vdgpre, float, 0, 3, T, B, R)                                                \
+    X(vdgi, float, 0, 3, T, B, 3 * R)                                              \
+    X(vdgh, float, 0, 3, T, B, 3 * R)                                              \
+    X(vdsig, float, 0, 1, W, 1, 1)       /* sigmoid'(code_bias)                                            */ \
+    X(vc, float, 0, 3, T, B, W)          /* sender code input: sigmoid(code_bias) at t = 0, w_{t-1} after */ \
+    X(va, float, 0, 3, T, B, H)          /* tanh(h_x + h_w), formed by the VJP                             */ \
+    X(vdlz, float, 0, 3, T, B, W)                                                  \
+    X(vdpre, float, 0, 3, T, B, H)                                                 \
+    X(vdhx, float, 0, 2, B, H, 1)                                                  \
+    X(vdc0, float, 0, 2, B, W, 1)        /* W_c^T dpre_0 (code_bias path)                                  */ \
+    X(vzr, float, 0, 3, T, B, W)         /* z_r: baseline_sen's message input                              */ \
+    X(vhid_s, float, 0, 3, T, B, K)      /* relu hidden units of the baselines, formed by the VJP          */ \
+    X(vhid_r, float, 0, 3, T, B, K)                                                \
+    X(vdbs, float, 0, 2, T, B, 1)                                                  \
+    X(vdbr, float, 0, 2, T, B, 1)                                                  \
+    X(tables, uint8_t, 1, 1, 98304, 1, 1) /* GEMM / column-sum job descriptors      */ \
+    X(vtables, uint8_t, 1, 1, 4 * MMG_VJP_TABLE_BYTES, 1, 1) /* the VJP's four job tables (one per agent), uploaded at mmg_create */
 
 // statistics vector (f64).  Per stream (0 = stop bits, 1 = receiver msgs, 2 = sender msgs) and
 // step: n, sum w, sum w^2, sum w*logp, sum negent; per baseline (0 = rec, 1 = sen) and step:
@@ -263,7 +292,7 @@ __host__ __device__ inline int dc_slices(int B) { return B >= 1024 ? 4 : 1; }
 
 struct TapeLayout {
     int n;
-    mmg_tape_entry e[128];
+    mmg_tape_entry e[176];
     int64_t total;
 };
 

@@ -22,6 +22,7 @@
 #include "kernels_mc3.h"
 #include "kernels_mc3p.h"
 #include "kernels_rc.h"
+#include "kernels_vjp.h"
 #ifdef MMG_ROLE_DIAG
 #include "diag_kernels.h"
 #endif
@@ -112,6 +113,7 @@ struct mmg_handle {
     // while it is set, the training entries refuse to run
     bool corrupt_on = false;
     uint32_t corrupt[MMG_BLOCK / 32] = {};
+    WgHead vjp_hd[4] = {};      // launch geometry of k_wgrad over the four VJP job tables (tape.vtables, mmg_exchange_vjp)
     mmg_handle() : params(nullptr), grads(nullptr), opt_state(nullptr), ws(nullptr), d_jt(nullptr), h_err(nullptr), d_err(nullptr),
                    no_roles(false), degraded(false), recoveries(0), last_code(0u), ar_fn(nullptr), ar_comm(nullptr) {}
     ~mmg_handle() {
@@ -385,6 +387,103 @@ static int build_jobs(mmg_handle* h) {
     }
     for (; blk < MMG_GN_BLOCKS; ++blk) { jt.np.begin[blk] = jt.np.end[blk] = 0; jt.np.agent[blk] = -1; }
     if (sizeof(JobTable) > 98304) return fail("job table does not fit its tape slot");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Job tables of mmg_exchange_vjp (kernels_vjp.h): one per agent, each writing only that agent's gradient slice.  Same job kinds as
+// build_jobs, but every (step, sample) job reduces over ALL T * B rows (rows of steps t >= n_steps carry zero deltas), no row
+// splits, no live-row list, no special block.  They depend on the shape only: built and uploaded once, at mmg_create.
+// ---------------------------------------------------------------------------------------------
+static int build_vjp_job_table(mmg_handle* h, int agent, JobTable& jt) {
+    memset(&jt, 0, sizeof(jt));
+    const Dims& d = h->dm;
+    const Tape& tp = h->tp;
+    const Params &G = h->G, &P = h->P;
+    const int B = d.B, H = d.H, W = d.W, R = d.R, V = d.V, K = d.K, D = d.D, F = d.F;
+    const int TB = d.T * B;
+    int tiles = 0, ng = 0, cblocks = 0, nc = 0;
+    auto gemm = [&](const float* A, int lda, const float* Bm, int ldb, int bmod, int bsrc, float* C, int ldc, int rows, int N, int Kk) {
+        GemmJob& g = jt.g[ng++];
+        g.A = A; g.Bm = Bm; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.rows = rows; g.N = N; g.K = Kk;
+        g.bmod = bmod; g.bsrc = bsrc; g.tile_begin = tiles; g.tiles_k = (Kk + 31) / 32;
+        g.vhid = nullptr; g.vw2 = nullptr; g.compact = 0; g.nsplit = 1;
+        tiles += ((N + 15) / 16) * g.tiles_k;
+    };
+    auto gemm_virt = [&](const float* dbeta, const float* hid, const float* w2, const float* Bm, int ldb, int bmod,
+                         float* C, int ldc, int rows, int N, int Kk) {
+        gemm(dbeta, N, Bm, ldb, bmod, SRC_STATIC, C, ldc, rows, N, Kk);
+        jt.g[ng - 1].vhid = hid; jt.g[ng - 1].vw2 = w2;
+    };
+    auto col = [&](const float* src, int ld, int rows, int cols, float* dst, const float* scale) -> ColJob& {
+        ColJob& c = jt.c[nc++];
+        c.src = src; c.dst = dst; c.scale = scale; c.ld = ld; c.rows = rows; c.cols = cols; c.blk_begin = cblocks;
+        c.vbeta = nullptr; c.vw2 = nullptr; c.wrow = nullptr; c.compact = 0; c.special = 0;
+        cblocks += (cols + 15) / 16;
+        return c;
+    };
+    const float* h_after = tp.h + (size_t)B * R;
+    if (agent == MMG_AGENT_RECEIVER) {
+        gemm(tp.vdgi, 3 * R, tp.z, W, 0, SRC_STATIC, G.p[R_WIH], W, TB, 3 * R, W);              // rnn.weight_ih
+        gemm(tp.vdgh, 3 * R, tp.h, R, 0, SRC_STATIC, G.p[R_WHH], R, TB, 3 * R, R);              // rnn.weight_hh (h before the step)
+        col(tp.vdgi, 3 * R, TB, 3 * R, G.p[R_BIH], nullptr);
+        col(tp.vdgh, 3 * R, TB, 3 * R, G.p[R_BHH], nullptr);
+        gemm(tp.vdA, R, h_after, R, 0, SRC_STATIC, G.p[R_Y1_W], R + V, TB, R, R);               // y1.weight[:, :R]: dA_t over T * B rows
+        gemm(tp.vdC, R, tp.vdesc, V, 0, SRC_STATIC, G.p[R_Y1_W] + R, R + V, D, R, V);          // y1.weight[:, R:]
+        col(tp.vdC, R, D, R, G.p[R_Y1_B], nullptr);
+        col(tp.vPy2, R, D, R, G.p[R_Y2_W], nullptr);
+        col(tp.vdys, 1, TB, 1, G.p[R_Y2_B], nullptr);
+        gemm(tp.vdgpre, R, h_after, R, 0, SRC_STATIC, G.p[R_WH_W], R, TB, R, R);               // w_h
+        col(tp.vdgpre, R, TB, R, G.p[R_WH_B], nullptr);
+        gemm(tp.vdgpre, R, tp.vdbar, V, 0, SRC_STATIC, G.p[R_WD_W], V, TB, R, V);              // w_d
+        gemm(tp.vdlw, W, tp.vg, R, 0, SRC_STATIC, G.p[R_W_W], R, TB, W, R);                    // w
+        col(tp.vdlw, W, TB, W, G.p[R_W_B], nullptr);
+        col(h_after, R, TB, R, G.p[R_S_W], nullptr).wrow = tp.vdls;                            // s.weight = dls^T . h_after
+        col(tp.vdls, 1, TB, 1, G.p[R_S_B], nullptr);
+    } else if (agent == MMG_AGENT_SENDER) {
+        gemm(tp.vdhx, H, nullptr, F, 0, SRC_X, G.p[S_IMG_W], F, B, H, F);                       // image_layer (sum over steps first)
+        col(tp.vdhx, H, B, H, G.p[S_IMG_B], nullptr);
+        gemm(tp.vdpre, H, tp.vc, W, 0, SRC_STATIC, G.p[S_CODE_W], W, TB, H, W);                 // code_layer (t = 0: sigmoid(code_bias))
+        col(tp.vdpre, H, TB, H, G.p[S_CODE_B], nullptr);
+        col(tp.vdc0, W, B, W, G.p[S_CODE_BIAS], tp.vdsig);                                      // code_bias
+        gemm(tp.vdlz, W, tp.va, H, 0, SRC_STATIC, G.p[S_BIN_W], H, TB, W, H);                   // binary_layer
+        col(tp.vdlz, W, TB, W, G.p[S_BIN_B], nullptr);
+    } else if (agent == MMG_AGENT_BASELINE_REC) {                                                // input [z || h_after]
+        gemm_virt(tp.vdbr, tp.vhid_r, P.p[BR_L2_W], tp.z, W, 0, G.p[BR_L1_W], W + R, TB, K, W);
+        gemm_virt(tp.vdbr, tp.vhid_r, P.p[BR_L2_W], h_after, R, 0, G.p[BR_L1_W] + W, W + R, TB, K, R);
+        ColJob& c1 = col(tp.vhid_r, K, TB, K, G.p[BR_L1_B], nullptr); c1.vbeta = tp.vdbr; c1.vw2 = P.p[BR_L2_W];
+        col(tp.vhid_r, K, TB, K, G.p[BR_L2_W], nullptr).wrow = tp.vdbr;
+        col(tp.vdbr, 1, TB, 1, G.p[BR_L2_B], nullptr);
+    } else {                                                                                    // input [h_x || z_r]
+        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], tp.hx, H, B, G.p[BS_L1_W], H + W, TB, K, H);
+        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], tp.vzr, W, 0, G.p[BS_L1_W] + H, H + W, TB, K, W);
+        ColJob& c1 = col(tp.vhid_s, K, TB, K, G.p[BS_L1_B], nullptr); c1.vbeta = tp.vdbs; c1.vw2 = P.p[BS_L2_W];
+        col(tp.vhid_s, K, TB, K, G.p[BS_L2_W], nullptr).wrow = tp.vdbs;
+        col(tp.vdbs, 1, TB, 1, G.p[BS_L2_B], nullptr);
+    }
+    jt.n_gemm = ng; jt.n_col = nc; jt.gemm_tiles = tiles; jt.gemm_blocks = tiles; jt.col_blocks = cblocks;
+    jt.n_wblocks = tiles + cblocks;
+    jt.special_block = -1; jt.special_job = -1;
+    for (int k = 0; k < 64; ++k) {
+        jt.g_begin[k] = k < ng ? jt.g[k].tile_begin : 0x7fffffff;
+        jt.c_begin[k] = k < nc ? jt.c[k].blk_begin : 0x7fffffff;
+    }
+    if (jt.n_wblocks > MMG_MAX_WBLOCKS) return fail("too many weight-gradient tiles in the VJP of agent %d (%d)", agent, jt.n_wblocks);
+    for (int k = 0; k < jt.n_wblocks; ++k) jt.wblock_agent[k] = (signed char)agent;
+    for (int k = 0; k < MMG_GN_BLOCKS; ++k) { jt.np.begin[k] = jt.np.end[k] = 0; jt.np.agent[k] = -1; }
+    return 0;
+}
+
+static int upload_vjp_tables(mmg_handle* h) {
+    static_assert(sizeof(JobTable) <= MMG_VJP_TABLE_BYTES, "a VJP job table does not fit its tape slot");
+    std::vector<JobTable> tabs(4);
+    for (int a = 0; a < 4; ++a) {
+        if (build_vjp_job_table(h, a, tabs[a])) return -1;
+        WgHead& hd = h->vjp_hd[a];
+        hd.gemm_tiles = tabs[a].gemm_tiles; hd.n_wblocks = tabs[a].n_wblocks; hd.special_block = -1; hd.special_job = -1;
+    }
+    for (int a = 0; a < 4; ++a)
+        HIP_OK(hipMemcpy(h->tp.vtables + (size_t)a * MMG_VJP_TABLE_BYTES, &tabs[a], sizeof(JobTable), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -703,6 +802,7 @@ extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int6
     }
     e = hipMemcpy(h->d_jt, &h->jt, sizeof(JobTable), hipMemcpyHostToDevice);
     if (e != hipSuccess) { fail("job table upload failed: %s", hipGetErrorString(e)); delete h; return nullptr; }
+    if (upload_vjp_tables(h)) { delete h; return nullptr; }
     return h;
 }
 
@@ -1558,4 +1658,70 @@ extern "C" int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, 
     }
     hipLaunchKernelGGL(k_baselines, dim3((rows + 15) / 16, 2), dim3(MMG_BLOCK), 0, st, d.K, rec, sen);
     return launch_check("k_baselines(agent)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// mmg_exchange_vjp: the backward pass of ONE agent's autograd graph of the last training exchange (kernels_vjp.h).  Reads the
+// run-all tape of mmg_exchange_forward(train = 1, run_all_steps = 1); writes only that agent's slice of the gradient buffer.
+// ---------------------------------------------------------------------------------------------
+extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
+                                const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
+                                void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (agent < 0 || agent > 3) return fail("unknown agent %d", agent);
+    if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
+    if (agent >= MMG_AGENT_BASELINE_REC && !d.use_binary) return fail("baseline scores exist in binary training only (model.py:834-843)");
+    hipStream_t st = (hipStream_t)stream;
+    VjpIn in;
+    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = d_dbs; in.dbr = d_dbr; in.n = n_steps;
+    if (agent == MMG_AGENT_RECEIVER) {
+        if (!d_desc) return fail("desc must not be NULL");
+        const size_t smem = sizeof(float) * (size_t)vjp_rec_smem_floats(d);
+        if (smem > 65536) return fail("the receiver VJP needs %zu bytes of LDS (too many classes)", smem);
+        {
+            Scope sc(h, st, "k_vjp_cd");
+            hipLaunchKernelGGL(k_vjp_cd, dim3(d.D), dim3(MMG_BLOCK), 0, st, d, h->P, h->tp, d_desc);
+            if (launch_check("k_vjp_cd")) return -1;
+        }
+        {
+            Scope sc(h, st, "k_vjp_rec");
+            hipLaunchKernelGGL(k_vjp_rec, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in);
+            if (launch_check("k_vjp_rec")) return -1;
+        }
+        {
+            Scope sc(h, st, "k_vjp_class");
+            hipLaunchKernelGGL(k_vjp_class, dim3(d.D), dim3(MMG_BLOCK), 0, st, d, h->P, h->tp, in);
+            if (launch_check("k_vjp_class")) return -1;
+        }
+    } else if (agent == MMG_AGENT_SENDER) {
+        if (!d_x) return fail("x must not be NULL");
+        const size_t smem = sizeof(float) * (size_t)vjp_sen_smem_floats(d);
+        if (smem > 65536) return fail("the sender VJP needs %zu bytes of LDS (h_dim too large)", smem);
+        Scope sc(h, st, "k_vjp_sen");
+        hipLaunchKernelGGL(k_vjp_sen, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in);
+        if (launch_check("k_vjp_sen")) return -1;
+    } else {
+        const size_t smem = sizeof(float) * (size_t)(agent == MMG_AGENT_BASELINE_REC ? d.W + d.R : d.H + d.W);
+        if (smem > 65536) return fail("the baseline VJP needs %zu bytes of LDS", smem);
+        Scope sc(h, st, "k_vjp_bas");
+        hipLaunchKernelGGL(k_vjp_bas, dim3(d.T * d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in, agent);
+        if (launch_check("k_vjp_bas")) return -1;
+    }
+    // the weight gradients: k_wgrad over the agent's own job table -- its tiles and column blocks only (no spare block: the
+    // logged losses, running totals and gradient tail stay untouched), no live-row list
+    const JobTable* djt = reinterpret_cast<const JobTable*>(h->tp.vtables + (size_t)agent * MMG_VJP_TABLE_BYTES);
+    const WgHead hd = h->vjp_hd[agent];
+    WgOpt wo;
+    memset(&wo, 0, sizeof(wo));
+    Scope sc(h, st, "k_wgrad");
+    hipLaunchKernelGGL(k_wgrad<false>, dim3(hd.n_wblocks), dim3(MMG_BLOCK), 0, st,
+                       djt, d_x, d_desc, h->tp.gnpart, h->dm, (const double*)h->tp.stats, h->tp.losses, h->tp.totals,
+                       (const int*)nullptr, (const int*)nullptr, h->tp.wpart, reinterpret_cast<uint32_t*>(h->tp.wcnt),
+                       (const uint32_t*)h->tp.sync, h->grads + h->pl.total, wo, 0, hd
+#ifdef MMG_TIMING
+                       , h->tp.dbg2
+#endif
+                       );
+    return launch_check("k_wgrad");
 }

@@ -67,6 +67,9 @@ class Engine(object):
             nbytes = numel * torch.empty((), dtype=dt).element_size()
             self.tape[e["name"]] = self.workspace[e["offset"]:e["offset"] + nbytes].view(dt).view(e["dims"])
         self.stats = self.tape["stats"]
+        # bumped by every call that rewrites the forward tape (forward, train_step(s), dp_*, the agent-level forwards): an autograd
+        # node of Game.exchange() refuses to run its VJP on a tape that is no longer the one its forward left
+        self.generation = 0
 
     def __del__(self):
         try:
@@ -108,6 +111,7 @@ class Engine(object):
         every step becomes |z - m| before the receiver reads it (model.py:813-820).  The mask is set for this call only: the
         engine may serve a training step next."""
         f32 = torch.float32
+        self.generation += 1
         if corrupt_mask is not None:
             if train:
                 raise NotImplementedError("message corruption applies to evaluation conversations only (model.py:637-638)")
@@ -150,6 +154,7 @@ class Engine(object):
 
     def train_step(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0):
         f32 = torch.float32
+        self.generation += 1
         _lib.check(self.lib.mmg_train_step(
             self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
             self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed), self._stream()))
@@ -159,6 +164,7 @@ class Engine(object):
         (include/mmg.h: mmg_train_steps)."""
         B = self.cfg.batch
         assert x.size(0) >= n * B and target.size(0) >= n * B
+        self.generation += 1
         _lib.check(self.lib.mmg_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                             self._ptr(desc, torch.float32), C.c_uint64(seed), self._stream()))
 
@@ -168,6 +174,7 @@ class Engine(object):
 
     def dp_train_step(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0, full_tape=False, reduce=True):
         f32 = torch.float32
+        self.generation += 1
         _lib.check(self.lib.mmg_dp_train_step(
             self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
             self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed), int(bool(full_tape)), int(bool(reduce)),
@@ -176,6 +183,7 @@ class Engine(object):
     def dp_train_steps(self, x, target, desc, n, seed=0, reduce=True):
         B = self.cfg.batch
         assert x.size(0) >= n * B and target.size(0) >= n * B
+        self.generation += 1
         _lib.check(self.lib.mmg_dp_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                                self._ptr(desc, torch.float32), C.c_uint64(seed), int(bool(reduce)), self._stream()))
 
@@ -199,6 +207,7 @@ class Engine(object):
     # ------------------------------------------------------------------ agent-level steps
     def sender_forward(self, x, w, t, train, u_z=None, seed=0):
         B, W, H = self.cfg.batch, self.cfg.w_dim, self.cfg.h_dim
+        self.generation += 1
         msg = torch.empty(B, W, device=self.device)
         probs = torch.empty(B, W, device=self.device) if self.cfg.use_binary else None
         h_x = torch.empty(B, H, device=self.device)
@@ -210,6 +219,7 @@ class Engine(object):
     def receiver_forward(self, z, desc, h_z, s_prob_prod, first, t, train, u_s=None, u_w=None, seed=0):
         B, W, R, D = self.cfg.batch, self.cfg.w_dim, self.cfg.rec_hidden, self.cfg.n_classes
         dev = self.device
+        self.generation += 1
         s, s_prob = torch.empty(B, 1, device=dev), torch.empty(B, 1, device=dev)
         w = torch.empty(B, W, device=dev)
         w_probs = torch.empty(B, W, device=dev) if self.cfg.use_binary else None
@@ -222,10 +232,31 @@ class Engine(object):
 
     def baseline_forward(self, which, x, binary, inp):
         rows = binary.shape[0]
+        self.generation += 1
         score = torch.empty(rows, 1, device=self.device)
         _lib.check(self.lib.mmg_baseline_forward(self.handle, _lib.AGENTS.index(which), self._ptr(x), self._ptr(binary),
                                                  self._ptr(inp), rows, self._ptr(score), self._stream()))
         return score
+
+    # ------------------------------------------------------------------ vector-Jacobian products
+    def vjp(self, agent, n_steps, x, desc, dy=None, dz=None, dw=None, dps=None, dbs=None, dbr=None):
+        """Backward pass of ONE agent's graph of the last training run-all forward (include/mmg.h: mmg_exchange_vjp): writes that
+        agent's slice of the gradient buffer (self.grads[agent]) from the upstream gradients of its outputs over the n_steps
+        executed steps -- dy [n, B, D], dz / dw [n, B, W] (probabilities when binary, logits when continuous), dps / dbs / dbr
+        [n, B] or [n, B, 1]; None = zero.  The caller checks that the tape is still the forward's (self.generation)."""
+        f32 = torch.float32
+        shapes = dict(dy=self.cfg.n_classes, dz=self.cfg.w_dim, dw=self.cfg.w_dim, dps=1, dbs=1, dbr=1)
+        args = {}
+        for k, g in (("dy", dy), ("dz", dz), ("dw", dw), ("dps", dps), ("dbs", dbs), ("dbr", dbr)):
+            if g is not None:
+                g = g.to(self.device, f32).contiguous()
+                if g.numel() != n_steps * self.cfg.batch * shapes[k]:
+                    raise ValueError("%s: %d entries for %d steps x %d samples x %d" % (k, g.numel(), n_steps, self.cfg.batch, shapes[k]))
+            args[k] = g
+        _lib.check(self.lib.mmg_exchange_vjp(
+            self.handle, _lib.AGENTS.index(agent), int(n_steps), self._ptr(x, f32), self._ptr(desc, f32),
+            self._ptr(args["dy"]), self._ptr(args["dz"]), self._ptr(args["dw"]), self._ptr(args["dps"]),
+            self._ptr(args["dbs"]), self._ptr(args["dbr"]), self._stream()))
 
     # ------------------------------------------------------------------ profiling
     def set_profiling(self, on):

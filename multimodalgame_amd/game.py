@@ -1,10 +1,77 @@
 """exchange() and the per-minibatch training block of the reference (model.py:725-876, 1240-1339)
 on top of the HIP engine, with the reference's calling conventions and return structures."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import flags as _flags
 from . import misc
 from .engine import Engine
+
+
+class _AgentVJP(torch.autograd.Function):
+    """One agent's graph of a training exchange() as ONE autograd node (the reference's four graphs are disjoint: every input
+    crossing between agents is detached, model.py:807-811, 826-829, 835-843).  Inputs: a spec (engine, tape generation, steps,
+    the forward's x / desc, the tape arrays to hand out) and the agent's parameters; outputs: the agent's differentiable outputs
+    stacked over the executed steps, [n, B, .] copies of the tape.  backward runs the agent's HIP VJP (Engine.vjp) and returns
+    copies of its gradient slice."""
+    AGENT = None
+    KEYS = ()          # Engine.vjp keyword of each output's gradient
+
+    @staticmethod
+    def forward(ctx, spec, *params):
+        ctx.spec = spec
+        ctx.set_materialize_grads(False)               # (an unused output: a NULL upstream gradient, i.e. zero)
+        ctx.save_for_backward(*params)                 # a second backward / an in-place update of the parameters raise
+        return tuple(t.clone() for t in spec["outs"])
+
+    @classmethod
+    def _backward(cls, ctx, grads):
+        ctx.saved_tensors                              # (raises once freed: backward through this node a second time)
+        spec = ctx.spec
+        eng = spec["eng"]
+        if eng.generation != spec["gen"]:
+            raise RuntimeError("the exchange tape this %s node was recorded on has been overwritten by a later engine call "
+                               "(exchange / train_step / forward): call backward() before the next one" % cls.AGENT)
+        eng.vjp(cls.AGENT, spec["n"], spec["x"], spec["desc"],
+                **{k: g for k, g in zip(cls.KEYS, grads) if g is not None})
+        views = eng.grads[cls.AGENT]
+        return (None,) + tuple(views[name].clone() for name in spec["names"])
+
+
+class _SenderVJP(_AgentVJP):
+    AGENT, KEYS = "sender", ("dz",)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _SenderVJP._backward(ctx, grads)
+
+
+class _ReceiverVJP(_AgentVJP):
+    AGENT, KEYS = "receiver", ("dy", "dps", "dw")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _ReceiverVJP._backward(ctx, grads)
+
+
+class _BaselineSenVJP(_AgentVJP):
+    AGENT, KEYS = "baseline_sen", ("dbs",)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _BaselineSenVJP._backward(ctx, grads)
+
+
+class _BaselineRecVJP(_AgentVJP):
+    AGENT, KEYS = "baseline_rec", ("dbr",)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _BaselineRecVJP._backward(ctx, grads)
 
 
 class FlatOptimizer(object):
@@ -72,9 +139,11 @@ class FlatOptimizer(object):
 
 class Game(object):
     """Binds the four agent modules to one flat parameter buffer on the GPU and caches one libmmg
-    handle per (batch size, number of classes)."""
+    handle per (batch size, number of classes).
 
-    def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0):
+    autograd=True: training exchange() calls return outputs that carry autograd graphs (see exchange())."""
+
+    def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -90,6 +159,7 @@ class Game(object):
         assert sender.bin_dim_out == sender.w_dim == receiver.w_dim == receiver.z_dim, \
             "Both sender and receiver should communicate with same dim vectors for now."     # model.py:1756
         self.seed = seed
+        self.autograd = bool(autograd)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -146,9 +216,24 @@ class Game(object):
 
     # ------------------------------------------------------------------ model.py:725-876
     def exchange(self, exchange_args):
+        """model.py:725-876: ``(s, sen_w, rec_w, y, bs, br)`` of per-step tensor lists, copies of the engine's tape.
+
+        Autograd (opt-in): with ``exchange_args["autograd"] = True`` (or ``Game(..., autograd=True)``), ``train`` true and
+        ``torch.is_grad_enabled()``, the differentiable outputs carry a ``grad_fn``, one autograd node per agent as in the
+        reference: the sender's ``sen_probs[t]`` (binary) / ``sen_feats[t]`` (continuous logits); the receiver's ``y[t]``,
+        ``s_probs[t]`` and ``rec_probs[t]`` (binary) / ``rec_feats[t]`` (continuous logits); ``bs[t]`` / ``br[t]`` (binary).
+        ``backward()`` on any scalar built from them runs the agents' HIP vector-Jacobian products (include/mmg.h:
+        mmg_exchange_vjp) and fills ``p.grad`` of the modules' parameters, so that ``clip_grad_norm_`` and ``torch.optim``
+        work as in the reference (model.py:1307-1330).  Constants, as in the reference: the sampled bits, the masks, data,
+        desc.  ``sender.h_x``, ``receiver.h_z`` and ``receiver.h_w`` stay plain tensors (no gradient flows into them).
+        The nodes read the engine's tape: backward() must run before the next exchange / train_step on the same batch shape
+        (a stale tape raises RuntimeError).  Otherwise exchange() returns exactly what it returns without autograd."""
         data, target, desc = exchange_args["data"], exchange_args.get("target"), exchange_args["desc"]
         train = exchange_args["train"]
         break_early = exchange_args.get("break_early", False)
+        autograd = bool(exchange_args.get("autograd", self.autograd)) and bool(train) and torch.is_grad_enabled()
+        if autograd and self.world > 1:
+            raise NotImplementedError("autograd through exchange() runs on one GPU only (data-parallel training: Game.train_step)")
         corrupt_mask = None
         if exchange_args.get("corrupt", False):                          # model.py:813-820 (eval_dev's call, model.py:637-638)
             if train:
@@ -166,7 +251,11 @@ class Game(object):
         desc = desc.to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
         self._call += 1
-        eng.forward(data, target, desc, seed=self.seed, train=train, run_all=True,
+        # exchange_args["uniforms"] (training): (u_z [T, B, W], u_s [T, B], u_w [T, B, W]) in place of the Philox stream -- the
+        # reference's numpy draws (model.py:227, 420, 460), for tests that replay one conversation on two paths
+        u = exchange_args.get("uniforms") if train else None
+        u = [None if v is None else torch.as_tensor(v).to(dev, torch.float32).contiguous() for v in (u or (None, None, None))]
+        eng.forward(data, target, desc, u[0], u[1], u[2], seed=self.seed, train=train, run_all=True,
                     **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         tp = eng.tape
         T = self.max_exchange
@@ -180,15 +269,42 @@ class Game(object):
         binary = self.cfg["use_binary"]
         masks = [tp["mask"][t].clone() for t in range(n + 1)]
         masks[-1].zero_()                                                 # model.py:870
+        self.modules["sender"].h_x = tp["hx"]
+        self.modules["receiver"].h_z = tp["h"][n]
+        self.modules["receiver"].h_w = tp["g"][n - 1]
+        if autograd:
+            return self._exchange_graph(eng, data, desc, n, masks)
         s = (masks, [tp["s"][t].clone() for t in range(n)], [tp["ps"][t].clone() for t in range(n)])
         sen_w = ([tp["z"][t].clone() for t in range(n)], [tp["pz"][t].clone() if binary else None for t in range(n)])
         rec_w = ([tp["w"][t].clone() for t in range(n)], [tp["pw"][t].clone() if binary else None for t in range(n)])
         y = [tp["y"][t].clone() for t in range(n)]
         bs = [tp["bs"][t].clone() for t in range(n)] if train and binary else []
         br = [tp["br"][t].clone() for t in range(n)] if train and binary else []
-        self.modules["sender"].h_x = tp["hx"]
-        self.modules["receiver"].h_z = tp["h"][n]
-        self.modules["receiver"].h_w = tp["g"][n - 1]
+        return s, sen_w, rec_w, y, bs, br
+
+    def _exchange_graph(self, eng, data, desc, n, masks):
+        """exchange()'s return structure with the four agents' autograd nodes (training, run-all tape of this call)."""
+        tp, binary = eng.tape, self.cfg["use_binary"]
+
+        def node(fn, agent, outs):
+            mod = self.modules[agent]
+            names = [name for name, _ in mod.named_parameters()]
+            spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=names, outs=outs)
+            return fn.apply(spec, *[p for _, p in mod.named_parameters()])
+
+        sen = node(_SenderVJP, "sender", [tp["pz" if binary else "z"][:n]])[0].unbind(0)
+        y_st, ps_st, w_st = node(_ReceiverVJP, "receiver", [tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
+        ps, rw, y = ps_st.unbind(0), w_st.unbind(0), list(y_st.unbind(0))
+        s = (masks, [tp["s"][t].clone() for t in range(n)], list(ps))
+        if binary:
+            sen_w = ([tp["z"][t].clone() for t in range(n)], list(sen))
+            rec_w = ([tp["w"][t].clone() for t in range(n)], list(rw))
+            bs = list(node(_BaselineSenVJP, "baseline_sen", [tp["bs"][:n]])[0].unbind(0))
+            br = list(node(_BaselineRecVJP, "baseline_rec", [tp["br"][:n]])[0].unbind(0))
+        else:
+            sen_w = (list(sen), [None] * n)
+            rec_w = (list(rw), [None] * n)
+            bs, br = [], []
         return s, sen_w, rec_w, y, bs, br
 
     def eval_forward(self, data, target, desc, corrupt_mask=None):
