@@ -10,7 +10,10 @@ own: one exchange step of one 64-sample batch ("bs=64").  At N GPUs the global m
 every exchange step of the sharded game advances N such batches, so value = N * loop iterations / wall time
 (the whole-job aggregate; identical to the 1-GPU definition at N = 1).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.  --full goes on
+  after the timed steps: the per-kernel roofline pass, the 2 s window (value_window) and, for the default workload, the other
+  BASELINE.json configs, the shipped training loop and the CPU baseline (N = 1) or the strong-scaling configs (N > 1).
   N > 1: one rank per GPU; the global minibatch is 64*N (weak scaling), sharded along the batch axis
   (multimodalgame_amd/dist.py).  Either the caller launches the ranks (torch.distributed.run sets WORLD_SIZE / RANK /
   LOCAL_RANK) or -- plain `python bench.py --gpus N` -- this script re-executes itself under
@@ -304,8 +307,10 @@ def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
     return written
 
 
-def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False):
-    """Times `steps` training minibatches of one workload (repeated until MIN_TIMED_SECONDS); returns a dict.
+def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False, full=True):
+    """Times `steps` training minibatches of one workload; returns a dict.
+    full: then also the per-kernel pass (if want_roofline), the long window (passes of `steps` repeated until
+    MIN_TIMED_SECONDS) and the collectives' us (N > 1); without it the run ends after the timed steps.
     outputs: res["outputs"] = host copies of what a caller of the timed path holds after its last step."""
     from multimodalgame_amd.engine import Engine
     from multimodalgame_amd.dist import DataParallel
@@ -324,7 +329,8 @@ def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=
     # random-init agents (reference init: Xavier-normal weights, zero biases, N(0,1) code_bias; baselines torch-default
     # uniform) from a fixed seed -- identical on every rank
     eng.load_state_dicts(init_state_dicts(eng, seed=0))
-    # warm-up + the timed --steps + the per-kernel pass all draw FRESH minibatches (no sample repeats before the window below)
+    # warm-up + the timed --steps + the per-kernel pass all draw FRESH minibatches (no sample repeats before the window below);
+    # sized the same with and without `full`, so that the synthetic file -- the timed steps' inputs -- does not depend on it
     n_cycle = min(steps + warmup + 20, 1024)
     xs, ts, desc_d = build_batches(CFG, Bg, B, rank, n_cycle, dev)
     dp = DataParallel(eng)
@@ -366,6 +372,19 @@ def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=
         timed_outputs = {k: v.detach().cpu().numpy().copy() for k, v in (
             ("params", eng.flat_params), ("grads", eng.flat_grads[:eng.n_params]), ("opt_state", eng.opt_state),
             ("losses", eng.tape["losses"]))}
+    collective = "none (single rank)"
+    if world > 1:
+        collective = ("direct RCCL communicator on the engine's stream (multimodalgame_amd/rccl.py), world %d" % dp.comm.world
+                      if dp.comm is not None else "torch.distributed.all_reduce, backend %s" % dist.get_backend())
+    res = dict(workload=workload, label=label, B=B, Bg=Bg, cfg=CFG, collective=collective,
+               first_pass_ms_per_minibatch=1e3 * first_elapsed / steps, first_pass_steps_per_minibatch=first_steps / steps,
+               first_pass_ex_steps=first_steps, first_pass_seconds=first_elapsed,
+               first_pass_sample_steps=float(totals_first[3] - totals_before[3]),
+               degraded=eng.degraded(), dist_world=(dist.get_world_size() if world > 1 else 1), outputs=timed_outputs)
+    if not full:
+        eng.check_sync()                                            # no in-launch dependency wait may have timed out
+        del eng
+        return res
     done = steps
     # ---- per-kernel durations at THIS point of the trajectory (right after the first pass, before the window trains the agents
     # further): HIP events on the launch stream (library hook mmg_set_profiling; rank 0 records, every rank runs the steps:
@@ -417,17 +436,9 @@ def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=
     sample_steps = float(totals_after[3] - totals_w0[3])            # sum_t n_active,t over the GLOBAL minibatches
     tstar_window = eng.tape["tstar"].float().mean().item() + 1.0    # live (step, sample) rows per sample at the END of the window
     eng.check_sync()                                                # no in-launch dependency wait may have timed out
-    collective, coll_us = "none (single rank)", None
-    if world > 1:
-        collective = ("direct RCCL communicator on the engine's stream (multimodalgame_amd/rccl.py), world %d" % dp.comm.world
-                      if dp.comm is not None else "torch.distributed.all_reduce, backend %s" % dist.get_backend())
-        coll_us = collective_us(dp, eng, dev)
-    res = dict(workload=workload, label=label, B=B, Bg=Bg, elapsed=elapsed, minibatches=timed_mb, ex_steps=ex_steps,
-               sample_steps=sample_steps, cfg=CFG, roofline=None, collective=collective, collective_us=coll_us,
-               first_pass_ms_per_minibatch=1e3 * first_elapsed / steps, first_pass_steps_per_minibatch=first_steps / steps,
-               first_pass_ex_steps=first_steps, first_pass_seconds=first_elapsed,
-               first_pass_sample_steps=float(totals_first[3] - totals_before[3]), window_live_rows_per_sample=tstar_window,
-               degraded=eng.degraded(), dist_world=(dist.get_world_size() if world > 1 else 1), outputs=timed_outputs)
+    res.update(elapsed=elapsed, minibatches=timed_mb, ex_steps=ex_steps, sample_steps=sample_steps, roofline=None,
+               collective_us=(collective_us(dp, eng, dev) if world > 1 else None), window_live_rows_per_sample=tstar_window,
+               degraded=eng.degraded())
     if want_roofline and rank == 0:
         avg = {k: float(np.mean(v)) for k, v in kern_ms.items()}           # ms per minibatch, HIP events (raw brackets)
         n_params = sum(e["rows"] * max(e["cols"], 1) for e in eng.param_entries)
@@ -637,10 +648,14 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short c3 / c4 / c5 runs of the default invocation")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the per-kernel pass (roofline), the 2 s "
+                         "window (value_window) and, for the default workload, the other configs, the shipped loop and the CPU baseline "
+                         "(N = 1) or the strong-scaling configs and the per-collective times (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short c3 / c4 / c5 runs")
     ap.add_argument("--cli", action="store_true", help="only time the shipped training loop (model.run() on synthetic HDF5) and print its numbers")
-    ap.add_argument("--no-cli", action="store_true", help="skip the model.run() measurement of the default invocation (config.cli_steps_per_s)")
+    ap.add_argument("--no-cli", action="store_true", help="with --full: skip the model.run() measurement (config.cli_steps_per_s)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="c2 = BASELINE.json's metric config (default); c3/c4/c5 = the other listed configs, for reference")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
@@ -678,52 +693,60 @@ def main():
         # "nccl" is RCCL on ROCm; MMG_BENCH_BACKEND=gloo only exists to smoke-test this code path on a 1-GPU box
         dist.init_process_group(os.environ.get("MMG_BENCH_BACKEND", "nccl"), rank=rank, world_size=world)
     strong = args.scaling == "strong"
-    r = run_workload(args.workload, args.steps, args.warmup, args.seed, rank, world, local_rank, strong=strong,
+    r = run_workload(args.workload, args.steps, args.warmup, args.seed, rank, world, local_rank, strong=strong, full=args.full,
                      **(dict(outputs=True) if args.dump_outputs else {}))
     if rank == 0 and args.dump_outputs:
         dumped = dump_outputs(r["outputs"], args.dump_outputs)
     if rank == 0:
-        per_mb = r["elapsed"] / r["minibatches"]
         unit_batch = r["Bg"] if strong else WORKLOADS[args.workload][1]
         # weak: one unit = an exchange step of one per-GPU-sized batch, a global minibatch of B*N samples advances N of them;
         # strong: one unit = an exchange step of the fixed global batch
-        value_window = (1.0 if strong else world) * r["ex_steps"] / r["elapsed"]
         value = value_first = (1.0 if strong else world) * r["first_pass_ex_steps"] / r["first_pass_seconds"]
         per_mb = r["first_pass_seconds"] / args.steps
         line = {
             "metric": ("exchange-steps/sec (whole node), 30-class Adaptive max_exchange=10 bs=64" if args.workload == "c2" else
                        "exchange-steps/sec (whole node) of reference workload %s -- NOT BASELINE.json's metric" % args.workload),
-            "value": value, "value_window": value_window, "value_first_pass": value_first, "unit": "exchange-steps/s", "n_gpus": world, "steps": args.steps,
+            "value": value}
+        if args.full:
+            value_window = (1.0 if strong else world) * r["ex_steps"] / r["elapsed"]
+            line["value_window"] = value_window
+        line.update({
+            "value_first_pass": value_first, "unit": "exchange-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * per_mb, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": r["label"], "global_batch": r["Bg"], "per_gpu_batch": r["B"], "parallelism": "dp%d" % world,
-                       "rccl_world": r["dist_world"], "collective": r["collective"], "collective_us": r["collective_us"],
-                       "value_definition": "EXACTLY --steps training minibatches after --warmup untimed ones, from the seed-0 initialisation, every "
-                                           "minibatch drawn fresh (no sample repeats), barrier + device synchronisation on both sides: the same point of "
-                                           "the same training trajectory in every round and on every box (value_first_pass = value; rounds 2-5 reported "
-                                           "the long window as value)",
-                       "exchange_steps_per_minibatch": r["first_pass_steps_per_minibatch"], "sampling": "in-kernel Philox4x32-10",
-                       "first_pass_ms_per_minibatch": r["first_pass_ms_per_minibatch"],
-                       "first_pass_exchange_steps_per_minibatch": r["first_pass_steps_per_minibatch"],
-                       "timed_minibatches": args.steps, "timed_seconds": r["first_pass_seconds"],
-                       "minibatches_per_s": (1.0 if strong else world) * args.steps / r["first_pass_seconds"],
-                       "sample_steps_per_s": r.get("first_pass_sample_steps", 0.0) / r["first_pass_seconds"],       # sum_t n_active,t per second, whole job
-                       "fail_soft_degraded": r.get("degraded", 0),
-                       # the %g s window that FOLLOWS the timed region (cycling the resident minibatches: many epochs of training, the
-                       # conversations lengthen): value_window and what the agents had become by its end
-                       "window": {"value": value_window, "seconds": r["elapsed"], "minibatches": r["minibatches"],
-                                  "ms_per_minibatch": 1e3 * r["elapsed"] / r["minibatches"],
-                                  "exchange_steps_per_minibatch": r["ex_steps"] / r["minibatches"],
-                                  "sample_steps_per_s": r["sample_steps"] / r["elapsed"],
-                                  "live_rows_per_sample_at_end": r.get("window_live_rows_per_sample")},
-                       "unit_definition": "one exchange step (model.py:801 loop iteration) of one %d-sample batch%s" % (
-                           unit_batch, " (the fixed global minibatch, sharded over the ranks)" if strong else
-                           "; a global minibatch of %d*N samples advances N of them per iteration" % unit_batch)},
-            "roofline": r["roofline"],
-        }
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full})
+        config = {"workload": r["label"], "global_batch": r["Bg"], "per_gpu_batch": r["B"], "parallelism": "dp%d" % world,
+                  "rccl_world": r["dist_world"], "collective": r["collective"]}
+        if args.full:
+            config["collective_us"] = r["collective_us"]
+        config.update({
+            "value_definition": "EXACTLY --steps training minibatches after --warmup untimed ones, from the seed-0 initialisation, every "
+                                "minibatch drawn fresh (no sample repeats), barrier + device synchronisation on both sides: the same point of "
+                                "the same training trajectory in every round and on every box (value_first_pass = value; rounds 2-5 reported "
+                                "the long window as value)",
+            "exchange_steps_per_minibatch": r["first_pass_steps_per_minibatch"], "sampling": "in-kernel Philox4x32-10",
+            "first_pass_ms_per_minibatch": r["first_pass_ms_per_minibatch"],
+            "first_pass_exchange_steps_per_minibatch": r["first_pass_steps_per_minibatch"],
+            "timed_minibatches": args.steps, "timed_seconds": r["first_pass_seconds"],
+            "minibatches_per_s": (1.0 if strong else world) * args.steps / r["first_pass_seconds"],
+            "sample_steps_per_s": r.get("first_pass_sample_steps", 0.0) / r["first_pass_seconds"],       # sum_t n_active,t per second, whole job
+            "fail_soft_degraded": r.get("degraded", 0)})
+        if args.full:
+            # the %g s window that FOLLOWS the timed region (cycling the resident minibatches: many epochs of training, the
+            # conversations lengthen): value_window and what the agents had become by its end
+            config["window"] = {"value": value_window, "seconds": r["elapsed"], "minibatches": r["minibatches"],
+                                "ms_per_minibatch": 1e3 * r["elapsed"] / r["minibatches"],
+                                "exchange_steps_per_minibatch": r["ex_steps"] / r["minibatches"],
+                                "sample_steps_per_s": r["sample_steps"] / r["elapsed"],
+                                "live_rows_per_sample_at_end": r.get("window_live_rows_per_sample")}
+        config["unit_definition"] = "one exchange step (model.py:801 loop iteration) of one %d-sample batch%s" % (
+            unit_batch, " (the fixed global minibatch, sharded over the ranks)" if strong else
+            "; a global minibatch of %d*N samples advances N of them per iteration" % unit_batch)
+        line["config"] = config
+        if args.full:
+            line["roofline"] = r["roofline"]
         if args.dump_outputs:
             line["dump_outputs"] = {"dir": args.dump_outputs, "entries": dumped}
-        if world == 1 and args.workload == "c2" and not args.no_other_configs:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_other_configs:
             # the other BASELINE.json configs on this GPU (short runs; parity-test cases, not the metric)
             other = {}
             # c3s / c5s: the whole global batch (512 / 2048 samples) on this one GPU = the N = 1 point of --scaling strong;
@@ -740,7 +763,7 @@ def main():
                                                                   "rocprof_kernel", "rocprof_avg_us", "rocprof_source", "frac_rocprof", "sec8d_bytes_per_minibatch", "step_frac", "launches_per_minibatch", "conversation_flop")},
                                 kernels_us=rf.get("kernels_us"))
             line["other_configs"] = other
-        if world == 1 and args.workload == "c2" and not args.no_cli and not strong:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_cli and not strong:
             # what `python -m multimodalgame_amd.model` sustains end to end (same GPU, right after the HBM-resident measurement)
             # (ONE nested object: the driver's record keeps the first keys of `config` only -- VERDICT r05 weak 10)
             cli = run_cli()
@@ -748,7 +771,7 @@ def main():
             cli["cli_ms_over_resident_window_ms"] = cli["cli_ms_per_minibatch"] / (1e3 * r["elapsed"] / r["minibatches"])
             cli.update(run_cli(log_dev=1000))
             line["config"] = dict(cli=cli, **line["config"])
-        if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
             line["cpu_baseline"] = cpu_baseline()
             cb = line["cpu_baseline"]
             # both legs from the same initial weights: the GPU's FIRST PASS is the leg at the CPU sample's conversation length
@@ -756,7 +779,7 @@ def main():
             cb["gpu_first_pass_exchange_steps_per_minibatch"] = r["first_pass_steps_per_minibatch"]
     # N > 1, default workload: the SURVEY.md 8(d) whole-node figures -- the GLOBAL batch of configs[2] (512) and configs[4] (2048)
     # sharded over the ranks (strong scaling) -- in the SAME line, so that one driver invocation per N yields them
-    if world > 1 and args.workload == "c2" and not strong and not args.no_other_configs:
+    if args.full and world > 1 and args.workload == "c2" and not strong and not args.no_other_configs:
         sc = {}
         for w in ("c3", "c5"):
             if STRONG_GLOBAL_BATCH[w] % world:

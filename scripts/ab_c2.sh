@@ -3,7 +3,7 @@
 #   scripts/ab_c2.sh "VAR=1" ["VAR2=1" ...]   -> first-pass us per minibatch + HIP-event kernel averages, default build first
 export MMG_BENCH_MIN_SECONDS=${MMG_BENCH_MIN_SECONDS:-0.5}
 W=${W:-c2}
-run() { env $1 python bench.py --workload $W --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs --no-cli 2>/dev/null | python -c "
+run() { env $1 python bench.py --workload $W --steps 200 --warmup 20 --full --no-cpu-baseline --no-other-configs --no-cli 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 c=d['config']

@@ -6,7 +6,7 @@ export MMG_BENCH_MIN_SECONDS=0.2
 for mode in generic mc; do
   rm -rf /tmp/l2_$mode
   if [ $mode = generic ]; then export MMG_NO_MC=1; else unset MMG_NO_MC; fi
-  timeout 300 rocprofv3 --pmc TCC_REQ_sum TCC_READ_sum TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d /tmp/l2_$mode -o l2 -- python $R/bench.py --workload c5 --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs > /dev/null 2> /tmp/l2_$mode.err
+  timeout 300 rocprofv3 --pmc TCC_REQ_sum TCC_READ_sum TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d /tmp/l2_$mode -o l2 -- python $R/bench.py --workload c5 --steps 30 --warmup 5 --full --no-cpu-baseline --no-other-configs > /dev/null 2> /tmp/l2_$mode.err
   tail -n 1 /tmp/l2_$mode.err
 done
 unset MMG_NO_MC

@@ -18,7 +18,7 @@ profile_workload() {   # <workload> <"" | strong>
   [ -n "$STRONG" ] && EXTRA="--scaling strong"
   ( cd /tmp && export TMPDIR=/tmp
     export MMG_BENCH_MIN_SECONDS=${MMG_BENCH_MIN_SECONDS:-0.3}     # (short timed window: the traces stay small; the un-profiled bench uses 2 s)
-    CMD="python $R/bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs --no-cli $EXTRA"
+    CMD="python $R/bench.py --workload $W --steps 30 --warmup 5 --full --no-cpu-baseline --no-other-configs --no-cli $EXTRA"
     rm -rf /tmp/ks /tmp/pf /tmp/pw /tmp/pc /tmp/pd
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o ks -- $CMD > $O/${NAME}_bench_under_rocprof.json 2> /tmp/ks.err
     find /tmp/ks -name "*kernel_stats.csv" -exec cp {} $O/${NAME}_kernel_stats.csv \;
@@ -39,7 +39,7 @@ profile_workload c3 strong
 profile_workload c5 strong
 # the un-profiled line AFTER the profiles: bench.py names its dominant kernel from the newest summary under profiles/, so the
 # caller copies this run's *_kernel_stats.csv / *_pmc_hbm_traffic.json there first when the line is to cite them
-python bench.py > $O/${TAG}_bench_line.json 2> /dev/null
+python bench.py --full > $O/${TAG}_bench_line.json 2> /dev/null
 timeout 300 python scripts/dp_overhead.py 2>&1 | grep -v "^/opt\|^\[W" > $O/${TAG}_dp_overhead.log
 timeout 300 python scripts/game_timeline.py 2>&1 | grep -v "^/opt\|hipcc" > $O/${TAG}_game_timeline_c2.log
 timeout 300 python scripts/tile_timeline.py c4 2>&1 | grep -v "^/opt\|hipcc\|Warning\|print(" > $O/${TAG}_tile_timeline_c4.log

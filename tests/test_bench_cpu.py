@@ -143,9 +143,9 @@ def test_sec8d_bytes_and_algorithmic_work_conventions():
     assert per_row == 2 * 256 + 6 * 32 + 13 * 64 + 30 + 100 + 16
 
 
-def test_n_gt_1_line_shape_under_gloo(tmp_path):
-    """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one JSON line on rank 0): the weak configs[1] figure AND
-    the strong-scaling figures of configs[2] (512) / configs[4] (2048) with rccl_world and per-collective us in the SAME line."""
+def _gloo_line(*extra):
+    """The one JSON line of `bench.py --gpus 2 --steps 4 --warmup 1 <extra>` as the driver launches it (torch.distributed.run,
+    two gloo ranks of tests/bench_stub_driver.py)."""
     import socket
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
@@ -154,12 +154,20 @@ def test_n_gt_1_line_shape_under_gloo(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(REPO, "tests", "bench_stub_driver.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"],
+                        "--master-port", str(port), os.path.join(REPO, "tests", "bench_stub_driver.py"), "--gpus", "2", "--steps", "4",
+                        "--warmup", "1"] + list(extra),
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_n_gt_1_line_shape_under_gloo(tmp_path):
+    """`bench.py --gpus 2 --full`: the weak configs[1] figure AND the strong-scaling figures of configs[2] (512) / configs[4] (2048)
+    with rccl_world and per-collective us in the SAME line."""
+    d = _gloo_line("--full")
+    assert d["full"] is True
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["rccl_world"] == 2 and d["config"]["global_batch"] == 128
     # value = the exact --steps pass (2 ranks x 4 x 7.0 exchange steps in 4 x 70 us); the long window is reported beside it
     assert abs(d["value"] - 2 * (4 * 7.0) / (4 * 7e-5)) < 1e-6 * d["value"] and d["value_first_pass"] == d["value"]
@@ -172,6 +180,19 @@ def test_n_gt_1_line_shape_under_gloo(tmp_path):
     assert sc["c5s"]["global_batch"] == 2048 and sc["c5s"]["per_gpu_batch"] == 1024
     assert sc["c5s"]["value_window"] == 30 * 100 * 8.0 / 2.0 and abs(sc["c5s"]["value"] - 1e5) < 1e-3 and "collective_us" in sc["c5s"]
     assert "other_configs" not in d and "cpu_baseline" not in d
+
+
+def test_n_gt_1_plain_line_under_gloo():
+    """A plain `bench.py --gpus 2`: the same headline from the timed steps of ONE workload run per rank (the stub leaves out
+    what only --full measures, so using it would fail), and nothing of the window or the strong-scaling configs."""
+    d = _gloo_line()
+    assert d["full"] is False and d["n_gpus"] == 2 and d["config"]["rccl_world"] == 2 and d["config"]["global_batch"] == 128
+    assert abs(d["value"] - 2 * (4 * 7.0) / (4 * 7e-5)) < 1e-6 * d["value"] and d["value_first_pass"] == d["value"]
+    assert abs(d["ms_per_step"] - 0.07) < 1e-9 and d["config"]["timed_minibatches"] == 4
+    assert d["config"]["collective"] == "torch.distributed.all_reduce, backend gloo"
+    for k in ("value_window", "roofline", "strong_configs", "other_configs", "cpu_baseline"):
+        assert k not in d, k
+    assert "window" not in d["config"] and "collective_us" not in d["config"]
 
 
 def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
@@ -202,11 +223,10 @@ def test_dump_outputs_flag_writes_what_the_timed_steps_returned(tmp_path, monkey
     import numpy as np
     seen = []
 
-    def stub(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False):
-        seen.append((workload, steps, warmup, outputs))
+    def stub(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False, full=True):
+        seen.append((workload, steps, warmup, outputs, full))
         CFG, B, label = bench.WORKLOADS[workload]
-        return dict(workload=workload, label=label, B=B, Bg=B, elapsed=2.0, minibatches=steps * 10, ex_steps=steps * 80.0,
-                    sample_steps=1.0, cfg=CFG, roofline=None, collective="none (single rank)", collective_us=None,
+        return dict(workload=workload, label=label, B=B, Bg=B, cfg=CFG, collective="none (single rank)",
                     first_pass_ms_per_minibatch=0.05, first_pass_steps_per_minibatch=7.0, first_pass_ex_steps=steps * 7.0,
                     first_pass_seconds=steps * 5e-5, dist_world=1,
                     outputs={"params": np.ones(5, np.float32), "losses": np.arange(8, dtype=np.float32)} if outputs else None)
@@ -218,9 +238,74 @@ def test_dump_outputs_flag_writes_what_the_timed_steps_returned(tmp_path, monkey
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2", "--no-other-configs", "--no-cli",
                                       "--no-cpu-baseline", "--dump-outputs", str(out)])
     bench.main()
-    assert seen == [("c2", 7, 2, True)]
+    assert seen == [("c2", 7, 2, True, False)]
     d = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert d["steps"] == 7 and abs(d["ms_per_step"] - 0.05) < 1e-9
     assert d["dump_outputs"]["entries"] == {"losses": 8, "params": 5}
     assert np.array_equal(np.load(out / "losses.npy"), np.arange(8, dtype=np.float32))
     assert np.array_equal(np.load(out / "params.npy"), np.ones(5, np.float32))
+
+
+def _stubbed_main(monkeypatch, capsys, argv):
+    """bench.main() with the GPU legs replaced by stubs that record their calls; returns (calls, the printed line)."""
+    calls = []
+
+    def run_workload(workload, steps, warmup, seed, rank, world, local_rank, strong=False, want_roofline=True, outputs=False, full=True):
+        calls.append(("run_workload", workload, strong, full))
+        CFG, B, label = bench.WORKLOADS[workload]
+        Bg = bench.STRONG_GLOBAL_BATCH[workload] if strong else B
+        res = dict(workload=workload, label=label, B=Bg, Bg=Bg, cfg=CFG, collective="none (single rank)",
+                   first_pass_ms_per_minibatch=0.05, first_pass_steps_per_minibatch=7.0, first_pass_ex_steps=steps * 7.0,
+                   first_pass_seconds=steps * 5e-5, dist_world=1, outputs=None)
+        if full:
+            res.update(elapsed=2.0, minibatches=steps * 10, ex_steps=steps * 80.0, sample_steps=1.0, collective_us=None,
+                       window_live_rows_per_sample=8.0, roofline={"kernel": "k_game", "kernels_us": {"k_game": 40.0}} if want_roofline else None)
+        return res
+
+    def run_cli(seconds=2.0, epochs=None, dist_backend=None, log_dev=10 ** 9):
+        calls.append(("run_cli", log_dev))
+        return dict(cli_steps_per_s=1.0, cli_ms_per_minibatch=1.0) if log_dev >= 10 ** 9 else dict(cli_default_flags_steps_per_s=1.0)
+
+    def cpu_baseline(seconds_budget=24.0):
+        calls.append(("cpu_baseline",))
+        return dict(value=100.0)
+
+    for name, f in (("run_workload", run_workload), ("run_cli", run_cli), ("cpu_baseline", cpu_baseline)):
+        monkeypatch.setattr(bench, name, f)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    bench.main()
+    return calls, json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_plain_run_times_the_steps_and_nothing_else(monkeypatch, capsys):
+    """`bench.py --steps N --warmup W` runs ONE workload without the post-timing passes, and no other config, CLI loop or CPU
+    baseline; the headline keys keep their meaning."""
+    calls, d = _stubbed_main(monkeypatch, capsys, ["--steps", "20", "--warmup", "3"])
+    assert calls == [("run_workload", "c2", False, False)]
+    assert d["metric"].startswith("exchange-steps/sec (whole node), 30-class Adaptive") and d["unit"] == "exchange-steps/s"
+    assert abs(d["value"] - 20 * 7.0 / (20 * 5e-5)) < 1e-6 * d["value"] and abs(d["ms_per_step"] - 0.05) < 1e-12
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 20 and d["warmup"] == 3 and d["full"] is False
+    for k in ("value_window", "roofline", "other_configs", "cpu_baseline", "strong_configs"):
+        assert k not in d, k
+    assert "window" not in d["config"] and "cli" not in d["config"]
+
+
+def test_full_run_keeps_every_other_measurement(monkeypatch, capsys):
+    """`--full`: the same headline, then the window and roofline of the metric's workload, the six other configs, the shipped loop
+    (twice: plain and with the reference's -log_dev 1000) and the CPU baseline -- in that order, as before the option existed."""
+    calls, d = _stubbed_main(monkeypatch, capsys, ["--steps", "20", "--warmup", "3", "--full"])
+    assert calls == ([("run_workload", "c2", False, True)]
+                     + [("run_workload", w, s, True) for w, s in (("c3", False), ("c4", False), ("c4r256", False), ("c5", False),
+                                                                 ("c3", True), ("c5", True))]
+                     + [("run_cli", 10 ** 9), ("run_cli", 1000), ("cpu_baseline",)])
+    assert abs(d["value"] - 20 * 7.0 / (20 * 5e-5)) < 1e-6 * d["value"] and abs(d["ms_per_step"] - 0.05) < 1e-12 and d["full"] is True
+    assert d["value_window"] == 20 * 80.0 / 2.0 == d["config"]["window"]["value"]
+    assert d["roofline"]["kernel"] == "k_game"
+    assert set(d["other_configs"]) == {"c3", "c4", "c4r256", "c5", "c3s", "c5s"}
+    assert d["config"]["cli"]["cli_over_resident_window"] == 1.0 / d["value_window"]
+    assert d["cpu_baseline"]["gpu_first_pass_over_cpu"] == d["value"] / 100.0
+    # the --no-* switches still narrow a --full run
+    calls, d = _stubbed_main(monkeypatch, capsys, ["--steps", "20", "--warmup", "3", "--full", "--no-other-configs", "--no-cli", "--no-cpu-baseline"])
+    assert calls == [("run_workload", "c2", False, True)] and "value_window" in d and "other_configs" not in d
