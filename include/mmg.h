@@ -20,6 +20,9 @@
  *   mmg_baseline_forward   <- Baseline.forward              model.py:496-516
  *   mmg_exchange_vjp       <- loss.backward() of ONE agent's graph for any loss built from exchange()'s outputs
  *                             (model.py:1309, 1316, 1322, 1328; graphs split at model.py:807-811, 826-829, 835-843)
+ *   mmg_sender_vjp         <- backward() through ONE Sender.forward call      model.py:193-238
+ *   mmg_receiver_vjp       <- backward() through ONE Receiver.forward call    model.py:333-474
+ *   mmg_baseline_vjp       <- backward() through ONE Baseline.forward call    model.py:496-516
  *
  * Conventions
  *   - plain pointers and sizes; every pointer named d_* is DEVICE memory owned by the caller
@@ -235,7 +238,8 @@ int mmg_dp_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target,
 int mmg_clear_error(mmg_handle* h, void* stream);
 int mmg_degraded(const mmg_handle* h);
 
-/* Agent-level entry points (forward only; one exchange step), mirroring the reference modules.
+/* Agent-level entry points (one exchange step), mirroring the reference modules.  Forward only: their backward pass is
+ * mmg_sender_vjp / mmg_receiver_vjp / mmg_baseline_vjp below, from the caller's copies of the call's inputs and outputs.
  *   sender:   x[B,F], w[B,W] (ignored when t==0), t -> message[B,W], probs[B,W] (NULL if continuous),
  *             h_x[B,H]                                                   model.py:193-238
  *   receiver: z[B,W], desc[D,V], h_z[B,R] in/out (zeros for a fresh conversation), s_prob_prod[B]
@@ -276,6 +280,30 @@ int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, const float
 int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
                      const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
                      void* stream);
+
+/* Vector-Jacobian products of ONE agent-level forward call (mmg_sender_forward / mmg_receiver_forward / mmg_baseline_forward with
+ * train = 1): the backward pass of that call alone, for a conversation the caller writes out of module calls.  Every array is
+ * [B, .] (B = the handle's batch) and is the caller's copy of the call's inputs and outputs: the tape is never read, so any
+ * forward, exchange or other VJP in between changes nothing.  The parameters must be the forward's.
+ *   upstream gradients d_d*: NULL = zero.  Input-gradient outputs (d_dx, d_dw, d_dz, d_dh_prev, d_dbinary, d_dinp): NULL = not
+ *   wanted; otherwise overwritten.  The weight gradients OVERWRITE the agent's slice of the gradient buffer (as mmg_exchange_vjp).
+ *   sender:   x[B,F], w[B,W] (the code input; ignored when t == 0: sigmoid(code_bias) then, model.py:196-200), h_x[B,H] and
+ *             probs[B,W] (binary; NULL if continuous) of the call; d_dout: d probs (binary) | d message logits (continuous),
+ *             d_dh_x: d sender.h_x  ->  d_dx[B,F], d_dw[B,W] (t > 0)
+ *   receiver: z[B,W], desc[D,V], h_prev[B,R] (NULL: the zero state of a first call), h_new[B,R] (= receiver.h_z after the
+ *             call), y[B,D], w_probs[B,W] (binary), s_prob[B]; upstream d_dy[B,D], d_dw[B,W] (w_probs | w logits), d_dps[B],
+ *             d_dh_w[B,R] (receiver.h_w), d_dh_new[B,R]  ->  d_dz[B,W], d_dh_prev[B,R] (the carry for the previous call's node).
+ *             softmax(y) inside dbar and desc are constants (model.py:441).
+ *   baseline: which = MMG_AGENT_BASELINE_REC/SEN; x[B,H] (sen) / binary[B,W] / inp[B,R] (rec) as in mmg_baseline_forward,
+ *             rows == B; d_dscore[B]  ->  d_dx, d_dbinary, d_dinp.
+ * fp32, deterministic (fixed summation order, no float atomics); enqueued on `stream`, no host synchronisation. */
+int mmg_sender_vjp(mmg_handle* h, const float* d_x, const float* d_w, int t, const float* d_h_x, const float* d_probs,
+                   const float* d_dout, const float* d_dh_x, float* d_dx, float* d_dw, void* stream);
+int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_desc, const float* d_h_prev, const float* d_h_new,
+                     const float* d_y, const float* d_w_probs, const float* d_s_prob, const float* d_dy, const float* d_dw,
+                     const float* d_dps, const float* d_dh_w, const float* d_dh_new, float* d_dz, float* d_dh_prev, void* stream);
+int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
+                     const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream);
 
 /* The log block of a minibatch (model.py:1342-1461) gathered on the device: ONE launch writes one flat float64 vector the
  * caller copies to the host (asynchronously) and formats.  Layout (mmg_log_snapshot_count() doubles):

@@ -10,10 +10,17 @@
 // The weight gradients are then the existing k_wgrad<false> over four job tables of their own (one per agent, all T * B rows,
 // built at mmg_create).  Every sum below runs in a fixed order inside one thread: results are deterministic.
 //
+// The per-call VJPs of the agent modules' forward() (mmg_sender_vjp / mmg_receiver_vjp / mmg_baseline_vjp) run the same step
+// math (vjp_rec_step, vjp_sen_step, vjp_bas_hidden) on ONE call: the call's inputs and outputs come from the caller's buffers,
+// the recurrent carry from d h_new and back out as d h_prev, and the input gradients (d z, d w, d x, the baselines' inputs) are
+// formed too.  Their deltas land in the first B rows of the same v* arrays; the operands that the exchange tables read from the
+// tape (z, h, h_x) are copied to vcz / vch0 / vch1 / vchx; k_wgrad<false> then runs over four per-call tables of B rows.
+//
 // Inputs crossing between agents are constants, as in the reference (model.py:807-811, 826-829, 835-843): the sender's and the
 // receiver's messages, data, desc and softmax(y) (dbar = softmax(y).detach() . desc, model.py:441-452).
 #pragma once
 #include "device_utils.h"
+#include "kernels_tile.h"
 #include "layout.h"
 
 namespace mmg {
@@ -56,16 +63,22 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_cd(Dims dm, Params P, Tape tp
     }
 }
 
-// dynamic LDS floats of k_vjp_rec
+// dynamic LDS floats of k_vjp_rec / k_vjp_rec_call
 __host__ __device__ inline int vjp_rec_smem_floats(const Dims& d) { return 14 * d.R + 3 * d.W + d.V + 2 * d.D + MMG_BLOCK; }
 
-// Receiver (model.py:303-477): one workgroup per sample, reverse time from t = T - 1.  Seeds at every step come from the upstream
-// gradients (dls = dps ps (1 - ps), dlw = dpw pw (1 - pw) or dw, dA_t from dy_t); backprop through time over the GRU state.
-// Writes the per-row deltas the weight-gradient jobs reduce (vdgi, vdgh, vdgpre, vdlw, vdls, vdA, vdys) and the recomputed
-// operands (vA, vg, vdbar).
-__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_rec(Dims dm, Params P, Tape tp, VjpIn in) {
-    extern __shared__ float smem[];
-    const int b = blockIdx.x, B = dm.B, D = dm.D, W = dm.W, R = dm.R, V = dm.V, T = dm.T;
+// One (step, sample) row of the receiver VJP: where the step's forward values and upstream gradients live (row pointers, NULL =
+// zero), and the row of the v* arrays it writes.  k_vjp_rec points into the exchange tape, k_vjp_rec_call into the caller's buffers.
+struct RecRow {
+    const float *h0, *h1, *z, *y, *pw, *ps;    // GRU state before (NULL = zero state) / after the step, message in, y, w / s probs
+    const float *dy, *dw, *dps, *dhw;          // d y, d w_probs | d w logits, d s_prob, d h_w
+    size_t row;
+};
+
+// The receiver's step backward (model.py:340-474), shared by the exchange and the per-call VJP.  On entry s_car (LDS, R floats)
+// holds d h_{t+1} from later uses of the state; on exit it holds d h_t.  Writes the row's deltas the weight-gradient jobs reduce
+// (vdgi, vdgh, vdgpre, vdlw, vdls, vdA, vdys) and the recomputed operands (vA, vg, vdbar).
+__device__ __forceinline__ void vjp_rec_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const RecRow& io) {
+    const int D = dm.D, W = dm.W, R = dm.R, V = dm.V;
     const int tid = threadIdx.x;
     float* s_h0 = smem;            float* s_h1 = s_h0 + R;       float* s_r = s_h1 + R;      float* s_u = s_r + R;
     float* s_n = s_u + R;          float* s_ghn = s_n + R;       float* s_g = s_ghn + R;     float* s_dgp = s_g + R;
@@ -76,124 +89,186 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_rec(Dims dm, Params P, Tape t
     const float *Wh = P.p[R_WH_W], *bh = P.p[R_WH_B], *Wd = P.p[R_WD_W], *Ww = P.p[R_W_W];
     const float *Wy1 = P.p[R_Y1_W], *w2 = P.p[R_Y2_W], *ws = P.p[R_S_W];
     const bool bin = dm.use_binary;
-    for (int i = tid; i < R; i += MMG_BLOCK) s_car[i] = 0.f;
+    const size_t row = io.row;
+    __syncthreads();
+    for (int i = tid; i < R; i += MMG_BLOCK) { s_h0[i] = io.h0 ? io.h0[i] : 0.f; s_h1[i] = io.h1[i]; }
+    for (int j = tid; j < W; j += MMG_BLOCK) { s_z[j] = io.z[j]; s_pw[j] = bin ? io.pw[j] : 0.f; }
+    for (int d = tid; d < D; d += MMG_BLOCK) {
+        s_p[d] = io.y[d];
+        s_dy[d] = io.dy ? io.dy[d] : 0.f;
+    }
+    // softmax(y_t) . desc (model.py:441-449), a constant of the graph
+    float m = -INFINITY;
+    for (int d = tid; d < D; d += MMG_BLOCK) m = fmaxf(m, s_p[d]);
+    m = vjp_block_reduce(m, s_red, true);
+    float sum = 0.f;
+    for (int d = tid; d < D; d += MMG_BLOCK) sum += expf(s_p[d] - m);
+    sum = vjp_block_reduce(sum, s_red, false);
+    float dys = 0.f;
+    for (int d = tid; d < D; d += MMG_BLOCK) dys += s_dy[d];
+    dys = vjp_block_reduce(dys, s_red, false);                // (ends with a barrier: s_p is complete below)
+    for (int d = tid; d < D; d += MMG_BLOCK) s_p[d] = expf(s_p[d] - m) / sum;
+    __syncthreads();
+    for (int v = tid; v < V; v += MMG_BLOCK) {
+        float acc = 0.f;
+        for (int d = 0; d < D; ++d) acc = fmaf(s_p[d], tp.vdesc[(size_t)d * V + v], acc);
+        s_dbar[v] = acc;
+        tp.vdbar[row * V + v] = acc;
+    }
+    if (tid == 0) tp.vdys[row] = dys;
+    // GRU gates of the step (model.py:340): r, u, n and W_hn h + b_hn
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        float gr = bih[i] + bhh[i], gu = bih[R + i] + bhh[R + i], gin = bih[2 * R + i], ghn = bhh[2 * R + i];
+        for (int k = 0; k < W; ++k) {
+            const float zk = s_z[k];
+            gr = fmaf(Wih[(size_t)i * W + k], zk, gr);
+            gu = fmaf(Wih[(size_t)(R + i) * W + k], zk, gu);
+            gin = fmaf(Wih[(size_t)(2 * R + i) * W + k], zk, gin);
+        }
+        for (int k = 0; k < R; ++k) {
+            const float hk = s_h0[k];
+            gr = fmaf(Whh[(size_t)i * R + k], hk, gr);
+            gu = fmaf(Whh[(size_t)(R + i) * R + k], hk, gu);
+            ghn = fmaf(Whh[(size_t)(2 * R + i) * R + k], hk, ghn);
+        }
+        const float r = sigmoidf_(gr), u = sigmoidf_(gu);
+        s_r[i] = r; s_u[i] = u; s_ghn[i] = ghn; s_n[i] = tanhf(gin + r * ghn);
+    }
+    __syncthreads();                                          // s_dbar complete
+    // h_w = tanh(w_h h_{t+1} + w_d dbar) (model.py:452) and A_t = W_y1[:, :R] h_{t+1}
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        float gp = bh[i], a = 0.f;
+        for (int k = 0; k < R; ++k) {
+            gp = fmaf(Wh[(size_t)i * R + k], s_h1[k], gp);
+            a = fmaf(Wy1[(size_t)i * (R + V) + k], s_h1[k], a);
+        }
+        for (int v = 0; v < V; ++v) gp = fmaf(Wd[(size_t)i * V + v], s_dbar[v], gp);
+        const float g = tanhf(gp);
+        s_g[i] = g;
+        tp.vg[row * R + i] = g;
+        tp.vA[row * R + i] = a;
+        // dA_t[r] = w2[r] sum_d dy_t[d] 1[A_t[r] + Cd[d, r] > 0]   (model.py:432-433)
+        float acc = 0.f;
+        for (int d = 0; d < D; ++d) acc += (a + tp.vCd[(size_t)d * R + i] > 0.f) ? s_dy[d] : 0.f;
+        s_dA[i] = w2[i] * acc;
+        tp.vdA[row * R + i] = s_dA[i];
+    }
+    // message seeds: sigmoid' of the receiver's message probabilities (model.py:456) or the logits' gradient directly (:474)
+    for (int j = tid; j < W; j += MMG_BLOCK) {
+        float dl = 0.f;
+        if (io.dw) {
+            const float gw = io.dw[j];
+            dl = bin ? gw * s_pw[j] * (1.f - s_pw[j]) : gw;
+        }
+        s_dlw[j] = dl;
+        tp.vdlw[row * W + j] = dl;
+    }
+    float dls = 0.f;
+    if (io.dps) { const float ps = io.ps[0]; dls = io.dps[0] * ps * (1.f - ps); }
+    if (tid == 0) tp.vdls[row] = dls;
+    __syncthreads();
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        float dg = io.dhw ? io.dhw[i] : 0.f;                  // (d h_w from a use of receiver.h_w: per-call VJP only)
+        for (int j = 0; j < W; ++j) dg = fmaf(Ww[(size_t)j * R + i], s_dlw[j], dg);
+        const float g = s_g[i], dgp = dg * (1.f - g * g);
+        s_dgp[i] = dgp;
+        tp.vdgpre[row * R + i] = dgp;
+    }
+    __syncthreads();
+    // d h_{t+1}: recurrence + w_h + s + the y head; then the GRU cell backward
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        float dh = s_car[i] + dls * ws[i];
+        for (int k = 0; k < R; ++k) {
+            dh = fmaf(Wh[(size_t)k * R + i], s_dgp[k], dh);
+            dh = fmaf(Wy1[(size_t)k * (R + V) + i], s_dA[k], dh);
+        }
+        const float r = s_r[i], u = s_u[i], nn = s_n[i];
+        const float dnp = dh * (1.f - u) * (1.f - nn * nn);
+        const float dup = dh * (s_h0[i] - nn) * u * (1.f - u);
+        const float drp = dnp * s_ghn[i] * r * (1.f - r);
+        float* dgi = tp.vdgi + row * 3 * R;
+        float* dgh = tp.vdgh + row * 3 * R;
+        dgi[i] = drp; dgi[R + i] = dup; dgi[2 * R + i] = dnp;
+        dgh[i] = drp; dgh[R + i] = dup; dgh[2 * R + i] = dnp * r;
+        s_dgh[i] = drp; s_dgh[R + i] = dup; s_dgh[2 * R + i] = dnp * r;
+        s_car[i] = dh * u;                                    // (own entry: read above by this thread only)
+    }
+    __syncthreads();
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        float c = s_car[i];
+        for (int k = 0; k < 3 * R; ++k) c = fmaf(Whh[(size_t)k * R + i], s_dgh[k], c);
+        s_car[i] = c;
+    }
+}
+
+// Receiver (model.py:303-477): one workgroup per sample, reverse time from t = T - 1.  Seeds at every step come from the upstream
+// gradients (dls = dps ps (1 - ps), dlw = dpw pw (1 - pw) or dw, dA_t from dy_t); backprop through time over the GRU state.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_rec(Dims dm, Params P, Tape tp, VjpIn in) {
+    extern __shared__ float smem[];
+    const int b = blockIdx.x, B = dm.B, D = dm.D, W = dm.W, R = dm.R, T = dm.T;
+    float* s_car = smem + 9 * R;                              // (vjp_rec_step's carry slot)
+    for (int i = threadIdx.x; i < R; i += MMG_BLOCK) s_car[i] = 0.f;
     for (int t = T - 1; t >= 0; --t) {
         const size_t row = (size_t)t * B + b;
         const bool live = t < in.n;
-        __syncthreads();
-        for (int i = tid; i < R; i += MMG_BLOCK) { s_h0[i] = tp.h[row * R + i]; s_h1[i] = tp.h[row * R + (size_t)B * R + i]; }
-        for (int j = tid; j < W; j += MMG_BLOCK) { s_z[j] = tp.z[row * W + j]; s_pw[j] = bin ? tp.pw[row * W + j] : 0.f; }
-        for (int d = tid; d < D; d += MMG_BLOCK) {
-            s_p[d] = tp.y[row * D + d];
-            s_dy[d] = (live && in.dy) ? in.dy[row * D + d] : 0.f;
-        }
-        // softmax(y_t) . desc (model.py:441-449), a constant of the graph
-        float m = -INFINITY;
-        for (int d = tid; d < D; d += MMG_BLOCK) m = fmaxf(m, s_p[d]);
-        m = vjp_block_reduce(m, s_red, true);
-        float sum = 0.f;
-        for (int d = tid; d < D; d += MMG_BLOCK) sum += expf(s_p[d] - m);
-        sum = vjp_block_reduce(sum, s_red, false);
-        float dys = 0.f;
-        for (int d = tid; d < D; d += MMG_BLOCK) dys += s_dy[d];
-        dys = vjp_block_reduce(dys, s_red, false);                // (ends with a barrier: s_p is complete below)
-        for (int d = tid; d < D; d += MMG_BLOCK) s_p[d] = expf(s_p[d] - m) / sum;
-        __syncthreads();
-        for (int v = tid; v < V; v += MMG_BLOCK) {
+        RecRow io;
+        io.h0 = tp.h + row * R; io.h1 = tp.h + row * R + (size_t)B * R; io.z = tp.z + row * W; io.y = tp.y + row * D;
+        io.pw = tp.pw + row * W; io.ps = tp.ps + row;
+        io.dy = (live && in.dy) ? in.dy + row * D : nullptr;
+        io.dw = (live && in.dw) ? in.dw + row * W : nullptr;
+        io.dps = (live && in.dps) ? in.dps + row : nullptr;
+        io.dhw = nullptr;
+        io.row = row;
+        vjp_rec_step(dm, P, tp, smem, io);
+    }
+}
+
+// The caller-side buffers of one receiver call (mmg_receiver_vjp): the call's inputs, outputs and upstream gradients, [B, .] each.
+struct RecCall {
+    const float *z, *h_prev, *h_new, *y, *w_probs, *s_prob;
+    const float *dy, *dw, *dps, *dh_w, *dh_new;
+    float *dz, *dh_prev;
+    int dz_tiles;              // d z is formed by k_vjp_nn (MFMA) after this kernel, from vdgi
+};
+
+// Receiver, one call: one workgroup per sample, vjp_rec_step on row b with the carry taken from d h_new and returned as d h_prev,
+// plus d z = W_ih^T dgi (here when the shape keeps it off the MFMA tiles, else k_vjp_nn).  Copies the operands of its weight-gradient jobs (z, h_prev, h_new) in front of the job tables.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_rec_call(Dims dm, Params P, Tape tp, RecCall c) {
+    extern __shared__ float smem[];
+    const int b = blockIdx.x, D = dm.D, W = dm.W, R = dm.R, tid = threadIdx.x;
+    float* s_car = smem + 9 * R;
+    for (int i = tid; i < R; i += MMG_BLOCK) {
+        s_car[i] = c.dh_new ? c.dh_new[(size_t)b * R + i] : 0.f;
+        tp.vch0[(size_t)b * R + i] = c.h_prev ? c.h_prev[(size_t)b * R + i] : 0.f;
+        tp.vch1[(size_t)b * R + i] = c.h_new[(size_t)b * R + i];
+    }
+    for (int j = tid; j < W; j += MMG_BLOCK) tp.vcz[(size_t)b * W + j] = c.z[(size_t)b * W + j];
+    RecRow io;
+    io.h0 = c.h_prev ? c.h_prev + (size_t)b * R : nullptr; io.h1 = c.h_new + (size_t)b * R; io.z = c.z + (size_t)b * W;
+    io.y = c.y + (size_t)b * D; io.pw = c.w_probs ? c.w_probs + (size_t)b * W : nullptr; io.ps = c.s_prob ? c.s_prob + b : nullptr;
+    io.dy = c.dy ? c.dy + (size_t)b * D : nullptr;
+    io.dw = c.dw ? c.dw + (size_t)b * W : nullptr;
+    io.dps = c.dps ? c.dps + b : nullptr;
+    io.dhw = c.dh_w ? c.dh_w + (size_t)b * R : nullptr;
+    io.row = b;
+    vjp_rec_step(dm, P, tp, smem, io);
+    __syncthreads();                                          // s_car and this row of vdgi complete
+    if (c.dh_prev)
+        for (int i = tid; i < R; i += MMG_BLOCK) c.dh_prev[(size_t)b * R + i] = s_car[i];
+    if (c.dz && !c.dz_tiles) {
+        const float* Wih = P.p[R_WIH];
+        const float* dgi = tp.vdgi + (size_t)b * 3 * R;
+        for (int k = tid; k < W; k += MMG_BLOCK) {
             float acc = 0.f;
-            for (int d = 0; d < D; ++d) acc = fmaf(s_p[d], tp.vdesc[(size_t)d * V + v], acc);
-            s_dbar[v] = acc;
-            tp.vdbar[row * V + v] = acc;
-        }
-        if (tid == 0) tp.vdys[row] = dys;
-        // GRU gates of the step (model.py:340): r, u, n and W_hn h + b_hn
-        for (int i = tid; i < R; i += MMG_BLOCK) {
-            float gr = bih[i] + bhh[i], gu = bih[R + i] + bhh[R + i], gin = bih[2 * R + i], ghn = bhh[2 * R + i];
-            for (int k = 0; k < W; ++k) {
-                const float zk = s_z[k];
-                gr = fmaf(Wih[(size_t)i * W + k], zk, gr);
-                gu = fmaf(Wih[(size_t)(R + i) * W + k], zk, gu);
-                gin = fmaf(Wih[(size_t)(2 * R + i) * W + k], zk, gin);
-            }
-            for (int k = 0; k < R; ++k) {
-                const float hk = s_h0[k];
-                gr = fmaf(Whh[(size_t)i * R + k], hk, gr);
-                gu = fmaf(Whh[(size_t)(R + i) * R + k], hk, gu);
-                ghn = fmaf(Whh[(size_t)(2 * R + i) * R + k], hk, ghn);
-            }
-            const float r = sigmoidf_(gr), u = sigmoidf_(gu);
-            s_r[i] = r; s_u[i] = u; s_ghn[i] = ghn; s_n[i] = tanhf(gin + r * ghn);
-        }
-        __syncthreads();                                          // s_dbar complete
-        // h_w = tanh(w_h h_{t+1} + w_d dbar) (model.py:452) and A_t = W_y1[:, :R] h_{t+1}
-        for (int i = tid; i < R; i += MMG_BLOCK) {
-            float gp = bh[i], a = 0.f;
-            for (int k = 0; k < R; ++k) {
-                gp = fmaf(Wh[(size_t)i * R + k], s_h1[k], gp);
-                a = fmaf(Wy1[(size_t)i * (R + V) + k], s_h1[k], a);
-            }
-            for (int v = 0; v < V; ++v) gp = fmaf(Wd[(size_t)i * V + v], s_dbar[v], gp);
-            const float g = tanhf(gp);
-            s_g[i] = g;
-            tp.vg[row * R + i] = g;
-            tp.vA[row * R + i] = a;
-            // dA_t[r] = w2[r] sum_d dy_t[d] 1[A_t[r] + Cd[d, r] > 0]   (model.py:432-433)
-            float acc = 0.f;
-            for (int d = 0; d < D; ++d) acc += (a + tp.vCd[(size_t)d * R + i] > 0.f) ? s_dy[d] : 0.f;
-            s_dA[i] = w2[i] * acc;
-            tp.vdA[row * R + i] = s_dA[i];
-        }
-        // message seeds: sigmoid' of the receiver's message probabilities (model.py:456) or the logits' gradient directly (:474)
-        for (int j = tid; j < W; j += MMG_BLOCK) {
-            float dl = 0.f;
-            if (live && in.dw) {
-                const float gw = in.dw[row * W + j];
-                dl = bin ? gw * s_pw[j] * (1.f - s_pw[j]) : gw;
-            }
-            s_dlw[j] = dl;
-            tp.vdlw[row * W + j] = dl;
-        }
-        float dls = 0.f;
-        if (live && in.dps) { const float ps = tp.ps[row]; dls = in.dps[row] * ps * (1.f - ps); }
-        if (tid == 0) tp.vdls[row] = dls;
-        __syncthreads();
-        for (int i = tid; i < R; i += MMG_BLOCK) {
-            float dg = 0.f;
-            for (int j = 0; j < W; ++j) dg = fmaf(Ww[(size_t)j * R + i], s_dlw[j], dg);
-            const float g = s_g[i], dgp = dg * (1.f - g * g);
-            s_dgp[i] = dgp;
-            tp.vdgpre[row * R + i] = dgp;
-        }
-        __syncthreads();
-        // d h_{t+1}: recurrence + w_h + s + the y head; then the GRU cell backward
-        for (int i = tid; i < R; i += MMG_BLOCK) {
-            float dh = s_car[i] + dls * ws[i];
-            for (int k = 0; k < R; ++k) {
-                dh = fmaf(Wh[(size_t)k * R + i], s_dgp[k], dh);
-                dh = fmaf(Wy1[(size_t)k * (R + V) + i], s_dA[k], dh);
-            }
-            const float r = s_r[i], u = s_u[i], nn = s_n[i];
-            const float dnp = dh * (1.f - u) * (1.f - nn * nn);
-            const float dup = dh * (s_h0[i] - nn) * u * (1.f - u);
-            const float drp = dnp * s_ghn[i] * r * (1.f - r);
-            float* dgi = tp.vdgi + row * 3 * R;
-            float* dgh = tp.vdgh + row * 3 * R;
-            dgi[i] = drp; dgi[R + i] = dup; dgi[2 * R + i] = dnp;
-            dgh[i] = drp; dgh[R + i] = dup; dgh[2 * R + i] = dnp * r;
-            s_dgh[i] = drp; s_dgh[R + i] = dup; s_dgh[2 * R + i] = dnp * r;
-            s_car[i] = dh * u;                                    // (own entry: read above by this thread only)
-        }
-        __syncthreads();
-        for (int i = tid; i < R; i += MMG_BLOCK) {
-            float c = s_car[i];
-            for (int k = 0; k < 3 * R; ++k) c = fmaf(Whh[(size_t)k * R + i], s_dgh[k], c);
-            s_car[i] = c;
+            for (int i = 0; i < 3 * R; ++i) acc = fmaf(Wih[(size_t)i * W + k], dgi[i], acc);
+            c.dz[(size_t)b * W + k] = acc;
         }
     }
 }
 
 // Class side of the receiver: dC[d, r] = w2[r] sum_{t < n, b} dy_t[b, d] 1[A_t[b, r] + Cd[d, r] > 0] (-> y1.weight[:, R:], y1.bias)
-// and Py2[d, r] = sum_{t < n, b} dy_t[b, d] relu(A_t[b, r] + Cd[d, r]) (-> y2.weight).  One workgroup per class.
+// and Py2[d, r] = sum_{t < n, b} dy_t[b, d] relu(A_t[b, r] + Cd[d, r]) (-> y2.weight).  One workgroup per class.  The per-call VJP
+// runs it with n = 1 over the call's B rows.
 __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_class(Dims dm, Params P, Tape tp, VjpIn in) {
     const int d = blockIdx.x, B = dm.B, D = dm.D, R = dm.R;
     for (int r = threadIdx.x; r < R; r += MMG_BLOCK) {
@@ -212,48 +287,60 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_class(Dims dm, Params P, Tape
 
 __host__ __device__ inline int vjp_sen_smem_floats(const Dims& d) { return 4 * d.H + 2 * d.W; }
 
+// The sender's step backward (model.py:195-238), shared by the exchange and the per-call VJP.  s_hx (LDS) holds h_x of the sample;
+// c: the code input w_{t-1} (NULL: sigmoid(code_bias), t = 0), pz: the message probabilities (binary), dz: d probs | d logits
+// (NULL = zero).  Adds d pre of the step to s_dhx and leaves it in s_dpre.
+__device__ __forceinline__ void vjp_sen_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const float* c,
+                                             const float* pz, const float* dz, size_t row) {
+    const int H = dm.H, W = dm.W, tid = threadIdx.x;
+    float* s_hx = smem;  float* s_a = s_hx + H;  float* s_dpre = s_a + H;  float* s_dhx = s_dpre + H;
+    float* s_c = s_dhx + H;  float* s_dlz = s_c + W;
+    const float *Wc = P.p[S_CODE_W], *bc = P.p[S_CODE_B], *cb = P.p[S_CODE_BIAS], *Wb = P.p[S_BIN_W];
+    const bool bin = dm.use_binary;
+    __syncthreads();
+    for (int j = tid; j < W; j += MMG_BLOCK) {
+        const float cj = c ? c[j] : sigmoidf_(cb[j]);
+        s_c[j] = cj;
+        tp.vc[row * W + j] = cj;
+        float dl = 0.f;
+        if (dz) {
+            const float g = dz[j];
+            if (bin) { const float p = pz[j]; dl = g * p * (1.f - p); } else dl = g;
+        }
+        s_dlz[j] = dl;
+        tp.vdlz[row * W + j] = dl;
+    }
+    __syncthreads();
+    for (int h = tid; h < H; h += MMG_BLOCK) {
+        float pre = s_hx[h] + bc[h];
+        for (int j = 0; j < W; ++j) pre = fmaf(Wc[(size_t)h * W + j], s_c[j], pre);
+        const float a = tanhf(pre);
+        s_a[h] = a;
+        tp.va[row * H + h] = a;
+        float da = 0.f;
+        for (int j = 0; j < W; ++j) da = fmaf(Wb[(size_t)j * H + h], s_dlz[j], da);
+        const float dp = da * (1.f - a * a);
+        s_dpre[h] = dp;
+        tp.vdpre[row * H + h] = dp;
+        s_dhx[h] += dp;
+    }
+}
+
 // Sender (model.py:144-238): one workgroup per sample.  dlz = dpz pz (1 - pz) (binary) or dz (continuous logits), dpre =
 // (W_b^T dlz)(1 - a^2), dhx = sum_t dpre, and at t = 0 the code_bias path W_c^T dpre_0 (model.py:196-200).
 __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen(Dims dm, Params P, Tape tp, VjpIn in) {
     extern __shared__ float smem[];
     const int b = blockIdx.x, B = dm.B, H = dm.H, W = dm.W, T = dm.T, tid = threadIdx.x;
-    float* s_hx = smem;  float* s_a = s_hx + H;  float* s_dpre = s_a + H;  float* s_dhx = s_dpre + H;
-    float* s_c = s_dhx + H;  float* s_dlz = s_c + W;
-    const float *Wc = P.p[S_CODE_W], *bc = P.p[S_CODE_B], *cb = P.p[S_CODE_BIAS], *Wb = P.p[S_BIN_W];
-    const bool bin = dm.use_binary;
+    float* s_hx = smem;  float* s_dpre = s_hx + 2 * H;  float* s_dhx = s_dpre + H;
+    const float *Wc = P.p[S_CODE_W], *cb = P.p[S_CODE_BIAS];
     if (b == 0)
         for (int j = tid; j < W; j += MMG_BLOCK) { const float s = sigmoidf_(cb[j]); tp.vdsig[j] = s * (1.f - s); }
     for (int h = tid; h < H; h += MMG_BLOCK) { s_hx[h] = tp.hx[(size_t)b * H + h]; s_dhx[h] = 0.f; }
     for (int t = 0; t < T; ++t) {
         const size_t row = (size_t)t * B + b;
         const bool live = t < in.n;
-        __syncthreads();
-        for (int j = tid; j < W; j += MMG_BLOCK) {
-            const float c = (t == 0) ? sigmoidf_(cb[j]) : tp.w[(row - B) * W + j];    // the receiver's previous message
-            s_c[j] = c;
-            tp.vc[row * W + j] = c;
-            float dl = 0.f;
-            if (live && in.dz) {
-                const float g = in.dz[row * W + j];
-                if (bin) { const float p = tp.pz[row * W + j]; dl = g * p * (1.f - p); } else dl = g;
-            }
-            s_dlz[j] = dl;
-            tp.vdlz[row * W + j] = dl;
-        }
-        __syncthreads();
-        for (int h = tid; h < H; h += MMG_BLOCK) {
-            float pre = s_hx[h] + bc[h];
-            for (int j = 0; j < W; ++j) pre = fmaf(Wc[(size_t)h * W + j], s_c[j], pre);
-            const float a = tanhf(pre);
-            s_a[h] = a;
-            tp.va[row * H + h] = a;
-            float da = 0.f;
-            for (int j = 0; j < W; ++j) da = fmaf(Wb[(size_t)j * H + h], s_dlz[j], da);
-            const float dp = da * (1.f - a * a);
-            s_dpre[h] = dp;
-            tp.vdpre[row * H + h] = dp;
-            s_dhx[h] += dp;
-        }
+        vjp_sen_step(dm, P, tp, smem, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W,
+                     (live && in.dz) ? in.dz + row * W : nullptr, row);    // (the receiver's previous message)
         if (t == 0) {
             __syncthreads();
             for (int j = tid; j < W; j += MMG_BLOCK) {
@@ -265,6 +352,62 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen(Dims dm, Params P, Tape t
     }
     __syncthreads();
     for (int h = tid; h < H; h += MMG_BLOCK) tp.vdhx[(size_t)b * H + h] = s_dhx[h];
+}
+
+// The caller-side buffers of one sender call (mmg_sender_vjp), [B, .] each.  w: the code input (t > 0).
+struct SenCall {
+    const float *w, *h_x, *probs, *dout, *dh_x;
+    float *dx, *dw;
+    int t;
+    int q_tiles, dx_tiles;     // W_c^T dpre / d x are formed by k_vjp_nn (MFMA) after this kernel, from vdpre / vdhx
+};
+
+// Sender, one call: one workgroup per sample.  vjp_sen_step on row b, then W_c^T dpre -> the code_bias path (t = 0) or d w (t > 0),
+// d h_x = dpre + the upstream gradient of sender.h_x (-> image_layer) and d x = W_img^T d h_x.  The two products run here only
+// when the shape keeps them off the MFMA tiles (q_tiles / dx_tiles: k_vjp_nn).
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen_call(Dims dm, Params P, Tape tp, const float* __restrict__ x, SenCall c) {
+    extern __shared__ float smem[];
+    const int b = blockIdx.x, H = dm.H, W = dm.W, F = dm.F, tid = threadIdx.x;
+    float* s_hx = smem;  float* s_dpre = s_hx + 2 * H;  float* s_dhx = s_dpre + H;
+    const float *Wc = P.p[S_CODE_W], *cb = P.p[S_CODE_BIAS], *Wi = P.p[S_IMG_W];
+    if (b == 0)
+        for (int j = tid; j < W; j += MMG_BLOCK) { const float s = sigmoidf_(cb[j]); tp.vdsig[j] = s * (1.f - s); }
+    for (int h = tid; h < H; h += MMG_BLOCK) { s_hx[h] = c.h_x[(size_t)b * H + h]; s_dhx[h] = 0.f; }
+    vjp_sen_step(dm, P, tp, smem, c.t == 0 ? nullptr : c.w + (size_t)b * W, c.probs ? c.probs + (size_t)b * W : nullptr,
+                 c.dout ? c.dout + (size_t)b * W : nullptr, b);
+    __syncthreads();
+    for (int j = tid; j < W; j += MMG_BLOCK) {
+        if (c.q_tiles) {                                      // (k_vjp_nn writes vdc0 at t = 0 and d w after)
+            if (c.t > 0) tp.vdc0[(size_t)b * W + j] = 0.f;
+            continue;
+        }
+        float acc = 0.f;
+        for (int h = 0; h < H; ++h) acc = fmaf(Wc[(size_t)h * W + j], s_dpre[h], acc);
+        tp.vdc0[(size_t)b * W + j] = c.t == 0 ? acc : 0.f;
+        if (c.t > 0 && c.dw) c.dw[(size_t)b * W + j] = acc;
+    }
+    for (int h = tid; h < H; h += MMG_BLOCK) {
+        const float dh = s_dhx[h] + (c.dh_x ? c.dh_x[(size_t)b * H + h] : 0.f);
+        s_dhx[h] = dh;
+        tp.vdhx[(size_t)b * H + h] = dh;
+    }
+    if (c.dx && !c.dx_tiles) {
+        __syncthreads();
+        for (int f = tid; f < F; f += MMG_BLOCK) {
+            float acc = 0.f;
+            for (int h = 0; h < H; ++h) acc = fmaf(Wi[(size_t)h * F + f], s_dhx[h], acc);
+            c.dx[(size_t)b * F + f] = acc;
+        }
+    }
+}
+
+// relu(linear1(in)) of one baseline row (model.py:513), in: the row's nin inputs in LDS.  Shared by both baseline VJPs.
+__device__ __forceinline__ void vjp_bas_hidden(int K, int nin, const float* W1, const float* b1, const float* in, float* hid) {
+    for (int k = threadIdx.x; k < K; k += MMG_BLOCK) {
+        float acc = b1[k];
+        for (int i = 0; i < nin; ++i) acc = fmaf(W1[(size_t)k * nin + i], in[i], acc);
+        hid[k] = fmaxf(acc, 0.f);
+    }
 }
 
 // Baselines (model.py:496-516): one workgroup per (step, sample) row.  The hidden units relu(linear1([..])) of the row and the
@@ -287,17 +430,101 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_bas(Dims dm, Params P, Tape t
         smem[i] = v;
     }
     __syncthreads();
-    const float* W1 = P.p[rec ? BR_L1_W : BS_L1_W];
-    const float* b1 = P.p[rec ? BR_L1_B : BS_L1_B];
-    float* hid = rec ? tp.vhid_r : tp.vhid_s;
-    for (int k = threadIdx.x; k < K; k += MMG_BLOCK) {
-        float acc = b1[k];
-        for (int i = 0; i < nin; ++i) acc = fmaf(W1[(size_t)k * nin + i], smem[i], acc);
-        hid[(size_t)row * K + k] = fmaxf(acc, 0.f);
-    }
+    vjp_bas_hidden(K, nin, P.p[rec ? BR_L1_W : BS_L1_W], P.p[rec ? BR_L1_B : BS_L1_B], smem,
+                   (rec ? tp.vhid_r : tp.vhid_s) + (size_t)row * K);
     if (threadIdx.x == 0) {
         const float* up = rec ? in.dbr : in.dbs;
         (rec ? tp.vdbr : tp.vdbs)[row] = (t < in.n && up) ? up[row] : 0.f;
+    }
+}
+
+// The caller-side buffers of one baseline call (mmg_baseline_vjp), [B, .] each: baseline_rec reads (binary, inp), baseline_sen
+// (x, binary).
+struct BasCall {
+    const float *x, *binary, *inp, *dscore;
+    float *dx, *dbinary, *dinp;
+    int tiles;                 // the input gradients are formed by k_vjp_nn (MFMA) from d hidden (vcdh) after this kernel
+};
+
+__host__ __device__ inline int vjp_bas_call_smem_floats(const Dims& d, int which) {
+    return (which == 2 ? d.W + d.R : d.H + d.W) + d.K;
+}
+
+// Baseline, one call: one workgroup per sample.  The hidden units (vjp_bas_hidden) and d score of the row for the weight-gradient
+// jobs, copies of the inputs in front of the job tables, and the input gradients W1^T (dscore * w2 * 1[hidden > 0]) -- here, or
+// (tiles) d hidden into vcdh for k_vjp_nn.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_bas_call(Dims dm, Params P, Tape tp, BasCall c, int which) {
+    extern __shared__ float smem[];
+    const int b = blockIdx.x, H = dm.H, W = dm.W, R = dm.R, K = dm.K, tid = threadIdx.x;
+    const bool rec = which == 2;
+    const int n1 = rec ? W : H, nin = rec ? W + R : H + W;
+    const float* in1 = rec ? c.binary : c.x;                  // the two inputs in linear1's column order
+    const float* in2 = rec ? c.inp : c.binary;
+    float* cp1 = rec ? tp.vcz : tp.vchx;
+    float* cp2 = rec ? tp.vch1 : tp.vcz;
+    float* s_dhid = smem + nin;
+    for (int i = tid; i < nin; i += MMG_BLOCK) {
+        float v;
+        if (i < n1) { v = in1[(size_t)b * n1 + i]; cp1[(size_t)b * n1 + i] = v; }
+        else { v = in2[(size_t)b * (nin - n1) + (i - n1)]; cp2[(size_t)b * (nin - n1) + (i - n1)] = v; }
+        smem[i] = v;
+    }
+    __syncthreads();
+    const float* W1 = P.p[rec ? BR_L1_W : BS_L1_W];
+    const float* w2 = P.p[rec ? BR_L2_W : BS_L2_W];
+    float* hid = (rec ? tp.vhid_r : tp.vhid_s) + (size_t)b * K;
+    vjp_bas_hidden(K, nin, W1, P.p[rec ? BR_L1_B : BS_L1_B], smem, hid);
+    const float ds = c.dscore ? c.dscore[b] : 0.f;
+    if (tid == 0) (rec ? tp.vdbr : tp.vdbs)[b] = ds;
+    float* dout1 = rec ? c.dbinary : c.dx;
+    float* dout2 = rec ? c.dinp : c.dbinary;
+    if (!dout1 && !dout2) return;
+    if (c.tiles) {
+        for (int k = tid; k < K; k += MMG_BLOCK) tp.vcdh[(size_t)b * K + k] = hid[k] > 0.f ? ds * w2[k] : 0.f;
+        return;
+    }
+    for (int k = tid; k < K; k += MMG_BLOCK) s_dhid[k] = hid[k] > 0.f ? ds * w2[k] : 0.f;   // (hid[k]: this thread's own store)
+    __syncthreads();
+    for (int i = tid; i < nin; i += MMG_BLOCK) {
+        float* dst = i < n1 ? dout1 : dout2;
+        if (!dst) continue;
+        float acc = 0.f;
+        for (int k = 0; k < K; ++k) acc = fmaf(W1[(size_t)k * nin + i], s_dhid[k], acc);
+        if (i < n1) dst[(size_t)b * n1 + i] = acc;
+        else dst[(size_t)b * (nin - n1) + (i - n1)] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The per-call-only products on the matrix cores: C[b, n] = sum_k A[b, k] Bm[k, n] over the B rows of one call, Bm a PyTorch
+// [out, in] weight read "NN" (n contiguous) -- d z = dgi . W_ih, d x = d h_x . W_img, dpre . W_c, d hidden . W1[:, cols].
+// One workgroup per 16-sample tile (blockIdx.x) and product (blockIdx.y: up to two products per launch); the A rows are staged
+// in LDS, zero-padded, and tgemm_nn_raw (kernels_tile.h) runs the fp32 MFMA tiles.  The k-parts are added in a fixed order:
+// deterministic.  Host: vjp_nn_fits decides per product (N, ldb multiples of 4, Bm 16-byte aligned, LDS within 64 KiB); a
+// product that does not fit stays in its per-sample kernel.
+// ---------------------------------------------------------------------------------------------
+struct NnProd { const float* A; const float* Bm; float* C; int lda, ldb, ldc, N, K; };
+
+__host__ __device__ inline int vjp_nn_smem_floats(int N, int K) { return MMG_TM * ld16(K) + tile_raw_floats_nn(N, MMG_BLOCK / 64); }
+
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_nn(int B, NnProd p0, NnProd p1) {
+    extern __shared__ float smem[];
+    const NnProd p = blockIdx.y ? p1 : p0;
+    const int b0 = blockIdx.x * MMG_TM, nw = MMG_BLOCK / 64, wave = threadIdx.x >> 6;
+    const int lda = ld16(p.K);
+    float* sA = smem;
+    float* raw = smem + MMG_TM * lda;
+    for (int e = threadIdx.x; e < MMG_TM * lda; e += MMG_BLOCK) {
+        const int m = e / lda, k = e - m * lda;
+        sA[e] = (b0 + m < B && k < p.K) ? p.A[(size_t)(b0 + m) * p.lda + k] : 0.f;
+    }
+    __syncthreads();
+    tgemm_nn_raw(sA, lda, p.Bm, p.ldb, p.N, p.K, raw, wave, nw);
+    __syncthreads();
+    const int ldr = ld16(p.N), kparts = tile_kparts((p.N + 63) >> 6, nw);
+    for (int e = threadIdx.x; e < MMG_TM * p.N; e += MMG_BLOCK) {
+        const int m = e / p.N, n = e - m * p.N;
+        if (b0 + m < B) p.C[(size_t)(b0 + m) * p.ldc + n] = raw_sum(raw, ldr, kparts, m, n);
     }
 }
 

@@ -231,8 +231,14 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
     X(vhid_r, float, 0, 3, T, B, K)                                                \
     X(vdbs, float, 0, 2, T, B, 1)                                                  \
     X(vdbr, float, 0, 2, T, B, 1)                                                  \
+    /* ---- per-call VJPs of the agent modules (mmg_sender_vjp / _receiver_vjp / _baseline_vjp): operand copies of one call ---- */ \
+    X(vcz, float, 0, 2, B, W, 1)         /* z (receiver, baseline_rec) | z_r (baseline_sen) of the call     */ \
+    X(vch0, float, 0, 2, B, R, 1)        /* receiver: h_prev (zeros for a first call)                      */ \
+    X(vch1, float, 0, 2, B, R, 1)        /* receiver: h_new; baseline_rec: inp                             */ \
+    X(vchx, float, 0, 2, B, H, 1)        /* baseline_sen: x (= sender.h_x)                                 */ \
+    X(vcdh, float, 0, 2, B, K, 1)        /* baselines: d hidden = dscore w2 1[hidden > 0] (A of k_vjp_nn)  */ \
     X(tables, uint8_t, 1, 1, 98304, 1, 1) /* GEMM / column-sum job descriptors      */ \
-    X(vtables, uint8_t, 1, 1, 4 * MMG_VJP_TABLE_BYTES, 1, 1) /* the VJP's four job tables (one per agent), uploaded at mmg_create */
+    X(vtables, uint8_t, 1, 1, 8 * MMG_VJP_TABLE_BYTES, 1, 1) /* VJP job tables: the exchange's four (one per agent), then the per-call four, uploaded at mmg_create */
 
 // statistics vector (f64).  Per stream (0 = stop bits, 1 = receiver msgs, 2 = sender msgs) and
 // step: n, sum w, sum w^2, sum w*logp, sum negent; per baseline (0 = rec, 1 = sen) and step:

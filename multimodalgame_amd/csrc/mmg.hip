@@ -113,7 +113,7 @@ struct mmg_handle {
     // while it is set, the training entries refuse to run
     bool corrupt_on = false;
     uint32_t corrupt[MMG_BLOCK / 32] = {};
-    WgHead vjp_hd[4] = {};      // launch geometry of k_wgrad over the four VJP job tables (tape.vtables, mmg_exchange_vjp)
+    WgHead vjp_hd[8] = {};      // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
     mmg_handle() : params(nullptr), grads(nullptr), opt_state(nullptr), ws(nullptr), d_jt(nullptr), h_err(nullptr), d_err(nullptr),
                    no_roles(false), degraded(false), recoveries(0), last_code(0u), ar_fn(nullptr), ar_comm(nullptr) {}
     ~mmg_handle() {
@@ -394,14 +394,16 @@ static int build_jobs(mmg_handle* h) {
 // Job tables of mmg_exchange_vjp (kernels_vjp.h): one per agent, each writing only that agent's gradient slice.  Same job kinds as
 // build_jobs, but every (step, sample) job reduces over ALL T * B rows (rows of steps t >= n_steps carry zero deltas), no row
 // splits, no live-row list, no special block.  They depend on the shape only: built and uploaded once, at mmg_create.
+// percall: the tables of the per-call VJPs (mmg_sender_vjp / _receiver_vjp / _baseline_vjp) -- the same jobs over the B rows of
+// one call, with the operands the exchange reads from the tape taken from the call's copies (vcz, vch0, vch1, vchx).
 // ---------------------------------------------------------------------------------------------
-static int build_vjp_job_table(mmg_handle* h, int agent, JobTable& jt) {
+static int build_vjp_job_table(mmg_handle* h, int agent, bool percall, JobTable& jt) {
     memset(&jt, 0, sizeof(jt));
     const Dims& d = h->dm;
     const Tape& tp = h->tp;
     const Params &G = h->G, &P = h->P;
     const int B = d.B, H = d.H, W = d.W, R = d.R, V = d.V, K = d.K, D = d.D, F = d.F;
-    const int TB = d.T * B;
+    const int TB = percall ? B : d.T * B;
     int tiles = 0, ng = 0, cblocks = 0, nc = 0;
     auto gemm = [&](const float* A, int lda, const float* Bm, int ldb, int bmod, int bsrc, float* C, int ldc, int rows, int N, int Kk) {
         GemmJob& g = jt.g[ng++];
@@ -422,10 +424,12 @@ static int build_vjp_job_table(mmg_handle* h, int agent, JobTable& jt) {
         cblocks += (cols + 15) / 16;
         return c;
     };
-    const float* h_after = tp.h + (size_t)B * R;
+    const float* h_before = percall ? tp.vch0 : tp.h;
+    const float* h_after = percall ? tp.vch1 : tp.h + (size_t)B * R;
+    const float* z_in = percall ? tp.vcz : tp.z;
     if (agent == MMG_AGENT_RECEIVER) {
-        gemm(tp.vdgi, 3 * R, tp.z, W, 0, SRC_STATIC, G.p[R_WIH], W, TB, 3 * R, W);              // rnn.weight_ih
-        gemm(tp.vdgh, 3 * R, tp.h, R, 0, SRC_STATIC, G.p[R_WHH], R, TB, 3 * R, R);              // rnn.weight_hh (h before the step)
+        gemm(tp.vdgi, 3 * R, z_in, W, 0, SRC_STATIC, G.p[R_WIH], W, TB, 3 * R, W);              // rnn.weight_ih
+        gemm(tp.vdgh, 3 * R, h_before, R, 0, SRC_STATIC, G.p[R_WHH], R, TB, 3 * R, R);          // rnn.weight_hh (h before the step)
         col(tp.vdgi, 3 * R, TB, 3 * R, G.p[R_BIH], nullptr);
         col(tp.vdgh, 3 * R, TB, 3 * R, G.p[R_BHH], nullptr);
         gemm(tp.vdA, R, h_after, R, 0, SRC_STATIC, G.p[R_Y1_W], R + V, TB, R, R);               // y1.weight[:, :R]: dA_t over T * B rows
@@ -449,14 +453,14 @@ static int build_vjp_job_table(mmg_handle* h, int agent, JobTable& jt) {
         gemm(tp.vdlz, W, tp.va, H, 0, SRC_STATIC, G.p[S_BIN_W], H, TB, W, H);                   // binary_layer
         col(tp.vdlz, W, TB, W, G.p[S_BIN_B], nullptr);
     } else if (agent == MMG_AGENT_BASELINE_REC) {                                                // input [z || h_after]
-        gemm_virt(tp.vdbr, tp.vhid_r, P.p[BR_L2_W], tp.z, W, 0, G.p[BR_L1_W], W + R, TB, K, W);
+        gemm_virt(tp.vdbr, tp.vhid_r, P.p[BR_L2_W], z_in, W, 0, G.p[BR_L1_W], W + R, TB, K, W);
         gemm_virt(tp.vdbr, tp.vhid_r, P.p[BR_L2_W], h_after, R, 0, G.p[BR_L1_W] + W, W + R, TB, K, R);
         ColJob& c1 = col(tp.vhid_r, K, TB, K, G.p[BR_L1_B], nullptr); c1.vbeta = tp.vdbr; c1.vw2 = P.p[BR_L2_W];
         col(tp.vhid_r, K, TB, K, G.p[BR_L2_W], nullptr).wrow = tp.vdbr;
         col(tp.vdbr, 1, TB, 1, G.p[BR_L2_B], nullptr);
     } else {                                                                                    // input [h_x || z_r]
-        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], tp.hx, H, B, G.p[BS_L1_W], H + W, TB, K, H);
-        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], tp.vzr, W, 0, G.p[BS_L1_W] + H, H + W, TB, K, W);
+        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], percall ? tp.vchx : tp.hx, H, B, G.p[BS_L1_W], H + W, TB, K, H);
+        gemm_virt(tp.vdbs, tp.vhid_s, P.p[BS_L2_W], percall ? tp.vcz : tp.vzr, W, 0, G.p[BS_L1_W] + H, H + W, TB, K, W);
         ColJob& c1 = col(tp.vhid_s, K, TB, K, G.p[BS_L1_B], nullptr); c1.vbeta = tp.vdbs; c1.vw2 = P.p[BS_L2_W];
         col(tp.vhid_s, K, TB, K, G.p[BS_L2_W], nullptr).wrow = tp.vdbs;
         col(tp.vdbs, 1, TB, 1, G.p[BS_L2_B], nullptr);
@@ -476,13 +480,13 @@ static int build_vjp_job_table(mmg_handle* h, int agent, JobTable& jt) {
 
 static int upload_vjp_tables(mmg_handle* h) {
     static_assert(sizeof(JobTable) <= MMG_VJP_TABLE_BYTES, "a VJP job table does not fit its tape slot");
-    std::vector<JobTable> tabs(4);
-    for (int a = 0; a < 4; ++a) {
-        if (build_vjp_job_table(h, a, tabs[a])) return -1;
+    std::vector<JobTable> tabs(8);
+    for (int a = 0; a < 8; ++a) {
+        if (build_vjp_job_table(h, a % 4, a >= 4, tabs[a])) return -1;
         WgHead& hd = h->vjp_hd[a];
         hd.gemm_tiles = tabs[a].gemm_tiles; hd.n_wblocks = tabs[a].n_wblocks; hd.special_block = -1; hd.special_job = -1;
     }
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < 8; ++a)
         HIP_OK(hipMemcpy(h->tp.vtables + (size_t)a * MMG_VJP_TABLE_BYTES, &tabs[a], sizeof(JobTable), hipMemcpyHostToDevice));
     return 0;
 }
@@ -1660,6 +1664,26 @@ extern "C" int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, 
     return launch_check("k_baselines(agent)");
 }
 
+// The weight gradients of a VJP: k_wgrad over job table `slot` of tape.vtables (0-3: exchange, 4-7: per call, agent = slot % 4) --
+// its tiles and column blocks only (no spare block: the logged losses, running totals and gradient tail stay untouched), no
+// live-row list.  Writes only the agent's slice of the gradient buffer.
+static int launch_vjp_wgrad(mmg_handle* h, hipStream_t st, int slot, const float* d_x, const float* d_desc) {
+    const JobTable* djt = reinterpret_cast<const JobTable*>(h->tp.vtables + (size_t)slot * MMG_VJP_TABLE_BYTES);
+    const WgHead hd = h->vjp_hd[slot];
+    WgOpt wo;
+    memset(&wo, 0, sizeof(wo));
+    Scope sc(h, st, "k_wgrad");
+    hipLaunchKernelGGL(k_wgrad<false>, dim3(hd.n_wblocks), dim3(MMG_BLOCK), 0, st,
+                       djt, d_x, d_desc, h->tp.gnpart, h->dm, (const double*)h->tp.stats, h->tp.losses, h->tp.totals,
+                       (const int*)nullptr, (const int*)nullptr, h->tp.wpart, reinterpret_cast<uint32_t*>(h->tp.wcnt),
+                       (const uint32_t*)h->tp.sync, h->grads + h->pl.total, wo, 0, hd
+#ifdef MMG_TIMING
+                       , h->tp.dbg2
+#endif
+                       );
+    return launch_check("k_wgrad");
+}
+
 // ---------------------------------------------------------------------------------------------
 // mmg_exchange_vjp: the backward pass of ONE agent's autograd graph of the last training exchange (kernels_vjp.h).  Reads the
 // run-all tape of mmg_exchange_forward(train = 1, run_all_steps = 1); writes only that agent's slice of the gradient buffer.
@@ -1708,20 +1732,143 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
         hipLaunchKernelGGL(k_vjp_bas, dim3(d.T * d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in, agent);
         if (launch_check("k_vjp_bas")) return -1;
     }
-    // the weight gradients: k_wgrad over the agent's own job table -- its tiles and column blocks only (no spare block: the
-    // logged losses, running totals and gradient tail stay untouched), no live-row list
-    const JobTable* djt = reinterpret_cast<const JobTable*>(h->tp.vtables + (size_t)agent * MMG_VJP_TABLE_BYTES);
-    const WgHead hd = h->vjp_hd[agent];
-    WgOpt wo;
-    memset(&wo, 0, sizeof(wo));
-    Scope sc(h, st, "k_wgrad");
-    hipLaunchKernelGGL(k_wgrad<false>, dim3(hd.n_wblocks), dim3(MMG_BLOCK), 0, st,
-                       djt, d_x, d_desc, h->tp.gnpart, h->dm, (const double*)h->tp.stats, h->tp.losses, h->tp.totals,
-                       (const int*)nullptr, (const int*)nullptr, h->tp.wpart, reinterpret_cast<uint32_t*>(h->tp.wcnt),
-                       (const uint32_t*)h->tp.sync, h->grads + h->pl.total, wo, 0, hd
-#ifdef MMG_TIMING
-                       , h->tp.dbg2
-#endif
-                       );
-    return launch_check("k_wgrad");
+    return launch_vjp_wgrad(h, st, agent, d_x, d_desc);
+}
+
+// Can a per-call product run on the MFMA tiles of k_vjp_nn?  tgemm_nn_raw reads Bm rows as float4 (16-byte aligned rows, N a
+// multiple of 4) and k_vjp_nn stages a [16, K] A tile plus the raw accumulators in LDS.
+static bool vjp_nn_fits(const NnProd& p) {
+    return p.N >= 4 && p.N % 4 == 0 && p.ldb % 4 == 0 && ((uintptr_t)p.Bm & 15) == 0 &&
+           sizeof(float) * (size_t)vjp_nn_smem_floats(p.N, p.K) <= 65536;
+}
+
+// Up to two products in one launch (B / 16 tiles each).  np == 0: nothing.
+static int launch_vjp_nn(mmg_handle* h, hipStream_t st, int np, const NnProd& p0, const NnProd& p1) {
+    if (np == 0) return 0;
+    const NnProd& q = np > 1 ? p1 : p0;
+    const int f0 = vjp_nn_smem_floats(p0.N, p0.K), f1 = vjp_nn_smem_floats(q.N, q.K);
+    const size_t smem = sizeof(float) * (size_t)(f0 > f1 ? f0 : f1);
+    Scope sc(h, st, "k_vjp_nn");
+    hipLaunchKernelGGL(k_vjp_nn, dim3((h->dm.B + MMG_TM - 1) / MMG_TM, np), dim3(MMG_BLOCK), smem, st, h->dm.B, p0, q);
+    return launch_check("k_vjp_nn");
+}
+
+static NnProd nn_prod(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int N, int K) {
+    NnProd p;
+    p.A = A; p.Bm = Bm; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.N = N; p.K = K;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The per-call VJPs of the agent modules' forward() (kernels_vjp.h: k_vjp_sen_call / k_vjp_rec_call / k_vjp_bas_call): the
+// backward pass of ONE mmg_sender_forward / mmg_receiver_forward / mmg_baseline_forward call from the caller's copies of its
+// inputs and outputs -- never the tape of a forward.  Each writes only its agent's slice of the gradient buffer.
+// ---------------------------------------------------------------------------------------------
+extern "C" int mmg_sender_vjp(mmg_handle* h, const float* d_x, const float* d_w, int t, const float* d_h_x, const float* d_probs,
+                              const float* d_dout, const float* d_dh_x, float* d_dx, float* d_dw, void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (!d_x || !d_h_x) return fail("x / h_x must not be NULL");
+    if (t < 0 || t >= d.T) return fail("t out of range");
+    if (t > 0 && !d_w) return fail("w must not be NULL for t > 0");
+    if (d.use_binary && d_dout && !d_probs) return fail("probs must not be NULL when d probs is given (binary messages)");
+    const size_t smem = sizeof(float) * (size_t)vjp_sen_smem_floats(d);
+    if (smem > 65536) return fail("the sender VJP needs %zu bytes of LDS (h_dim too large)", smem);
+    hipStream_t st = (hipStream_t)stream;
+    SenCall c;
+    c.w = d_w; c.h_x = d_h_x; c.probs = d.use_binary ? d_probs : nullptr; c.dout = d_dout; c.dh_x = d_dh_x;
+    c.dx = d_dx; c.dw = d_dw; c.t = t;
+    // W_c^T dpre (-> vdc0 at t = 0, d w after) and d x = W_img^T d h_x on the MFMA tiles where the shape allows
+    NnProd pr[2];
+    int np = 0;
+    float* q_out = t == 0 ? h->tp.vdc0 : d_dw;
+    const NnProd pq = nn_prod(h->tp.vdpre, d.H, h->P.p[S_CODE_W], d.W, q_out, d.W, d.W, d.H);
+    const NnProd px = nn_prod(h->tp.vdhx, d.H, h->P.p[S_IMG_W], d.F, d_dx, d.F, d.F, d.H);
+    c.q_tiles = vjp_nn_fits(pq) ? 1 : 0;
+    c.dx_tiles = vjp_nn_fits(px) ? 1 : 0;
+    if (c.q_tiles && q_out) pr[np++] = pq;
+    if (c.dx_tiles && d_dx) pr[np++] = px;
+    {
+        Scope sc(h, st, "k_vjp_sen_call");
+        hipLaunchKernelGGL(k_vjp_sen_call, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, d_x, c);
+        if (launch_check("k_vjp_sen_call")) return -1;
+    }
+    if (launch_vjp_nn(h, st, np, pr[0], pr[1])) return -1;
+    return launch_vjp_wgrad(h, st, 4 + MMG_AGENT_SENDER, d_x, nullptr);
+}
+
+extern "C" int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_desc, const float* d_h_prev, const float* d_h_new,
+                                const float* d_y, const float* d_w_probs, const float* d_s_prob, const float* d_dy,
+                                const float* d_dw, const float* d_dps, const float* d_dh_w, const float* d_dh_new,
+                                float* d_dz, float* d_dh_prev, void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (!d_z || !d_desc || !d_h_new || !d_y) return fail("z / desc / h_new / y must not be NULL");
+    if (d.use_binary && d_dw && !d_w_probs) return fail("w_probs must not be NULL when d w_probs is given (binary messages)");
+    if (d_dps && !d_s_prob) return fail("s_prob must not be NULL when d s_prob is given");
+    const size_t smem = sizeof(float) * (size_t)vjp_rec_smem_floats(d);
+    if (smem > 65536) return fail("the receiver VJP needs %zu bytes of LDS (too many classes)", smem);
+    hipStream_t st = (hipStream_t)stream;
+    RecCall c;
+    c.z = d_z; c.h_prev = d_h_prev; c.h_new = d_h_new; c.y = d_y; c.w_probs = d.use_binary ? d_w_probs : nullptr; c.s_prob = d_s_prob;
+    c.dy = d_dy; c.dw = d_dw; c.dps = d_dps; c.dh_w = d_dh_w; c.dh_new = d_dh_new; c.dz = d_dz; c.dh_prev = d_dh_prev;
+    const NnProd pz = nn_prod(h->tp.vdgi, 3 * d.R, h->P.p[R_WIH], d.W, d_dz, d.W, d.W, 3 * d.R);      // d z = dgi . W_ih
+    c.dz_tiles = vjp_nn_fits(pz) ? 1 : 0;
+    VjpIn in;
+    memset(&in, 0, sizeof(in));
+    in.dy = d_dy; in.n = 1;                                    // k_vjp_class over the call's B rows
+    {
+        Scope sc(h, st, "k_vjp_cd");
+        hipLaunchKernelGGL(k_vjp_cd, dim3(d.D), dim3(MMG_BLOCK), 0, st, d, h->P, h->tp, d_desc);
+        if (launch_check("k_vjp_cd")) return -1;
+    }
+    {
+        Scope sc(h, st, "k_vjp_rec_call");
+        hipLaunchKernelGGL(k_vjp_rec_call, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, c);
+        if (launch_check("k_vjp_rec_call")) return -1;
+    }
+    if (launch_vjp_nn(h, st, (c.dz_tiles && d_dz) ? 1 : 0, pz, pz)) return -1;
+    {
+        Scope sc(h, st, "k_vjp_class");
+        hipLaunchKernelGGL(k_vjp_class, dim3(d.D), dim3(MMG_BLOCK), 0, st, d, h->P, h->tp, in);
+        if (launch_check("k_vjp_class")) return -1;
+    }
+    return launch_vjp_wgrad(h, st, 4 + MMG_AGENT_RECEIVER, nullptr, d_desc);
+}
+
+extern "C" int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
+                                const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (which != MMG_AGENT_BASELINE_REC && which != MMG_AGENT_BASELINE_SEN)
+        return fail("which must be MMG_AGENT_BASELINE_REC or MMG_AGENT_BASELINE_SEN");
+    if (rows != d.B) return fail("rows must equal the handle's batch (%d, got %d)", d.B, rows);
+    if (!d_binary) return fail("binary must not be NULL");
+    if (which == MMG_AGENT_BASELINE_REC && !d_inp) return fail("baseline_rec needs inp (receiver hidden state)");
+    if (which == MMG_AGENT_BASELINE_SEN && !d_x) return fail("baseline_sen needs x (sender.h_x)");
+    const size_t smem = sizeof(float) * (size_t)vjp_bas_call_smem_floats(d, which);
+    if (smem > 65536) return fail("the baseline VJP needs %zu bytes of LDS", smem);
+    hipStream_t st = (hipStream_t)stream;
+    BasCall c;
+    c.x = d_x; c.binary = d_binary; c.inp = d_inp; c.dscore = d_dscore; c.dx = d_dx; c.dbinary = d_dbinary; c.dinp = d_dinp;
+    // the input gradients d hidden . W1[:, columns of the input] on the MFMA tiles where both column ranges allow
+    const bool rec = which == MMG_AGENT_BASELINE_REC;
+    const int n1 = rec ? d.W : d.H, nin = rec ? d.W + d.R : d.H + d.W;
+    const float* W1 = h->P.p[rec ? BR_L1_W : BS_L1_W];
+    float* out1 = rec ? d_dbinary : d_dx;
+    float* out2 = rec ? d_dinp : d_dbinary;
+    const NnProd p1 = nn_prod(h->tp.vcdh, d.K, W1, nin, out1, n1, n1, d.K);
+    const NnProd p2 = nn_prod(h->tp.vcdh, d.K, W1 + n1, nin, out2, nin - n1, nin - n1, d.K);
+    NnProd pr[2];
+    int np = 0;
+    c.tiles = (out1 || out2) && vjp_nn_fits(p1) && vjp_nn_fits(p2) ? 1 : 0;
+    if (c.tiles && out1) pr[np++] = p1;
+    if (c.tiles && out2) pr[np++] = p2;
+    {
+        Scope sc(h, st, "k_vjp_bas_call");
+        hipLaunchKernelGGL(k_vjp_bas_call, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, c, which);
+        if (launch_check("k_vjp_bas_call")) return -1;
+    }
+    if (launch_vjp_nn(h, st, np, pr[0], pr[1])) return -1;
+    return launch_vjp_wgrad(h, st, 4 + which, nullptr, nullptr);
 }

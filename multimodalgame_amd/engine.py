@@ -70,6 +70,17 @@ class Engine(object):
         # bumped by every call that rewrites the forward tape (forward, train_step(s), dp_*, the agent-level forwards): an autograd
         # node of Game.exchange() refuses to run its VJP on a tape that is no longer the one its forward left
         self.generation = 0
+        # parameter version, shared by the engines over the same flat buffers: bumped by every call that changes the parameters
+        # (or the optimizer state) behind torch's back -- load_state_dicts, clip_step, train_step(s), dp_train_step(s).  A node of
+        # an agent module's forward() refuses to run its VJP on parameters that are no longer its forward's.
+        self._param_version = share._param_version if share is not None else [0]
+
+    @property
+    def param_version(self):
+        return self._param_version[0]
+
+    def bump_param_version(self):
+        self._param_version[0] += 1
 
     def __del__(self):
         try:
@@ -94,6 +105,7 @@ class Engine(object):
 
     def load_state_dicts(self, sd):
         """sd: {agent: {key: array-like}} -> copied into the flat parameter buffer."""
+        self.bump_param_version()
         for agent, d in sd.items():
             for k, v in d.items():
                 self.params[agent][k].copy_(torch.as_tensor(v, dtype=torch.float32).to(self.device).view_as(self.params[agent][k]))
@@ -150,11 +162,13 @@ class Engine(object):
                                          self._ptr(desc, torch.float32), self._stream()))
 
     def clip_step(self):
+        self.bump_param_version()
         _lib.check(self.lib.mmg_clip_step(self.handle, self._stream()))
 
     def train_step(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0):
         f32 = torch.float32
         self.generation += 1
+        self.bump_param_version()
         _lib.check(self.lib.mmg_train_step(
             self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
             self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed), self._stream()))
@@ -165,6 +179,7 @@ class Engine(object):
         B = self.cfg.batch
         assert x.size(0) >= n * B and target.size(0) >= n * B
         self.generation += 1
+        self.bump_param_version()
         _lib.check(self.lib.mmg_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                             self._ptr(desc, torch.float32), C.c_uint64(seed), self._stream()))
 
@@ -175,6 +190,7 @@ class Engine(object):
     def dp_train_step(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0, full_tape=False, reduce=True):
         f32 = torch.float32
         self.generation += 1
+        self.bump_param_version()
         _lib.check(self.lib.mmg_dp_train_step(
             self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
             self._ptr(u_z, f32), self._ptr(u_s, f32), self._ptr(u_w, f32), C.c_uint64(seed), int(bool(full_tape)), int(bool(reduce)),
@@ -184,6 +200,7 @@ class Engine(object):
         B = self.cfg.batch
         assert x.size(0) >= n * B and target.size(0) >= n * B
         self.generation += 1
+        self.bump_param_version()
         _lib.check(self.lib.mmg_dp_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                                self._ptr(desc, torch.float32), C.c_uint64(seed), int(bool(reduce)), self._stream()))
 
@@ -257,6 +274,63 @@ class Engine(object):
             self.handle, _lib.AGENTS.index(agent), int(n_steps), self._ptr(x, f32), self._ptr(desc, f32),
             self._ptr(args["dy"]), self._ptr(args["dz"]), self._ptr(args["dw"]), self._ptr(args["dps"]),
             self._ptr(args["dbs"]), self._ptr(args["dbr"]), self._stream()))
+
+    # ------------------------------------------------------------------ per-call vector-Jacobian products
+    def _vjp_args(self, named):
+        """(name, tensor or None, floats per sample) -> device pointers of fp32 contiguous copies, checked to hold B rows."""
+        B, out, keep = self.cfg.batch, [], []
+        for name, t, width in named:
+            if t is not None:
+                t = t.detach().to(self.device, torch.float32).contiguous()
+                if t.numel() != B * width:
+                    raise ValueError("%s: %d entries for %d samples x %d" % (name, t.numel(), B, width))
+                keep.append(t)
+            out.append(self._ptr(t))
+        return out, keep
+
+    def _grad_out(self, want, width):
+        return torch.empty(self.cfg.batch, width, device=self.device) if want else None
+
+    def sender_vjp(self, x, w, t, h_x, probs, dout=None, dh_x=None, want_dx=False, want_dw=False):
+        """Backward pass of ONE sender_forward call (include/mmg.h: mmg_sender_vjp): writes self.grads["sender"] from the
+        upstream gradients of its probs (binary) | message logits (continuous) and of h_x; returns (d x, d w), None where not
+        wanted.  None upstream = zero."""
+        c = self.cfg
+        (px, pw, phx, pp, pdo, pdh), keep = self._vjp_args(
+            (("x", x, c.feat_dim), ("w", w if t > 0 else None, c.w_dim), ("h_x", h_x, c.h_dim),
+             ("probs", probs if c.use_binary else None, c.w_dim), ("dout", dout, c.w_dim), ("dh_x", dh_x, c.h_dim)))
+        dx, dw = self._grad_out(want_dx, c.feat_dim), self._grad_out(want_dw and t > 0, c.w_dim)
+        _lib.check(self.lib.mmg_sender_vjp(self.handle, px, pw, int(t), phx, pp, pdo, pdh, self._ptr(dx), self._ptr(dw),
+                                           self._stream()))
+        return dx, dw
+
+    def receiver_vjp(self, z, desc, h_prev, h_new, y, w_probs, s_prob, dy=None, dw=None, dps=None, dh_w=None, dh_new=None,
+                     want_dz=False, want_dh_prev=False):
+        """Backward pass of ONE receiver_forward call (include/mmg.h: mmg_receiver_vjp): writes self.grads["receiver"];
+        returns (d z, d h_prev), None where not wanted.  h_prev None: the zero state of a first call.  None upstream = zero."""
+        c = self.cfg
+        R, W, D = c.rec_hidden, c.w_dim, c.n_classes
+        desc = desc.detach().to(self.device, torch.float32).contiguous()
+        (pz, ph0, ph1, py, ppw, pps, pdy, pdw, pdps, pdhw, pdhn), keep = self._vjp_args(
+            (("z", z, W), ("h_prev", h_prev, R), ("h_new", h_new, R), ("y", y, D), ("w_probs", w_probs if c.use_binary else None, W),
+             ("s_prob", s_prob, 1), ("dy", dy, D), ("dw", dw, W), ("dps", dps, 1), ("dh_w", dh_w, R), ("dh_new", dh_new, R)))
+        dz, dh0 = self._grad_out(want_dz, W), self._grad_out(want_dh_prev and h_prev is not None, R)
+        _lib.check(self.lib.mmg_receiver_vjp(self.handle, pz, self._ptr(desc), ph0, ph1, py, ppw, pps, pdy, pdw, pdps, pdhw, pdhn,
+                                             self._ptr(dz), self._ptr(dh0), self._stream()))
+        return dz, dh0
+
+    def baseline_vjp(self, which, x, binary, inp, dscore=None, want=(False, False, False)):
+        """Backward pass of ONE baseline_forward call (include/mmg.h: mmg_baseline_vjp): writes self.grads[which]; returns
+        (d x, d binary, d inp), None where not wanted or absent."""
+        c = self.cfg
+        widths = (c.h_dim, c.w_dim, c.rec_hidden)
+        ins = (x, binary, inp)
+        (px, pb, pi, pds), keep = self._vjp_args(
+            (("x", x, widths[0]), ("binary", binary, widths[1]), ("inp", inp, widths[2]), ("dscore", dscore, 1)))
+        outs = [self._grad_out(wnt and v is not None, wd) for wnt, v, wd in zip(want, ins, widths)]
+        _lib.check(self.lib.mmg_baseline_vjp(self.handle, _lib.AGENTS.index(which), px, pb, pi, c.batch, pds,
+                                             *[self._ptr(o) for o in outs], self._stream()))
+        return tuple(outs)
 
     # ------------------------------------------------------------------ profiling
     def set_profiling(self, on):

@@ -119,6 +119,9 @@ class FlatOptimizer(object):
 
     def load_state_dict(self, sd):
         eng, kind = self.game.engine, self.game.cfg["optim_type"]
+        # The parameters themselves do not change here, but a pending node of an agent module's forward() was recorded before
+        # the optimizer state it is meant to be stepped with: it raises, as for the other library-side updates (Engine.param_version).
+        eng.bump_param_version()
         n = eng.n_params
         step = 0
         for i, (name, view) in enumerate(self._params()):
