@@ -1,0 +1,189 @@
+// host_launch.h -- host side of mmg.hip: the handle, the timing scope of a launch and the launch helpers that more than one
+// entry point uses.  Included by mmg.hip only (after the kernels and fail() / HIP_OK).
+#pragma once
+
+struct KernelTimer { std::string name; hipEvent_t t0, t1; };
+
+// What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes and the
+// co-residency budgets.  Constant until the next selection (mmg_create; error_gate after a timed-out dependency).
+struct Selection {
+    int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
+    bool sw_merge_bas = false;   // (= merge_roles) the baselines' forward pass rides in the backward / statistics launch; off: its own launch
+    bool sw_merge_prep = false;  // k_prep's blocks as roles of k_conversation_fast3's launch (MMG_NO_MERGE_PREP=1: a launch of their own)
+    bool game_ok = false;        // fused step of the small Adaptive agents: conversation + statistics + baselines + backward in ONE launch (kernels_game.h); MMG_NO_GAME=1: off
+    int game_bas_ub = 1;         // ... 64-unit blocks of a baseline per role: 2 when the block count is even
+    int game_nbas = 0;           // ... its baseline roles (a multiple of 2 * ceil(K / 64), sized by the co-residency budget)
+    int wgrad_stride = 0;        // > 0: k_wgrad's GEMM tiles are walked by this many resident workgroups (more tiles than slots); 0: one workgroup per tile
+    bool wgrad_opt_ok = false;   // the clip + optimizer step can run inside k_wgrad's launch (k_wgrad<true>: every block co-resident, no row splits); MMG_NO_WGRAD_OPT=1: off
+    bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
+    bool merge_roles = false;    // MMG_NO_MERGE=1 keeps k_stats / k_dC / basehx as separate launches / in-kernel work
+    // sample-tile MFMA path (kernels_tile.h): every shape the register-resident kernels do not cover
+    bool tile_ok = false;        // its LDS plan fits (MMG_NO_TILE=1: never use it)
+    bool rc_bwd = false;         // ... and the reverse-time loop of its backward as co-resident roles over 16-unit slices (k_rc_bwd); MMG_NO_RC_BWD=1: k_bwd_tile's loop
+    bool rc_persist = false;     // ... as ONE launch of co-resident roles (k_rc_persist) when they all fit on the device; MMG_NO_RC_PERSIST=1: per-step launches
+    int rc_budget = 0;
+    bool rc_fwd = false;         // wide receiver (kernels_rc.h): the tile's receiver step as three chip-wide launches over 16-unit slices -- the
+                                 // one-workgroup-per-tile forward does not fit its LDS plan (R > 128 with a 256-bit message); MMG_NO_RC=1: off
+    bool tile_force = false;     // MMG_TILE=1: use it even where the register-resident kernels apply (cross-checks)
+    bool tile_ext = false;       // the sender MLP of a step runs as its own chip-wide launches (k_send_s1 / k_send_s2)
+    int tile_nt = 0, tile_smem = 0;   // threads per tile workgroup, dynamic LDS bytes
+    int tile_bwd_smem = 0, send_bwd_smem = 0;
+    bool tile_persist = false;   // the whole conversation as one launch of co-resident roles (k_conv_persist)
+    bool tile_split = false;     // many classes: idle CUs as class helpers of the sample tiles (k_conv_split)
+    int split_nh = 0, split_per = 0, split_smem = 0;
+    int persist_ns1 = 0, persist_ns2 = 0, persist_smem = 0;
+    // debugging switches of the launch paths (environment, read ONCE at mmg_create -- never on the per-minibatch path)
+    bool sw_rsample = false, sw_rmsg = false, sw_fused_s = false, rs_capable = false;
+    bool persist_ll = false;     // k_conv_persist's fused sender roles hand over (value, epoch) pairs in per-step slots (tape.pll_*); MMG_NO_PERSIST_LL=1: counters
+    bool mc_ok = false;          // many-class register-resident conversation (kernels_mc.h); MMG_NO_MC=1: off
+    bool mc3p_ok = false;        // ... for batches of several rounds of workgroups: two sample tiles per workgroup, pipelined (kernels_mc3p.h); MMG_NO_MC3P=1: off
+    bool mc3_ok = false;         // continuous messages: the one-wave-per-SIMD many-class kernel (kernels_mc3.h); binary messages: k_conversation_mc
+    bool any_split = false;      // some k_wgrad job splits its rows over workgroups (the last slice to arrive adds the partial tiles)
+    bool wgrad_small_split = false;   // jobs with few output tiles split their (step, sample) rows further (layout.h: wgrad_job_nsplit)
+    int mc_per = 0, mc_xcd = 0;  // classes per member of a tile; mc_xcd: a tile's 16 workgroups on one XCD
+    // workgroups of 512 threads that are guaranteed to be resident together on this device (occupancy query at mmg_create,
+    // minus a margin): the role launches (k_conv_persist / k_conv_split / k_conversation_mc) spin on each other, so a launch
+    // may never hold more roles than this
+    int resident_budget = 0, split_budget = 0, n_cu = 0;
+};
+
+// What the last forward pass left for the later phases of the same minibatch (mmg_loss_stats / mmg_backward may be separate ABI
+// calls).  Reset where a forward pass starts (exchange_forward_impl); the fused step (k_game_fast) states all of it.
+struct ForwardState {
+    bool scores_in_parts = false;   // the last forward left baseline scores as partials (k_baselines2)
+    bool bas_deferred = false;      // the fused step's forward left the baselines to the backward launch (k_bwd_conv_fast: baseline roles)
+    bool bas_pending = false;       // phased step: the forward pass left the baselines to mmg_loss_stats (k_bas_stats: one launch for both)
+    bool basehx_ready = false;      // this forward pass formed tape.basehx inside the conversation launch
+};
+
+struct mmg_handle {
+    mmg_config cfg = {};
+    Dims dm = {};
+    ParamLayout pl = {};
+    TapeLayout tl = {};
+    Params P = {}, G = {};
+    Tape tp = {};
+    float *params = nullptr, *grads = nullptr, *opt_state = nullptr;
+    void* ws = nullptr;
+    JobTable* d_jt = nullptr;
+    JobTable jt = {};
+    Selection sel;
+    ForwardState fwd;
+    bool profiling = false;
+    std::vector<KernelTimer> timers;
+    size_t timers_used = 0;
+    uint32_t* h_err = nullptr;   // pinned host copy of sync[MMG_SYNC_ERR], written by k_opt of every step (posted store to mapped host memory)
+    uint32_t* d_err = nullptr;   // its device-side address
+    bool xcd_rule_ok = false;    // probed at mmg_create (k_xcc_probe): workgroup i of a launch runs on XCD i % 8 -- a hand-off between workgroups of one XCD may stay in its L2
+    // fail-soft (round 6): no_roles = only launches without in-launch waits are selected (select_paths).  Set at mmg_create by
+    // MMG_NO_ROLES=1 / a CU mask in the environment, or by recover() after a timed-out dependency (degraded)
+    bool no_roles = false, degraded = false;
+    int recoveries = 0;          // recover() calls so far (bounded: a wait that keeps timing out without roles is a real fault)
+    uint32_t last_code = 0u;     // the dependency word of the last recovery
+    // data-parallel step inside the library (mmg_dp_set_allreduce): RCCL's ncclAllReduce by address + the caller's communicator
+    void* ar_fn = nullptr; void* ar_comm = nullptr;
+    // mmg_set_message_corruption: the mask every evaluation conversation applies to the sender's messages (model.py:813-820);
+    // while it is set, the training entries refuse to run
+    bool corrupt_on = false;
+    uint32_t corrupt[MMG_BLOCK / 32] = {};
+    WgHead vjp_hd[8] = {};       // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
+    ~mmg_handle() {
+        for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }
+        if (h_err) hipHostFree(h_err);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// launch helper with optional HIP-event timing on the launch stream
+// ---------------------------------------------------------------------------------------------
+struct Scope {
+    mmg_handle* h; hipStream_t st; KernelTimer* kt;
+    Scope(mmg_handle* h_, hipStream_t st_, const char* name) : h(h_), st(st_), kt(nullptr) {
+        if (!h->profiling) return;
+        if (h->timers_used == h->timers.size()) {
+            KernelTimer t; hipEventCreate(&t.t0); hipEventCreate(&t.t1); h->timers.push_back(t);
+        }
+        kt = &h->timers[h->timers_used++];
+        kt->name = name;
+        hipEventRecord(kt->t0, st);
+    }
+    ~Scope() { if (kt) hipEventRecord(kt->t1, st); }
+};
+
+static int launch_check(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("launch of %s failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+// The D == 30 instantiations of the register-resident kernels (D = 30: own instantiation, other D <= 32: capacity 32): each
+// family picks its function once, selection and launch share the choice.
+static auto game_fast_fn(int D) { return D == 30 ? k_game_fast<30> : k_game_fast<32>; }
+static auto bwd_sample_fn(int D) { return D == 30 ? k_bwd_sample<64, 100, 30> : k_bwd_sample<64, 100, 32>; }
+template <bool STATS, bool DC> static auto bwd_conv_fast_fn(int D) {
+    return D == 30 ? k_bwd_conv_fast<256, 32, 64, 100, 30, STATS, DC> : k_bwd_conv_fast<256, 32, 64, 100, 32, STATS, DC>;
+}
+
+static int launch_gemm_nt(mmg_handle* h, hipStream_t st, const char* name, const float* X, int ldx, const float* Wm, int ldw,
+                          const float* bias, float* out, int ldo, int M, int N, int K) {
+    Scope sc(h, st, name);
+    const int tiles = ((M + 15) / 16) * ((N + 15) / 16);
+    hipLaunchKernelGGL(k_gemm_nt, dim3(tiles), dim3(MMG_BLOCK), 0, st, X, ldx, Wm, ldw, bias, out, ldo, M, N, K);
+    return launch_check(name);
+}
+
+// x != NULL: also computes h_x = image_layer(x) in the same launch
+static int launch_prep(mmg_handle* h, hipStream_t st, const float* desc, const float* x, int bump_mb) {
+    Scope sc(h, st, x ? "k_prep+h_x" : "k_prep");
+    const int cpb = h->sel.prep_cpb;
+    hipLaunchKernelGGL(k_prep, dim3(prep_blocks(h->dm, cpb, x != nullptr)), dim3(MMG_BLOCK), h->sel.prep_smem, st, h->dm, h->P, h->tp, desc, x, cpb, bump_mb);
+    return launch_check("k_prep");
+}
+
+// k_wgrad over one job table.  live_rows: the (step, sample) jobs reduce over the live-row list (tape.rmap) instead of all rows.
+// stride > 0: that many resident workgroups walk the GEMM tiles.  closing: the spare block behind the tiles and column blocks
+// (logged losses, running totals, gradient tail); opt != NULL: k_wgrad<true>, the clip + optimizer step inside the launch.
+static int launch_wgrad(mmg_handle* h, hipStream_t st, const JobTable* djt, const WgHead& hd, const float* d_x, const float* d_desc,
+                        bool live_rows, int stride, bool closing, const WgOpt* opt) {
+    Scope sc(h, st, "k_wgrad");
+    WgOpt wo;
+    memset(&wo, 0, sizeof(wo));
+    if (opt) wo = *opt;
+    int grid = (stride > 0 ? stride - hd.gemm_tiles : 0) + hd.n_wblocks + (closing ? 1 : 0);
+    if (opt) grid = hd.n_wblocks + 1 + 4;                // tiles + column blocks | spare / closing block | four norm roles
+    hipLaunchKernelGGL(opt ? k_wgrad<true> : k_wgrad<false>, dim3(grid), dim3(MMG_BLOCK), 0, st,
+                       djt, d_x, d_desc, h->tp.gnpart, h->dm, (const double*)h->tp.stats, h->tp.losses, h->tp.totals,
+                       (const int*)(live_rows ? h->tp.rmap : nullptr), (const int*)(live_rows ? h->tp.rcount : nullptr), h->tp.wpart,
+                       reinterpret_cast<uint32_t*>(h->tp.wcnt), (const uint32_t*)h->tp.sync, h->grads + h->pl.total, wo, opt ? 0 : stride, hd
+#ifdef MMG_TIMING
+                       , h->tp.dbg2
+#endif
+                       );
+    return launch_check("k_wgrad");
+}
+
+// The weight gradients of a VJP: k_wgrad over job table `slot` of tape.vtables (0-3: exchange, 4-7: per call, agent = slot % 4) --
+// its tiles and column blocks only (no spare block: the logged losses, running totals and gradient tail stay untouched), no
+// live-row list.  Writes only the agent's slice of the gradient buffer.
+static int launch_vjp_wgrad(mmg_handle* h, hipStream_t st, int slot, const float* d_x, const float* d_desc) {
+    const JobTable* djt = reinterpret_cast<const JobTable*>(h->tp.vtables + (size_t)slot * MMG_VJP_TABLE_BYTES);
+    return launch_wgrad(h, st, djt, h->vjp_hd[slot], d_x, d_desc, false, 0, false, nullptr);
+}
+
+// The class side of the receiver's VJPs: k_vjp_cd forms Cd before the per-sample kernel, k_vjp_class reduces over it afterwards.
+static int launch_vjp_cd(mmg_handle* h, hipStream_t st, const float* d_desc) {
+    Scope sc(h, st, "k_vjp_cd");
+    hipLaunchKernelGGL(k_vjp_cd, dim3(h->dm.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, d_desc);
+    return launch_check("k_vjp_cd");
+}
+static int launch_vjp_class(mmg_handle* h, hipStream_t st, const VjpIn& in) {
+    Scope sc(h, st, "k_vjp_class");
+    hipLaunchKernelGGL(k_vjp_class, dim3(h->dm.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, in);
+    return launch_check("k_vjp_class");
+}
+
+// dynamic LDS of a VJP kernel in bytes; the kernels run under the default limit
+static int vjp_lds_ok(size_t smem, const char* who, const char* why) {
+    if (smem > 65536) return fail("the %s VJP needs %zu bytes of LDS%s", who, smem, why);
+    return 0;
+}

@@ -83,6 +83,7 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
 // ---------------------------------------------------------------------------------------------
 #define MMG_GN_BLOCKS 128      // blocks (= partial sums) of the gradient-norm kernel
 #define MMG_VJP_TABLE_BYTES 32768   // one job table of mmg_exchange_vjp (sizeof(JobTable), checked at mmg_create)
+#define MMG_TABLE_BYTES 98304       // the minibatch job table's slot, tape.tables below (static_assert in tape_layout; sizeof(JobTable): host_jobs.h)
 #define MMG_TAPE_LIST(X)                                                          \
     /* ---- forward ---- */                                                        \
     X(hx, float, 0, 2, B, H, 1)          /* image_layer(x)            model.py:195 */ \
@@ -302,6 +303,8 @@ struct TapeLayout {
     int64_t total;
 };
 
+constexpr bool tape_name_is(const char* a, const char* b) { return *a == *b && (*a == 0 || tape_name_is(a + 1, b + 1)); }
+
 inline TapeLayout tape_layout(const mmg_config& c) {
     TapeLayout L;
     L.n = 0;
@@ -340,6 +343,9 @@ inline TapeLayout tape_layout(const mmg_config& c) {
 #undef X
 #define X(name_, ctype, code, nd, d0, d1, d2) +1
     static_assert(0 MMG_TAPE_LIST(X) <= (int)(sizeof(L.e) / sizeof(L.e[0])), "TapeLayout::e is too small for MMG_TAPE_LIST");
+#undef X
+#define X(name_, ctype, code, nd, d0, d1, d2) && (!tape_name_is(#name_, "tables") || (d0) == MMG_TABLE_BYTES)
+    static_assert(true MMG_TAPE_LIST(X), "MMG_TABLE_BYTES is not the size of tape.tables in MMG_TAPE_LIST");
 #undef X
     L.total = o;
     return L;

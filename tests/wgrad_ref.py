@@ -1,4 +1,4 @@
-"""Float64 restatement of k_wgrad's job table (multimodalgame_amd/csrc/mmg.hip: build_jobs) for the GPU tests of
+"""Float64 restatement of k_wgrad's job table (multimodalgame_amd/csrc/host_jobs.h: build_jobs) for the GPU tests of
 tests/test_hip_wgrad.py.  Host only: numpy on arrays already fetched from the engine.
 
 Every parameter block's gradient is one job
@@ -27,7 +27,7 @@ def dims_of(cfg):
 
 
 def fast_shape(d):
-    """mmg.hip: fast_shape -- the register-resident kernels' agent shape (configs 1-3)."""
+    """host_select.h: fast_shape -- the register-resident kernels' agent shape (configs 1-3)."""
     return d["H"] == 256 and d["W"] == 32 and d["R"] == 64 and d["V"] == 100 and d["D"] <= 32 and d["T"] <= 16
 
 
@@ -78,7 +78,7 @@ class Job(object):
 def build_jobs(d, table, variant=None):
     """The jobs of build_jobs for dims `d` (dims_of) and the parameter table `table` (_lib.param_table), with the row-split
     plan (nsplit per GEMM job, bias columns as K = 1 GEMMs) k_wgrad takes.  variant: the code_bias job -- "fast" | "tile" |
-    "generic" (mmg.hip: the three branches of build_jobs; default: "fast" at fast_shape, else "tile")."""
+    "generic" (host_jobs.h: the three CodeBiasJob branches of build_jobs; default: "fast" at fast_shape, else "tile")."""
     B, T, H, W, R, V, K, D = (d[k] for k in "BTHWRVKD")
     TB = T * B
     ent = {(e["agent"], e["name"]): e for e in table}
@@ -167,7 +167,7 @@ def build_jobs(d, table, variant=None):
             col(agent, "linear1.bias", "tb", vop, virt=True)
             wsum(agent, "linear2.weight", "tb", (lambda env, beta=beta: env["tb"](beta)[:, 0]), tbv(hid))
             col(agent, "linear2.bias", "tb", tbv(beta))
-    # ---- row-split plan (mmg.hip: build_jobs' gemm lambda, bias_as_gemm, and mmg_create's wgrad_small_split retry)
+    # ---- row-split plan (host_jobs.h: JobBuilder::gemm, bias_as_gemm, and plan_jobs' choice of wgrad_small_split)
     nrows = {"tb": TB, "b": B, "d": D, "h": H}
 
     def plan(small_split):
