@@ -120,7 +120,9 @@ static int launch_check(const char* what) {
 // family picks its function once, selection and launch share the choice.
 static auto game_fast_fn(int D) { return D == 30 ? k_game_fast<30> : k_game_fast<32>; }
 static auto bwd_sample_fn(int D) { return D == 30 ? k_bwd_sample<64, 100, 30> : k_bwd_sample<64, 100, 32>; }
-template <bool STATS, bool DC> static auto bwd_conv_fast_fn(int D) {
+// V == 100 has its own instantiation as well; every other width runs the V = 0 one (layout.h: fast_wide_v)
+template <bool STATS, bool DC> static auto bwd_conv_fast_fn(int D, int V) {
+    if (V != 100) return k_bwd_conv_fast<256, 32, 64, 0, 32, STATS, DC>;
     return D == 30 ? k_bwd_conv_fast<256, 32, 64, 100, 30, STATS, DC> : k_bwd_conv_fast<256, 32, 64, 100, 32, STATS, DC>;
 }
 

@@ -24,7 +24,7 @@ inline int rc_roles_per_tile(const Dims& d) {
 static bool fast_shape(const mmg_handle* h) {
     const Dims& d = h->dm;
     if (h->sel.tile_ok && h->sel.tile_force) return false;
-    return h->sel.use_fast && d.H == 256 && d.W == 32 && d.R == 64 && d.V == 100 && d.D <= 32 && d.T <= 16;   // (D = 30: own instantiation, other D <= 32: capacity 32)
+    return h->sel.use_fast && d.H == 256 && d.W == 32 && d.R == 64 && (d.V == 100 || fast_wide_v(d.V)) && d.D <= 32 && d.T <= 16;   // (D = 30: own instantiation, other D <= 32: capacity 32; V = 100 likewise, other V % 4 == 0: at run time)
 }
 // every other shape: sample tiles on the matrix cores (kernels_tile.h); the per-sample generic kernels remain for
 // dimensions whose tile does not fit the LDS and for the agent-level entry points
@@ -114,7 +114,9 @@ static int select_paths(mmg_handle* h) {
         // 16-byte aligned weight rows (float4 fragments): every BASELINE shape; odd dimensions take the per-sample kernels
         const bool aligned = !(d.H & 3) && !(d.W & 3) && !(d.R & 3) && !(d.V & 3);
         s.rc_fwd = aligned && s.tile_ext && s.tile_smem > 160 * 1024 && rc_shape(d.B, d.H, d.W, d.R, d.V, d.D) && !getenv("MMG_NO_RC");
-        s.tile_ok = aligned && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !getenv("MMG_NO_TILE");
+        // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
+        //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
+        s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !getenv("MMG_NO_TILE");
         s.tile_force = getenv("MMG_TILE") != nullptr;
         // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
         // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -215,6 +217,10 @@ static int select_paths(mmg_handle* h) {
     }
     raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 100, false>), fast3_lds_bytes());
     raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 100, true>), fast3_lds_bytes());
+    if (fast_wide_v(d.V)) {
+        raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 0, false>), fast3_lds_bytes());
+        raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 0, true>), fast3_lds_bytes());
+    }
     {
         const bool shape = s.use_fast && s.merge_roles && s.sw_merge_prep && s.sw_merge_bas && d.H == 256 && d.W == 32 && d.R == 64 && d.V == 100 &&
                            d.D <= 32 && d.T <= 15 && d.B <= 64 && d.use_binary && !d.fixed && (d.K + 63) / 64 <= 8 && d.K <= 512 &&

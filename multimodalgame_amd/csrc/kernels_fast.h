@@ -19,7 +19,7 @@ namespace mmg {
 template <int H, int W, int R, int V, int D>
 struct FastDims {
     static constexpr int NT = 256;
-    static constexpr bool ok = (H == NT) && (W == 32) && (R == 64) && (V % 4 == 0) && (V <= NT) && (D <= 32) && (3 * R <= NT);
+    static constexpr bool ok = (H == NT) && (W == 32) && (R == 64) && (V == 0 || ((V % 4 == 0) && (V <= NT))) && (D <= 32)      /* V == 0: the run's width (dm.V) */  && (3 * R <= NT);
 };
 
 // Hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp): absolute error ~1e-7 on
@@ -80,28 +80,38 @@ namespace mmg {
 // kernel of kernels_fast3.h folds the description product onto the classes (Dd) and never forms dbar; only the weight-gradient job
 // of w_d reads it, so it is made HERE, by workgroups the backward launch carries along on idle CUs (nothing in this launch depends
 // on them; k_wgrad is the next launch).  Dead rows hold stale softmax rows (finite): their dgpre is zero / they are not in the row list.
+// V == 0: the description width of this run (dm.V, a multiple of 4 up to MMG_MAX_WV): a wave walks the 16-column tiles
+// wave, wave + 4, ... of the row block -- the class operand stays in registers, nothing V-wide lives in LDS.
 template <int V>
 __device__ __forceinline__ void dbar_role(const Dims& dm, const Tape& tp, int tile) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
-    const int rows = dm.T * dm.B, r0 = tile * 16, Dr = dm.D;
+    const int rows = dm.T * dm.B, r0 = tile * 16, Dr = dm.D, Vr = V ? V : dm.V;
     const float* prow = tp.pi + (size_t)min(r0 + i, rows - 1) * 32;
     float a[8];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) a[ks] = prow[4 * ks + q];
-    constexpr int NTILE = (V + 15) / 16;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int nt = wave + 4 * u;
-        if (nt >= NTILE) break;                                              // (wave-uniform)
+    auto col_tile = [&](int nt) {                                            // 16 rows x the columns 16 nt .. 16 nt + 15
         const int n = nt * 16 + i;
         float bv[8];
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) { const int d = 4 * ks + q; bv[ks] = (d < Dr && n < V) ? tp.descc[(size_t)min(d, Dr - 1) * V + min(n, V - 1)] : 0.f; }
+        for (int ks = 0; ks < 8; ++ks) { const int d = 4 * ks + q; bv[ks] = (d < Dr && n < Vr) ? tp.descc[(size_t)min(d, Dr - 1) * Vr + min(n, Vr - 1)] : 0.f; }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) acc = mfma16(a[ks], bv[ks], acc);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int row = r0 + 4 * q + r; if (row < rows && n < V) tp.dbar[(size_t)row * V + n] = acc[r]; }
+        for (int r = 0; r < 4; ++r) { const int row = r0 + 4 * q + r; if (row < rows && n < Vr) tp.dbar[(size_t)row * Vr + n] = acc[r]; }
+    };
+    if constexpr (V == 0) {
+        for (int nt = wave; nt * 16 < Vr; nt += 4) col_tile(nt);             // (wave-uniform trip count)
+    } else {
+        static_assert(V <= 128, "two column tiles per wave");
+        constexpr int NTILE = (V + 15) / 16;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int nt = wave + 4 * u;
+            if (nt >= NTILE) break;                                          // (wave-uniform)
+            col_tile(nt);
+        }
     }
 }
 
@@ -238,7 +248,7 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
     }
     float y1r[R / K4];                             // y1[:, :R] row k4 fragment (forward product A = y1h . h*)
 #pragma unroll
-    for (int i = 0; i < R / K4; ++i) y1r[i] = P.p[R_Y1_W][(size_t)k4 * (R + V) + p4 * (R / K4) + i];
+    for (int i = 0; i < R / K4; ++i) y1r[i] = P.p[R_Y1_W][(size_t)k4 * (R + (V ? V : dm.V)) + p4 * (R / K4) + i];      // (V == 0: the run's width, dbar_role)
     const float sm_mine = (tid < Dr) ? tp.sm[(size_t)b * Dr + tid] : 0.f;
     const float w2_mine = (tid < R) ? P.p[R_Y2_W][tid] : 0.f;
     float cdcol[D];                                // Cd[:, tid] for tid < R

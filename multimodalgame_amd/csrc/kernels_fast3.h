@@ -99,7 +99,10 @@ __host__ __device__ inline int fast3_lds_bytes() { return Fast3Lds::total * 4; }
 template <int H, int W, int R, int V, bool MERGED>
 __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P, Tape tp, ConvArgs ar) {
     constexpr int NT = 256, TMAX = Fast3Lds::TMAX;
-    static_assert(H == 256 && W == 32 && R == 64 && V % 4 == 0 && V <= 128, "lane maps of k_conversation_fast3");
+    static_assert(H == 256 && W == 32 && R == 64 && (V == 0 || (V % 4 == 0 && V <= 128)), "lane maps of k_conversation_fast3; V: a compile-time width, or 0 = the run's width (dm.V)");
+    // V == 0: the description width of this run (dm.V, any multiple of 4: layout.h fast_wide_v).  The recurrence reads Cd / Dd,
+    // which k_prep forms with a loop over V; V itself is only the row stride of y1.weight here.
+    const int ldy1 = R + (V ? V : dm.V);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // Roles of the launch, in workgroup order:
     //   [0, B)                one conversation per sample
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
     const int row4 = tid >> 1, half4 = tid & 1;
     float w4[32];
     {
-        const float* src = (row4 < R) ? P.p[R_Y1_W] + (size_t)row4 * (R + V) : P.p[R_WH_W] + (size_t)(row4 - R) * R;
+        const float* src = (row4 < R) ? P.p[R_Y1_W] + (size_t)row4 * ldy1 : P.p[R_WH_W] + (size_t)(row4 - R) * R;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float4 v = *reinterpret_cast<const float4*>(src + (j * 2 + half4) * 4);

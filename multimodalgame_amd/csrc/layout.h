@@ -245,6 +245,13 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
 // step: n, sum w, sum w^2, sum w*logp, sum negent; per baseline (0 = rec, 1 = sen) and step:
 // sum (beta-L)^2; then sum logs, hits.
 #define MMG_ST_PER 5
+
+// Description width (wv_dim): GloVe ships 50 / 100 / 200 / 300-d files; the generic kernels loop over V, the register-resident
+// small agents take V = 100 (own instantiation) and every other multiple of 4 at run time (fast_wide_v).
+#define MMG_MAX_WV 512
+// V of the register-resident kernels' run-time instantiation (template V = 0: strides and the dbar tiles read dm.V).  V lives
+// only in k_prep (Cd / Dd, a K-loop over V), in the y1 row stride and in the dbar roles of the backward launch.
+__host__ __device__ inline bool fast_wide_v(int V) { return V != 100 && V >= 4 && !(V & 3) && V <= MMG_MAX_WV; }
 __host__ __device__ inline int stat_stream(int T, int stream, int t, int k) { return (stream * T + t) * MMG_ST_PER + k; }
 __host__ __device__ inline int stat_bas(int T, int which, int t) { return 3 * T * MMG_ST_PER + which * T + t; }
 __host__ __device__ inline int stat_glob(int T, int k) { return 3 * T * MMG_ST_PER + 2 * T + k; }

@@ -122,7 +122,7 @@ static int validate(const mmg_config* c) {
     if (c->max_exchange > 64) return fail("max_exchange must be <= 64");
     if (c->w_dim > MMG_BLOCK || c->rec_hidden > MMG_BLOCK)
         return fail("w_dim and rec_hidden must be <= %d (got %d, %d)", MMG_BLOCK, c->w_dim, c->rec_hidden);
-    if (c->wv_dim > MMG_BLOCK) return fail("wv_dim must be <= %d", MMG_BLOCK);
+    if (c->wv_dim > MMG_MAX_WV) return fail("wv_dim must be <= %d (got %d)", MMG_MAX_WV, c->wv_dim);
     if (c->optim_type < 0 || c->optim_type > 2) return fail("unknown optim_type %d", c->optim_type);
     if (c->global_batch > 0 && c->global_batch < c->batch) return fail("global_batch < batch");
     return 0;
@@ -460,13 +460,15 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
             hipLaunchKernelGGL((k_conversation_mc<256, 32, 64, 100, 64>), dim3(grid), dim3(512), 0, st, h->dm, h->P, h->tp, ar, ntile, h->sel.mc_xcd, y_last_only);
         if (launch_check("k_conversation_mc")) return -1;
     } else {
-        Scope sc(h, st, "k_conversation");
-        const bool fast = fast_shape(h);
+        const bool fast = fast_shape(h), wide = fast && d.V != 100;
+        Scope sc(h, st, wide ? "k_conversation_wv" : "k_conversation");
         base_ready = fast && bas && !run_all_steps && h->sel.merge_roles;
         const int base_tiles = base_ready ? basehx_tiles(d) : 0;
         if (fast) {
             ar.nprep = merge_prep ? prep_blocks(d, h->sel.prep_cpb, true) : 0; ar.prep_cpb = h->sel.prep_cpb; ar.nbase = base_tiles;
-            if (merge_prep) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 100, true>), dim3(ar.nprep + d.B + base_tiles + 1), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
+            if (wide && merge_prep) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 0, true>), dim3(ar.nprep + d.B + base_tiles + 1), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
+            else if (wide) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 0, false>), dim3(d.B + base_tiles), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
+            else if (merge_prep) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 100, true>), dim3(ar.nprep + d.B + base_tiles + 1), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
             else hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 100, false>), dim3(d.B + base_tiles), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
         }
         else
@@ -631,8 +633,8 @@ static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_targe
         hipLaunchKernelGGL((k_bwd_mc2<64, 100>), dim3(d.B + nred + (with_stats ? 1 : 0)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ngroup, nred, with_stats ? 1 : 0);
         if (launch_check("k_bwd_mc")) return -1;
     } else {
-        Scope sc(h, st, "k_bwd_conv");
         const bool fast = fast_shape(h);
+        Scope sc(h, st, (fast && d.V != 100) ? "k_bwd_conv_wv" : "k_bwd_conv");
         const bool merge_dc = fast && h->sel.merge_roles;
         row_map = merge_dc && d.T * d.B <= 2048;         // class role 0 lists the live (step, sample) rows for k_wgrad
         // k_conversation_fast3 stores softmax rows, not dbar = softmax(y) . desc: trailing workgroups form it (16 rows each)
@@ -640,7 +642,7 @@ static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_targe
         if (fast) {      // (a 512-thread variant of this kernel measured slower: 31.8 vs 28.8 us -- it is not issue-bound)
             const int n_stats = with_stats ? stat_roles(d.T) : 0, n_bas = (with_stats && h->fwd.bas_deferred) ? bas_roles(d) : 0;
             const int n_class = (with_stats || merge_dc) ? d.D : 0;          // class roles (k_dC's work inside the launch)
-            const auto fn = with_stats ? bwd_conv_fast_fn<true, true>(d.D) : merge_dc ? bwd_conv_fast_fn<false, true>(d.D) : bwd_conv_fast_fn<false, false>(d.D);
+            const auto fn = with_stats ? bwd_conv_fast_fn<true, true>(d.D, d.V) : merge_dc ? bwd_conv_fast_fn<false, true>(d.D, d.V) : bwd_conv_fast_fn<false, false>(d.D, d.V);
             hipLaunchKernelGGL(fn, dim3(n_stats + d.B + n_class + n_dbar + n_bas), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, n_stats, row_map ? 0 : 1, n_dbar, n_bas);
         }
         else
