@@ -13,6 +13,8 @@
  *   mmg_clip_step          <- clip_grad_norm + optimizer    model.py:1310-1311, 1317-1318, 1323-1324, 1329-1330
  *   mmg_train_step         <- the whole per-minibatch block model.py:1240-1339 (single GPU)
  *   mmg_train_steps        <- n iterations of the epoch loop's body, model.py:1218-1240 (batches of misc.py:257-302)
+ *   mmg_eval_steps         <- n iterations of eval_dev's loop body: exchange(train = False) + the per-batch
+ *                             accuracy / confusion / length / Hamming arithmetic   model.py:620-691
  *   mmg_dp_train_step[s]   <- the same block on one rank of a data-parallel job (statistics + gradient
  *                             all-reduce; couplings model.py:912-915, 947-961, 1310)
  *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (non-attention, sender_mix=sum)
@@ -163,6 +165,37 @@ int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64_t* d_targe
  *     of running: the reference never corrupts a training conversation (model.py:1240).
  * Returns 0, or negative for n != w_dim or an entry other than 0 / 1 (the mask set before stays). */
 int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, int n);
+
+/* Dev evaluation inside the library (eval_dev's loop body, model.py:620-691): n consecutive evaluation conversations, each
+ * followed on the same stream by ONE reduction launch (k_eval_reduce) that leaves what the reference computes per dev batch
+ * on the host -- as integers, so the results do not depend on any summation order and are bit-reproducible.
+ *   d_x [n * B, F] f32, d_target [n * B] i64: batch i reads rows [i * B, (i + 1) * B), as mmg_train_steps lays them out.
+ *   Each conversation is mmg_exchange_forward(train = 0, run_all_steps = 1): rounded messages, no Philox draw, the minibatch
+ *   counter is not touched (a training call afterwards draws what it would have drawn without the evaluation); a mask set by
+ *   mmg_set_message_corruption applies.  The tape of the LAST batch stays valid (the dev sample dump reads it, model.py:1463-1518).
+ *   top_k: -top_k_dev (model.py:657-658).
+ * Step count of a batch (model.py:866): n_b = the first t + 1 with sum_b mask[t + 1, b] == 0, else T; Fixed mode: T.  Output step
+ * of a sample (model.py:870, 1261, 879-904): tsel[b] = #{t in 1..n_b - 1 : mask[t, b] = 1}; Fixed mode: T - 1.  With
+ * y = the class logits of that step: hit iff #{d : y[d] > y[target]} < min(top_k, D) (model.py:657-668: membership in the
+ * top_k of the log-softmax, which is monotone in y); prediction = argmax y, lowest index on ties (model.py:700).
+ *   d_acc: mmg_eval_acc_count() int64, ZEROED BY THE CALLER before the first batch of an evaluation and added to atomically:
+ *     [0] hits | [1] batches added | [2] samples added | [3] 0 |
+ *     [4, 4 + D * D) confusion counts conf[target * D + prediction] (model.py:709) |
+ *     [4 + D * D, 4 + D * D + D) seen[c] = times class c occurred as target or as prediction (sklearn's confusion_matrix keeps
+ *     the classes that occur).
+ *     Handles of different batch sizes (the short final dev batch) may share one accumulator.  A target outside [0, D) counts as
+ *     a sample only.
+ *   d_len [n * B] i32, written: conversation length sum_{t < n_b} s[t, b] of every sample, in dataset order (model.py:671-672).
+ *   d_batch [n, 1 + 2 T] i64, written, per batch: [0] n_b | [1 + t] ham_sen[t] = sum_b sum_j |z[t, b, j] - z[t - 1, b, j]| with
+ *     z[-1] = 0 | [1 + T + t] ham_rec[t], the same over the receiver's messages w -- for EVERY t < T; the reference's statistic of
+ *     the batch is sum_{t < n_b} ham[t] / (B n_b) (model.py:675-691), formed by the caller in float64.  Binary messages: int64
+ *     counts.  Continuous messages (use_binary == 0): the int64 slot holds the bits of the float64 sum, reduced in a fixed
+ *     order by the one workgroup that owns the slot (per-thread partial sums in index order, a fixed tree over the workgroup;
+ *     there is one slot per batch and step, so no second pass over slots): bit-identical from run to run.
+ * No host synchronisation; returns 0, or negative for a NULL pointer, top_k < 1 or n < 0. */
+int64_t mmg_eval_acc_count(const mmg_config* cfg);
+int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                   int64_t* d_acc, int32_t* d_len, int64_t* d_batch, void* stream);
 
 /* Per-rank partial sums of every batch statistic the losses need (counts, sums and squared sums
  * of reward-minus-baseline per stream and step, ...) into the f64 tape array "stats".  With more

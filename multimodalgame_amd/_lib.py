@@ -47,7 +47,10 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_baseline_forward", "mmg_set_profiling", "mmg_get_kernel_times", "mmg_host_shuffle", "mmg_train_steps",
            "mmg_dp_set_allreduce", "mmg_dp_train_step", "mmg_dp_train_steps", "mmg_clear_error", "mmg_degraded",
            "mmg_log_snapshot_count", "mmg_log_snapshot", "mmg_set_message_corruption", "mmg_exchange_vjp",
-           "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp"]
+           "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps"]
+
+# the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
+EVAL_ACC_HEAD = 4
 
 
 def load():
@@ -77,6 +80,8 @@ def load():
     lib.mmg_clip_step.restype = i32; lib.mmg_clip_step.argtypes = [vp, vp]
     lib.mmg_train_step.restype = i32; lib.mmg_train_step.argtypes = [vp, fp, vp, fp, fp, fp, fp, u64, vp]
     lib.mmg_train_steps.restype = i32; lib.mmg_train_steps.argtypes = [vp, fp, vp, i64, fp, u64, vp]
+    lib.mmg_eval_acc_count.restype = i64; lib.mmg_eval_acc_count.argtypes = [cfgp]
+    lib.mmg_eval_steps.restype = i32; lib.mmg_eval_steps.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp]
     lib.mmg_set_message_corruption.restype = i32; lib.mmg_set_message_corruption.argtypes = [vp, vp, i32]
     lib.mmg_exchange_vjp.restype = i32; lib.mmg_exchange_vjp.argtypes = [vp, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_sender_vjp.restype = i32; lib.mmg_sender_vjp.argtypes = [vp, fp, fp, i32, fp, fp, fp, fp, fp, fp, vp]

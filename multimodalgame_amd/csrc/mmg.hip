@@ -23,6 +23,7 @@
 #include "kernels_mc3p.h"
 #include "kernels_rc.h"
 #include "kernels_vjp.h"
+#include "kernels_eval.h"
 #ifdef MMG_ROLE_DIAG
 #include "diag_kernels.h"
 #endif
@@ -528,6 +529,37 @@ extern "C" int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64
     if (!train) return fwd(0);
     if (begin_minibatch(h, "mmg_exchange_forward(train = 1)")) return -1;
     return run_minibatches(h, 1, stream, fwd);             // a training forward pass starts a minibatch
+}
+
+// ---------------------------------------------------------------------------------------------
+// mmg_eval_steps: n consecutive dev batches of eval_dev (model.py:620-691) enqueued by ONE call -- the eval-mode conversation
+// (train = 0, run-all: no Philox draw, the minibatch counter stays) and behind each one k_eval_reduce (kernels_eval.h), which
+// adds the batch's hits / confusion matrix / classes seen to the caller's accumulator and writes its conversation lengths,
+// step count and Hamming counts.  Not a minibatch start: no error gate, and nothing here waits inside a launch.
+// ---------------------------------------------------------------------------------------------
+extern "C" int64_t mmg_eval_acc_count(const mmg_config* cfg) {
+    if (validate(cfg)) return -1;
+    return eval_acc_count(cfg->n_classes);
+}
+
+extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                              int64_t* d_acc, int32_t* d_len, int64_t* d_batch, void* stream) {
+    if (!h) return fail("NULL handle");
+    if (!d_x || !d_target || !d_desc || !d_acc || !d_len || !d_batch) return fail("mmg_eval_steps: x / target / desc / acc / len / batch must not be NULL");
+    if (top_k < 1) return fail("mmg_eval_steps: top_k must be >= 1 (got %d)", top_k);
+    if (n < 0) return fail("mmg_eval_steps: n must be >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    const Dims& d = h->dm;
+    const int nsb = eval_sample_blocks(d.B);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t* tgt = d_target + (size_t)i * d.B;
+        if (exchange_forward_impl(h, d_x + (size_t)i * d.B * d.F, tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, 1, stream)) return -1;
+        Scope sc(h, st, "k_eval_reduce");
+        hipLaunchKernelGGL(k_eval_reduce, dim3(nsb + 2 * d.T), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_acc,
+                           d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
+        if (launch_check("k_eval_reduce")) return -1;
+    }
+    return 0;
 }
 
 // The evaluation mask of -bit_flip (include/mmg.h): host state only; exchange_forward_impl copies it into the launch arguments.

@@ -183,6 +183,40 @@ class Engine(object):
         _lib.check(self.lib.mmg_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                             self._ptr(desc, torch.float32), C.c_uint64(seed), self._stream()))
 
+    def eval_acc(self):
+        """A zeroed accumulator for eval_steps (include/mmg.h: mmg_eval_acc_count int64 -- hits, batches, samples, 0, the
+        [D, D] confusion counts, the [D] classes seen).  Engines of the same class count may share one."""
+        n = int(self.lib.mmg_eval_acc_count(C.byref(self.cfg)))
+        if n < 0:
+            raise _lib.MmgError(self.lib.mmg_last_error().decode())
+        return torch.zeros(n, dtype=torch.int64, device=self.device)
+
+    def eval_steps(self, x, target, desc, n, top_k, acc, lens=None, batch=None, corrupt_mask=None):
+        """n consecutive evaluation conversations (x [n * B, F], target [n * B]), each followed by the library's reduction launch
+        (include/mmg.h: mmg_eval_steps): hits / confusion counts / classes seen are ADDED to `acc` (eval_acc()); returns
+        (lens [n * B] int32: conversation lengths, batch [n, 1 + 2 T] int64: executed steps | Hamming counts of the sender's
+        and of the receiver's messages per step -- float64 bits with continuous messages).  No host synchronisation; the
+        minibatch counter is untouched; the tape holds the last batch.  corrupt_mask: as forward()."""
+        B, T = self.cfg.batch, self.cfg.max_exchange
+        assert x.size(0) >= n * B and target.size(0) >= n * B
+        assert acc.dtype == torch.int64 and acc.numel() == _lib.EVAL_ACC_HEAD + self.cfg.n_classes * (self.cfg.n_classes + 1)
+        if lens is None:
+            lens = torch.empty(n * B, dtype=torch.int32, device=self.device)
+        if batch is None:
+            batch = torch.empty(n, 1 + 2 * T, dtype=torch.int64, device=self.device)
+        assert lens.numel() >= n * B and batch.numel() >= n * (1 + 2 * T)
+        self.generation += 1
+        if corrupt_mask is not None:
+            self.set_message_corruption(corrupt_mask)
+        try:
+            _lib.check(self.lib.mmg_eval_steps(
+                self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n), self._ptr(desc, torch.float32),
+                int(top_k), self._ptr(acc, torch.int64), self._ptr(lens, torch.int32), self._ptr(batch, torch.int64), self._stream()))
+        finally:
+            if corrupt_mask is not None:
+                self.set_message_corruption(None)
+        return lens, batch
+
     def set_allreduce(self, fn_address, comm):
         """RCCL's ncclAllReduce by address + a communicator: the data-parallel step then runs inside ONE C call (dp_train_step)."""
         _lib.check(self.lib.mmg_dp_set_allreduce(self.handle, C.c_void_p(fn_address), comm))

@@ -1,8 +1,10 @@
 """exchange() and the per-minibatch training block of the reference (model.py:725-876, 1240-1339)
 on top of the HIP engine, with the reference's calling conventions and return structures."""
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from . import flags as _flags
 from . import misc
 from .engine import Engine
@@ -138,6 +140,51 @@ class FlatOptimizer(object):
         if step:
             for e in self.game.engines.values():
                 e.tape["counter"][1:3] = step
+
+
+class EvalAccumulator(object):
+    """What one dev evaluation adds up ON THE DEVICE (Game.eval_steps; include/mmg.h: mmg_eval_steps): the library's int64
+    accumulator -- hits, the [D, D] confusion counts, the classes seen -- shared by the engines of every batch size, and per
+    call the conversation lengths and the per-batch step count / Hamming counts.  fetch() copies everything to the host ONCE."""
+
+    def __init__(self, n_classes, top_k):
+        self.n_classes, self.top_k = int(n_classes), int(top_k)
+        self.acc = None                                # created by the first engine that adds to it
+        self.parts = []                                # (B, n, T, binary, lens [n * B] i32, batch [n, 1 + 2 T] i64)
+
+    def add(self, eng, data, target, desc, n, corrupt_mask=None):
+        if self.acc is None:
+            self.acc = eng.eval_acc()
+        lens, batch = eng.eval_steps(data, target, desc, n, self.top_k, self.acc, corrupt_mask=corrupt_mask)
+        self.parts.append((eng.cfg.batch, int(n), eng.cfg.max_exchange, bool(eng.cfg.use_binary), lens, batch))
+
+    def fetch(self):
+        """dict(hits, batches, samples, conf [D, D], seen [D], lens [samples] int64 in dataset order, n [batches],
+        sizes [batches], ham_sen / ham_rec [batches] float64 = sum_{t < n} ham[t] / (B n): the reference's per-batch mean
+        Hamming distance, model.py:675-691) -- one device -> host copy."""
+        D = self.n_classes
+        if self.acc is None:
+            z = np.zeros(0)
+            return dict(hits=0, batches=0, samples=0, conf=np.zeros((D, D), np.int64), seen=np.zeros(D, np.int64),
+                        lens=np.zeros(0, np.int64), n=np.zeros(0, np.int64), sizes=np.zeros(0, np.int64), ham_sen=z, ham_rec=z)
+        lens = torch.cat([p[4] for p in self.parts]).to(torch.int64)           # (one conversion for all batches, not one per batch)
+        flat = torch.cat([self.acc] + [p[5].reshape(-1) for p in self.parts] + [lens]).cpu().numpy()
+        H = _lib.EVAL_ACC_HEAD
+        out = dict(hits=int(flat[0]), batches=int(flat[1]), samples=int(flat[2]), conf=flat[H:H + D * D].reshape(D, D),
+                   seen=flat[H + D * D:H + D * D + D])
+        o = H + D * D + D
+        ns, sizes, hs, hr = [], [], [], []
+        for B, n, T, binary, _, _ in self.parts:
+            rows = flat[o:o + n * (1 + 2 * T)].reshape(n, 1 + 2 * T); o += n * (1 + 2 * T)
+            ham = rows[:, 1:] if binary else np.ascontiguousarray(rows[:, 1:]).view(np.float64)
+            for i in range(n):
+                k = int(rows[i, 0])
+                ns.append(k); sizes.append(B)
+                hs.append(float(ham[i, :k].astype(np.float64).sum()) / (float(B) * k))
+                hr.append(float(ham[i, T:T + k].astype(np.float64).sum()) / (float(B) * k))
+        out.update(lens=flat[o:], n=np.asarray(ns, np.int64), sizes=np.asarray(sizes, np.int64),
+                   ham_sen=np.asarray(hs, np.float64), ham_rec=np.asarray(hr, np.float64))
+        return out
 
 
 class Game(object):
@@ -319,16 +366,41 @@ class Game(object):
         for k in ("sender", "receiver"):
             if self.modules.get(k) is not None:
                 self.modules[k].train(False)
-        B = data.size(0)
+        n, acc = getattr(self, "_eval_into", None) or (1, None)       # (eval_steps: n conversations, each reduced into acc)
+        B = data.size(0) // n
         eng = self.engine_for(B, desc.size(0))
         dev = eng.device
-        data = data.to(dev, torch.float32).contiguous().view(B, -1)
+        data = data.to(dev, torch.float32).contiguous().view(n * B, -1)
         desc = desc.to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
         self._call += 1
+        if acc is not None:
+            acc.add(eng, data, target, desc, n, corrupt_mask=corrupt_mask)
+            return eng
         eng.forward(data, target, desc, seed=self.seed, train=False, run_all=True,
                     **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         return eng
+
+    def eval_accumulator(self, n_classes, top_k):
+        return EvalAccumulator(n_classes, top_k)
+
+    def eval_steps(self, data, target, desc, n, acc, corrupt_mask=None):
+        """n consecutive dev batches (data [n * B, F], target [n * B], as train_steps lays them out) evaluated by ONE library
+        call (include/mmg.h: mmg_eval_steps): each conversation of eval_forward() is followed by the library's reduction launch,
+        which adds the batch's top-k hits, confusion counts and classes seen to `acc` (eval_accumulator(); the calls of one
+        evaluation share it, whatever their batch size) and writes its conversation lengths, step count and Hamming counts
+        (model.py:640-691).  No host synchronisation; acc.fetch() copies the results once.  Returns the engine, whose tape
+        holds the last batch.  The conversations go through eval_forward(), the one place an evaluation conversation is
+        enqueued: whatever wraps it (a corruption mask handed in by a caller) sees these too."""
+        if n < 1:
+            raise ValueError("eval_steps: n must be >= 1")
+        if target is None:
+            raise ValueError("eval_steps: the reductions need the targets")
+        self._eval_into = (int(n), acc)
+        try:
+            return self.eval_forward(data, target, desc, corrupt_mask=corrupt_mask)
+        finally:
+            self._eval_into = None
 
     # ------------------------------------------------------------------ model.py:1240-1339
     def train_step(self, data, target, desc, uniforms=None, full_tape=False):

@@ -87,14 +87,20 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     """model.py:580-722 ON THE DEVICE: deterministic conversations on the dev set, top-k accuracy (nominal batch size in the
     denominator, line 667), confusion matrix, conversation length and Hamming statistics.
 
-    One pass per dev batch with NO host synchronisation: the eval-mode conversation (Game.eval_forward: one launch, all T
-    steps of every sample) leaves masks / stop bits / messages / class logits on the engine's tape, and everything the
-    reference then does on the host per batch -- the early-break step count n (model.py:866), output selection
-    (get_rec_outp, 879-904), log-softmax, top-k membership (657-668), argmax, conversation lengths (671-672), the per-step
-    mean Hamming distance of both agents' messages averaged over the n executed steps (675-691) -- is a handful of torch ops
-    enqueued on the device: the tape slices of every batch are stacked (five device copies per batch) and the arithmetic runs
-    ONCE per batch size over all batches together (hit count, a [D, D] confusion matrix by index_add_, the conversation
-    lengths, the two Hamming means); the results are copied to the host ONCE.
+    One pass over the dev batches with NO host synchronisation, results copied to the host ONCE.  Two forms:
+
+    * the library's (engines with eval_steps, i.e. the HIP engine): ONE call per dev batch (Game.eval_steps; include/mmg.h:
+      mmg_eval_steps) enqueues the eval-mode conversation and, behind it, one reduction launch (csrc/kernels_eval.h) that does
+      what the reference does on the host per batch -- the early-break step count n (model.py:866), output selection
+      (get_rec_outp, 879-904), top-k membership (657-668), argmax, conversation lengths (671-672), the Hamming counts of both
+      agents' messages (675-691) -- in integers: hits, confusion counts and classes seen go into one accumulator that the
+      engines of all batch sizes share (the short final batch has its own engine), lengths and per-step counts are written
+      per batch.  No tape copies, no torch ops.
+    * the torch form (an engine stand-in without eval_steps: tests/oracle_engine.py; MMG_EVAL_TORCH=1 for cross-checks):
+      Game.eval_forward per batch, five tape slices per batch copied into stacks, _eval_reduce over the stacks.
+
+    The host arithmetic is the same for both: nominal batch size in the denominator (model.py:667), sklearn's confusion matrix
+    over the classes that occur, numpy mean / std of the lengths, mean over the batches of the per-batch Hamming means.
     (Round 4 transcribed the host loop literally: numpy argsort per batch and ~20 float() syncs per batch.)
 
     dump: optional dict that receives the last batch's engine (the dev sample dump of model.py:1463-1518 reads its tape).
@@ -104,11 +110,12 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     corrupt_mask = corrupt_mask_from_flags()
     n_cls = desc.size(0)
     T = game.max_exchange
-    # ---- pass 1: one eval-mode launch per batch; what the statistics need of its tape is copied into per-batch-size stacks
-    # (five device copies per batch, no host synchronisation, no per-batch reduction kernels)
-    groups = {}                                        # batch size -> dict of lists
     total = 0.0
     eng = None
+    dacc = None                                        # library form: Game.eval_steps adds every batch to it
+    # torch form, pass 1: what the statistics need of a batch's tape is copied into per-batch-size stacks (five device copies
+    # per batch, no per-batch reduction kernels)
+    groups = {}                                        # batch size -> dict of lists
     acc = dict(correct=None, conf_flat=None, seen=None)
     conv_lens, ham_sen, ham_rec = [], [], []
     pending = 0
@@ -116,28 +123,38 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
                            feats=(FLAGS.img_feat,), device=device):
         target, data = batch["target"], batch[FLAGS.img_feat]
         _bs = target.size(0)
+        total += float(batch_size)                                           # model.py:667: the NOMINAL batch size
+        if eng is None and hasattr(game.engine_for(_bs, n_cls), "eval_steps") and not os.environ.get("MMG_EVAL_TORCH"):
+            dacc = game.eval_accumulator(n_cls, top_k)
+        if dacc is not None:
+            eng = game.eval_steps(data, target, desc, 1, dacc, corrupt_mask=corrupt_mask)
+            continue
         eng = game.eval_forward(data, target, desc, corrupt_mask=corrupt_mask)
         tp = eng.tape
         g = groups.setdefault(_bs, dict(mask=[], s=[], z=[], w=[], y=[], target=[]))
         g["mask"].append(tp["mask"].view(T + 1, _bs).clone()); g["s"].append(tp["s"].view(T, _bs).clone())
         g["z"].append(tp["z"].view(T, _bs, W).clone()); g["w"].append(tp["w"].view(T, _bs, W).clone())
         g["y"].append(tp["y"].view(T, _bs, -1).clone()); g["target"].append(target.view(-1))
-        total += float(batch_size)                                           # model.py:667: the NOMINAL batch size
         pending += 1
         if pending >= EVAL_FLUSH_BATCHES:              # bound the stacked tape copies (a 1000-class dev set of 50k samples would hold GBs)
             _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
             groups, pending = {}, 0
-    _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
-    correct, conf_flat, seen = acc["correct"], acc["conf_flat"], acc["seen"]
     # ---- ONE copy to the host
-    correct_h = int(correct.item()) if correct is not None else 0
-    conf_full = conf_flat.view(n_cls, n_cls).cpu().numpy() if conf_flat is not None else np.zeros((n_cls, n_cls), np.int64)
-    occ = np.nonzero(seen.cpu().numpy() > 0)[0] if seen is not None else np.zeros(0, np.int64)
+    if dacc is not None:
+        r = dacc.fetch()
+        correct_h, conf_full, occ = r["hits"], r["conf"], np.nonzero(r["seen"] > 0)[0]
+        cl, hs, hr = r["lens"].astype(np.float64), r["ham_sen"], r["ham_rec"]
+    else:
+        _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
+        correct, conf_flat, seen = acc["correct"], acc["conf_flat"], acc["seen"]
+        correct_h = int(correct.item()) if correct is not None else 0
+        conf_full = conf_flat.view(n_cls, n_cls).cpu().numpy() if conf_flat is not None else np.zeros((n_cls, n_cls), np.int64)
+        occ = np.nonzero(seen.cpu().numpy() > 0)[0] if seen is not None else np.zeros(0, np.int64)
+        cl = torch.cat(conv_lens).cpu().numpy().astype(np.float64) if conv_lens else np.zeros(0)
+        hs = torch.cat(ham_sen).cpu().numpy().astype(np.float64) if ham_sen else np.zeros(0)
+        hr = torch.cat(ham_rec).cpu().numpy().astype(np.float64) if ham_rec else np.zeros(0)
     # sklearn.metrics.confusion_matrix (model.py:709): rows / columns = the SORTED CLASSES THAT OCCUR in truth or prediction
     np.savetxt(conf_mat_path, conf_full[np.ix_(occ, occ)], delimiter=",", fmt="%d")
-    cl = torch.cat(conv_lens).cpu().numpy().astype(np.float64) if conv_lens else np.zeros(0)
-    hs = torch.cat(ham_sen).cpu().numpy().astype(np.float64) if ham_sen else np.zeros(0)
-    hr = torch.cat(ham_rec).cpu().numpy().astype(np.float64) if ham_rec else np.zeros(0)
     extra = dict(conversation_lengths_mean=cl.mean(), conversation_lengths_std=cl.std(),
                  hamming_sen_mean=hs.mean(), hamming_rec_mean=hr.mean())
     if dump is not None:
