@@ -108,8 +108,19 @@ def _relu_flips(res, y1_out, bas_out, n_classes, binary=True, fixed=False):
 _FORCE_TINY = 1e-30       # a forced unit's pre-activation: +tiny (mask on, value ~0) / -tiny (mask off)
 
 
-def oracle_train_case(name, meta, flips=None, force=None, params_before=None, y2_bias=None):
+def apply_tweak(models, filled, tweak):
+    """tweak(state_dicts): edits the four agents' seeded state dicts ({agent: {key: float32 ndarray}}, what load_filled /
+    fill_state_dicts return) IN PLACE, before the first minibatch; the oracle's modules are then re-loaded from the edited
+    arrays.  The engine side (make_engine) hands the same function the same arrays, so both sides start from identical bits."""
+    tweak(filled)
+    for a, m in models.items():
+        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in filled[a].items()})
+
+
+def oracle_train_case(name, meta, flips=None, force=None, params_before=None, y2_bias=None, tweak=None):
     """Re-run a golden train case with the CPU oracle; returns the packed dict.
+    tweak: see apply_tweak (None: the seeded weights as they are).  It is recorded with the flips, so that assert_parity's
+    forced re-run starts from the same weights.
     y2_bias: per minibatch, the value the receiver's y2.bias is set to after that minibatch's update (the reference's own: its
     exact gradient is 0 and the update it takes is rounding noise that differs from CPU to CPU, see compare_packed; every
     other quantity of the later minibatches is then compared against the reference at full strictness).
@@ -123,7 +134,9 @@ def oracle_train_case(name, meta, flips=None, force=None, params_before=None, y2
     torch.manual_seed(0)
     tape = cpu_ref.UniformTape()
     models = cpu_ref.build_agents(fl, rng=tape)
-    cpu_ref.load_filled(models, seed=meta["seed_weights"])
+    filled = cpu_ref.load_filled(models, seed=meta["seed_weights"])
+    if tweak is not None:
+        apply_tweak(models, filled, tweak)
     optimizers = cpu_ref.build_optimizers(models, fl)
     out = {}
     y1_out, bas_out = [], {"bas_rec": [], "bas_sen": []}
@@ -164,6 +177,7 @@ def oracle_train_case(name, meta, flips=None, force=None, params_before=None, y2
         if flips is not None:
             f = _relu_flips(res, y1_out, bas_out, meta["n_classes"], binary=bool(fl.use_binary), fixed=bool(fl.fixed_exchange))
             f["case"] = (name, meta)
+            f["tweak"] = tweak
             flips.append(f)
         out.update(cpu_ref.pack_train(res, models, prefix="mb%d." % i))
     for h in hooks:
@@ -171,7 +185,10 @@ def oracle_train_case(name, meta, flips=None, force=None, params_before=None, y2
     return out
 
 
-def oracle_losses_f64(name, meta, want, params_oracle, params_gpu):
+F64_EXTRA = ("logs", "dist", "outp", "y")      # forward quantities oracle_losses_f64 can gate beside the six losses
+
+
+def oracle_losses_f64(name, meta, want, params_oracle, params_gpu, tweak=None, extra=()):
     """The float64 gate of the six losses (shapes whose losses are far above fp32's absolute resolution: config 4's means of
     256-bit log-likelihood sums times a reward weight, |loss| ~ 600, one fp32 ulp = 6e-5).  For every minibatch i the oracle's
     loss computation is re-run in FLOAT64 on the DISCRETE trajectory of the fp32 run (`want`: its sampled bits are injected as
@@ -181,8 +198,20 @@ def oracle_losses_f64(name, meta, want, params_oracle, params_gpu):
     {"mb<i>.losses": (exact at the GPU's parameters, exact at the oracle's parameters)}; compare_packed gates
         |GPU - exact(GPU params)| <= |fp32 oracle - exact(oracle params)| + 1e-4
     i.e. each implementation against the exact value of ITS OWN forward pass: "at least as close to exact as the reference's
-    fp32 arithmetic, plus north_star's 1e-4" (replaces round 4's 16-ulp allow-list)."""
+    fp32 arithmetic, plus north_star's 1e-4" (replaces round 4's 16-ulp allow-list).
+    tweak: the weight edit of the case (apply_tweak).  Both parameter snapshots were taken AFTER it, so nothing is left to
+    apply here; the argument keeps the call sites of a tweaked case uniform and is checked against the snapshot.
+    extra: names out of F64_EXTRA (cases whose logits are scaled up, e.g. y2.weight x 8: |y| ~ 10^1, where 1e-4 absolute is a
+    few fp32 ulps of a 64-term sum) -- "mb<i>.<name>" entries are returned and gated the same way."""
     fl = flags_from_meta(meta)
+    assert all(e in F64_EXTRA for e in extra), extra
+    if tweak is not None:                       # the snapshot the oracle started from already holds the edited weights
+        shapes = {a: {k: tuple(v.shape) for k, v in d.items()} for a, d in params_oracle[0].items()}
+        filled = cpu_ref.fill_state_dicts(shapes, seed=meta["seed_weights"])
+        tweak(filled)
+        for a, d in filled.items():
+            for k, v in d.items():
+                assert np.array_equal(np.asarray(params_oracle[0][a][k]), v), "snapshot without the tweak: %s.%s" % (a, k)
     old = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)
     keys6 = ("nll_loss", "loss_binary_s", "loss_binary_rec", "loss_binary_sen", "loss_bas_rec", "loss_bas_sen")
@@ -209,8 +238,11 @@ def oracle_losses_f64(name, meta, want, params_oracle, params_gpu):
                 res = cpu_ref.train_minibatch(models, optimizers, torch.from_numpy(x).double(), torch.from_numpy(target),
                                               torch.from_numpy(desc).double(), fl, update=False)
                 assert int(res["n_steps"]) == int(want["mb%d.n_steps" % i]), "the float64 re-run left the fp32 run's trajectory"
-                both.append(np.array([float(res[k].detach()) for k in keys6], np.float64))
-            out["mb%d.losses" % i] = (both[0], both[-1])
+                both.append(dict(losses=np.array([float(res[k].detach()) for k in keys6], np.float64),
+                                 **{e: (np.stack([t.detach().numpy() for t in res[e]]) if e == "y" else res[e].detach().numpy()).astype(np.float64)
+                                    for e in extra}))
+            for e in ("losses",) + tuple(extra):
+                out["mb%d.%s" % (i, e)] = (both[0][e], both[-1][e])
         return out
     finally:
         torch.set_default_dtype(old)
@@ -258,14 +290,14 @@ def sampling_margin(packed, meta, name=None):
     return m
 
 
-def separate_draws(name, meta, margin=1e-4):
+def separate_draws(name, meta, margin=1e-4, tweak=None):
     """Registers uniforms for the case `name` in which no Bernoulli draw lies within `margin` of its probability: the oracle
     runs once on the seeded uniforms, every u with |u - p| < margin is moved to p -/+ margin on the side it was on (the
     sampled bit, hence the whole trajectory and every later p, is unchanged), and the adjusted arrays become the case's
     inputs (U_OVERRIDES).  With ~10^5 draws per minibatch some draw always sits within 1e-6 of p, where two correct fp32
     implementations toss a coin; this removes the coin, not the comparison."""
     U_OVERRIDES.pop(name, None)
-    packed = oracle_train_case(name, meta)
+    packed = oracle_train_case(name, meta, tweak=tweak)
     adjusted = []
     for i in range(meta["n_minibatches"]):
         _, _, _, us = case_inputs(meta, i, None)
@@ -344,7 +376,8 @@ def compare_packed(got, want, atol=1e-5, rtol=1e-4, skip=(), only_prefix=None, s
             continue
         tail = k.split(".")[-1]
         # (minibatch 0 has seen no update: y2.bias is the initial one on both sides and the RAW logits must agree)
-        if shift_invariant and tail in SHIFT_INVARIANT and a.size and not k.startswith("mb0."):
+        shifted = shift_invariant and tail in SHIFT_INVARIANT and a.size and not k.startswith("mb0.")
+        if shifted:
             a = a - a.mean(-1, keepdims=True)
             b = b - b.mean(-1, keepdims=True)
         is_bits = b.size == 0 or bool(np.all((b == 0) | (b == 1))) or tail in ("n_steps", "hits")
@@ -359,6 +392,8 @@ def compare_packed(got, want, atol=1e-5, rtol=1e-4, skip=(), only_prefix=None, s
             elif gate64:
                 ex_got, ex_want = [np.asarray(v, np.float64).reshape(b.shape) for v in
                                    (f64[k] if isinstance(f64[k], tuple) else (f64[k], f64[k]))]
+                if shifted:
+                    ex_got, ex_want = ex_got - ex_got.mean(-1, keepdims=True), ex_want - ex_want.mean(-1, keepdims=True)
                 err = np.abs(a.astype(np.float64) - ex_got)          # each side against the exact value of ITS OWN forward pass
                 tol = np.abs(b.astype(np.float64) - ex_want) + min(atol, FORWARD_ATOL)
             else:
@@ -422,7 +457,7 @@ def assert_parity(got, want, flips, eng, label, skip=(), atol=1e-4, rtol=1e-3, m
             break                                         # no near-threshold unit sits on the other side on the GPU
         force = new_force
         cur_flips = []
-        want2 = oracle_train_case(name, meta, flips=cur_flips, force=force)
+        want2 = oracle_train_case(name, meta, flips=cur_flips, force=force, tweak=flips[0].get("tweak"))
         want2 = {k: want2[k] for k in (want.keys() if hasattr(want, "keys") else want.files) if k in want2}
         left = compare_packed(got, want2, atol=atol, rtol=rtol, skip=skip, shift_invariant=True,
                               label=(label + "/forced") if label else None, f64=f64)
@@ -474,11 +509,15 @@ def engine_kwargs(meta, batch=None, **over):
     return kw
 
 
-def make_engine(meta, **over):
+def make_engine(meta, tweak=None, **over):
+    """tweak: see apply_tweak -- the same in-place edit of the seeded state dicts the oracle side gets."""
     from multimodalgame_amd.engine import Engine
     eng = Engine(**engine_kwargs(meta, **over))
     shapes = {a: {k: tuple(v.shape) for k, v in d.items()} for a, d in eng.params.items()}
-    eng.load_state_dicts(cpu_ref.fill_state_dicts(shapes, seed=meta["seed_weights"]))
+    filled = cpu_ref.fill_state_dicts(shapes, seed=meta["seed_weights"])
+    if tweak is not None:
+        tweak(filled)
+    eng.load_state_dicts(filled)
     return eng
 
 
@@ -504,12 +543,12 @@ def engine_result(eng, fl):
     return res
 
 
-def hip_train_case(name, meta, early_exit=False, fused=False, log_tape=False, dp_full_tape=False):
+def hip_train_case(name, meta, early_exit=False, fused=False, log_tape=False, dp_full_tape=False, tweak=None):
     """Run a golden train case on the GPU through the C-ABI; returns (packed dict, engine).
     log_tape: phased log minibatches (run_all_steps == 3, Game.train_step(full_tape=True)); dp_full_tape: the same through
-    one mmg_dp_train_step(full_tape=1, reduce=0) call."""
+    one mmg_dp_train_step(full_tape=1, reduce=0) call; tweak: see apply_tweak."""
     fl = flags_from_meta(meta)
-    eng = make_engine(meta)
+    eng = make_engine(meta, tweak=tweak)
     dev = eng.device
     out = {}
     agents = ("receiver", "sender", "baseline_rec", "baseline_sen") if fl.use_binary else ("receiver",)
