@@ -25,6 +25,10 @@
  *   mmg_sender_vjp         <- backward() through ONE Sender.forward call      model.py:193-238
  *   mmg_receiver_vjp       <- backward() through ONE Receiver.forward call    model.py:333-474
  *   mmg_baseline_vjp       <- backward() through ONE Baseline.forward call    model.py:496-516
+ *   mmg_loss_binary_forward / _vjp <- multistep_loss_binary and its backward  model.py:907-968
+ *   mmg_loss_bas_forward / _vjp    <- multistep_loss_bas and its backward     model.py:971-988
+ *   mmg_rec_outp_forward / _vjp    <- get_rec_outp + log_softmax + nll_loss + loglikelihood and their backward
+ *                                                                             model.py:879-904, 1264-1275, 571-577
  *
  * Conventions
  *   - plain pointers and sizes; every pointer named d_* is DEVICE memory owned by the caller
@@ -337,6 +341,53 @@ int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_desc, const
                      const float* d_dps, const float* d_dh_w, const float* d_dh_new, float* d_dz, float* d_dh_prev, void* stream);
 int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
                      const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream);
+
+/* The loss functions of the training block as forward / vector-Jacobian launches over the CALLER'S tensors: handle-free (the
+ * arithmetic depends on no mmg_config), on the calling thread's current device, enqueued on `stream`; no host synchronisation, no
+ * hipMemset, at most 2 launches per forward and 1 per VJP.  Every array is fp32 and contiguous: per-step arrays are the reference's
+ * lists stacked over the n_steps steps, [n_steps, batch, .]; d_mask / d_ymask [n_steps, batch] uint8 (NULL = the reference's
+ * masks = None); d_target [batch] int64.  n_steps <= 1024 (an error beyond, never a truncation).  Sums over rows and row elements
+ * are formed in float64 in an order fixed by the shapes (no float atomics): bit-identical from run to run.
+ *   d_save: mmg_loss_save_doubles(n_steps) float64 of scratch the forward writes and the matching VJP reads (per step: active rows
+ *   n_t, the std guard den_t, c_t / n_t, c_t; then partial sums) -- caller-owned like everything else, no initialisation needed.
+ * With A_t = the rows of step t whose mask is set (all rows without masks), n_t = |A_t|, N = sum_t n_t, c_t = n_t / N with masks
+ * (model.py:960-961) and 1 / n_steps without (model.py:967), eps = 1e-8; a step with n_t == 0 contributes 0; N == 0 gives NaN.
+ *
+ * mmg_loss_binary_forward <- multistep_loss_binary / calculate_loss_binary            model.py:930-968, 907-927
+ *   feat, prob [n, B, W] (the sampled bits and their probabilities), logs [B], scores [n, B]; feat, logs and scores are constants
+ *   (the reference detaches them).  lp = sum_j z log(p + eps) + (1 - z) log((1 - p) + eps); w = (logs - scores) / den_t, den_t =
+ *   max(1, unbiased std over A_t of logs - scores) when n_t > 1, else 1 (model.py:912-915); ne_t = mean over A_t of
+ *   sum_j p log(p + eps) + (1 - p) log((1 - p) + eps).  loss[1] = sum_t c_t (mean over A_t of -w lp + (has_entropy ?
+ *   entropy_penalty ne_t : 0)); negent[n] = ne_t (the returned `entropies`).
+ * mmg_loss_binary_vjp: d_dloss [1], d_dnegent [n] (either NULL = zero) -> d_dprob [n, B, W], overwritten in full (0 off A_t).
+ *
+ * mmg_loss_bas_forward <- multistep_loss_bas / calculate_loss_bas                      model.py:971-988
+ *   loss[1] = sum_t c_t mean over A_t of (scores - logs)^2; logs is a constant (model.py:972).
+ * mmg_loss_bas_vjp: d_dloss [1] (NULL = zero) -> d_dscores [n, B], overwritten in full.
+ *
+ * mmg_rec_outp_forward <- get_rec_outp, log_softmax, nll_loss, loglikelihood          model.py:879-904, 1264-1275, 571-577
+ *   y [n, B, D] -> outp [B, D] = y[t*_b, b, :], t*_b = the first step whose ymask is set; the LAST step when ymask is NULL and
+ *   for a row without a set step (the reference's masked_select is undefined there, model.py:896-900); negent [n] = mean over ALL
+ *   rows of sum_d pi log(pi + eps), pi = softmax(y[t, b, :]) (model.py:880-886).  With d_target: logs [B] =
+ *   log_softmax(outp)[b, target_b] (model.py:1274) and nll [1] = -mean_b logs (model.py:1271); a target outside [0, D) is not
+ *   dereferenced, its logs entry and the nll are NaN.  d_target NULL: d_logs / d_nll are not touched.
+ * mmg_rec_outp_vjp: d_doutp [B, D], d_dnll [1], d_dnegent [n] (each NULL = zero) -> d_dy [n, B, D], overwritten in full; reads
+ *   no save array (t*_b and the softmax are recomputed from y and ymask). */
+int64_t mmg_loss_save_doubles(int n_steps);                                       /* host only; -1 outside 1..1024 */
+int mmg_loss_binary_forward(const float* d_feat, const float* d_prob, const float* d_logs, const float* d_scores,
+                            const uint8_t* d_mask, int n_steps, int batch, int width, int has_entropy, float entropy_penalty,
+                            float* d_loss, float* d_negent, double* d_save, void* stream);
+int mmg_loss_binary_vjp(const float* d_feat, const float* d_prob, const float* d_logs, const float* d_scores,
+                        const uint8_t* d_mask, const double* d_save, const float* d_dloss, const float* d_dnegent,
+                        int n_steps, int batch, int width, int has_entropy, float entropy_penalty, float* d_dprob, void* stream);
+int mmg_loss_bas_forward(const float* d_scores, const float* d_logs, const uint8_t* d_mask, int n_steps, int batch,
+                         float* d_loss, double* d_save, void* stream);
+int mmg_loss_bas_vjp(const float* d_scores, const float* d_logs, const uint8_t* d_mask, const double* d_save,
+                     const float* d_dloss, int n_steps, int batch, float* d_dscores, void* stream);
+int mmg_rec_outp_forward(const float* d_y, const uint8_t* d_ymask, const int64_t* d_target, int n_steps, int batch, int n_classes,
+                         float* d_outp, float* d_negent, float* d_logs, float* d_nll, double* d_save, void* stream);
+int mmg_rec_outp_vjp(const float* d_y, const uint8_t* d_ymask, const int64_t* d_target, const float* d_doutp, const float* d_dnll,
+                     const float* d_dnegent, int n_steps, int batch, int n_classes, float* d_dy, void* stream);
 
 /* The log block of a minibatch (model.py:1342-1461) gathered on the device: ONE launch writes one flat float64 vector the
  * caller copies to the host (asynchronously) and formats.  Layout (mmg_log_snapshot_count() doubles):

@@ -47,7 +47,9 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_baseline_forward", "mmg_set_profiling", "mmg_get_kernel_times", "mmg_host_shuffle", "mmg_train_steps",
            "mmg_dp_set_allreduce", "mmg_dp_train_step", "mmg_dp_train_steps", "mmg_clear_error", "mmg_degraded",
            "mmg_log_snapshot_count", "mmg_log_snapshot", "mmg_set_message_corruption", "mmg_exchange_vjp",
-           "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps"]
+           "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps",
+           "mmg_loss_save_doubles", "mmg_loss_binary_forward", "mmg_loss_binary_vjp", "mmg_loss_bas_forward", "mmg_loss_bas_vjp",
+           "mmg_rec_outp_forward", "mmg_rec_outp_vjp"]
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
 EVAL_ACC_HEAD = 4
@@ -88,6 +90,17 @@ def load():
     lib.mmg_receiver_vjp.restype = i32
     lib.mmg_receiver_vjp.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_baseline_vjp.restype = i32; lib.mmg_baseline_vjp.argtypes = [vp, i32, fp, fp, fp, i32, fp, fp, fp, fp, vp]
+    # the loss functions (handle-free): pointers, then sizes; see include/mmg.h
+    f32 = C.c_float
+    lib.mmg_loss_save_doubles.restype = i64; lib.mmg_loss_save_doubles.argtypes = [i32]
+    lib.mmg_loss_binary_forward.restype = i32
+    lib.mmg_loss_binary_forward.argtypes = [fp, fp, fp, fp, vp, i32, i32, i32, i32, f32, fp, fp, vp, vp]
+    lib.mmg_loss_binary_vjp.restype = i32
+    lib.mmg_loss_binary_vjp.argtypes = [fp, fp, fp, fp, vp, vp, fp, fp, i32, i32, i32, i32, f32, fp, vp]
+    lib.mmg_loss_bas_forward.restype = i32; lib.mmg_loss_bas_forward.argtypes = [fp, fp, vp, i32, i32, fp, vp, vp]
+    lib.mmg_loss_bas_vjp.restype = i32; lib.mmg_loss_bas_vjp.argtypes = [fp, fp, vp, vp, fp, i32, i32, fp, vp]
+    lib.mmg_rec_outp_forward.restype = i32; lib.mmg_rec_outp_forward.argtypes = [fp, vp, vp, i32, i32, i32, fp, fp, fp, fp, vp, vp]
+    lib.mmg_rec_outp_vjp.restype = i32; lib.mmg_rec_outp_vjp.argtypes = [fp, vp, vp, fp, fp, fp, i32, i32, i32, fp, vp]
     lib.mmg_dp_set_allreduce.restype = i32; lib.mmg_dp_set_allreduce.argtypes = [vp, vp, vp]
     lib.mmg_dp_train_step.restype = i32; lib.mmg_dp_train_step.argtypes = [vp, fp, vp, fp, fp, fp, fp, u64, i32, i32, vp]
     lib.mmg_dp_train_steps.restype = i32; lib.mmg_dp_train_steps.argtypes = [vp, fp, vp, i64, fp, u64, i32, vp]

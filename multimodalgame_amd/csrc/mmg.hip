@@ -24,6 +24,7 @@
 #include "kernels_rc.h"
 #include "kernels_vjp.h"
 #include "kernels_eval.h"
+#include "kernels_loss.h"
 #ifdef MMG_ROLE_DIAG
 #include "diag_kernels.h"
 #endif
@@ -1158,4 +1159,96 @@ extern "C" int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, cons
     }
     if (launch_vjp_nn(h, st, np, pr[0], pr[1])) return -1;
     return launch_vjp_wgrad(h, st, 4 + which, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The loss functions (kernels_loss.h): handle-free -- the arithmetic depends on no mmg_config -- on the calling thread's current
+// device.  Forward: the partial-sum launch over (slots, steps) and the one-workgroup finishing launch; VJP: one launch.
+// ---------------------------------------------------------------------------------------------
+static int loss_shape_ok(const char* who, int n, int B, int inner) {
+    if (n < 1 || B < 1 || inner < 1) return fail("%s: n_steps, batch and the row width must be positive (got %d, %d, %d)", who, n, B, inner);
+    if (n > MMG_LOSS_MAX_STEPS) return fail("%s: n_steps must be <= %d (got %d)", who, MMG_LOSS_MAX_STEPS, n);
+    return 0;
+}
+static int loss_flat_grid(size_t items) {
+    const size_t g = (items + MMG_BLOCK - 1) / MMG_BLOCK;
+    return (int)(g > 65536 ? 65536 : g);                 // the kernels walk the rest with a grid stride
+}
+
+extern "C" int64_t mmg_loss_save_doubles(int n_steps) {
+    if (n_steps < 1 || n_steps > MMG_LOSS_MAX_STEPS) { fail("mmg_loss_save_doubles: n_steps must be in 1..%d (got %d)", MMG_LOSS_MAX_STEPS, n_steps); return -1; }
+    return loss_save_doubles(n_steps);
+}
+
+extern "C" int mmg_loss_binary_forward(const float* d_feat, const float* d_prob, const float* d_logs, const float* d_scores,
+                                       const uint8_t* d_mask, int n_steps, int batch, int width, int has_entropy,
+                                       float entropy_penalty, float* d_loss, float* d_negent, double* d_save, void* stream) {
+    if (loss_shape_ok("mmg_loss_binary_forward", n_steps, batch, width)) return -1;
+    if (!d_feat || !d_prob || !d_logs || !d_scores || !d_loss || !d_negent || !d_save)
+        return fail("mmg_loss_binary_forward: feat / prob / logs / scores / loss / negent / save must not be NULL");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_loss_binary_part, dim3(loss_slots(batch), n_steps), dim3(MMG_BLOCK), 0, st, d_feat, d_prob, d_logs, d_scores,
+                       d_mask, n_steps, batch, width, d_save);
+    hipLaunchKernelGGL(k_loss_finish<true>, dim3(1), dim3(MMG_BLOCK), 0, st, d_save, n_steps, batch, d_mask ? 1 : 0,
+                       has_entropy ? 1 : 0, entropy_penalty, d_loss, d_negent);
+    return launch_check("k_loss_binary");
+}
+
+extern "C" int mmg_loss_binary_vjp(const float* d_feat, const float* d_prob, const float* d_logs, const float* d_scores,
+                                   const uint8_t* d_mask, const double* d_save, const float* d_dloss, const float* d_dnegent,
+                                   int n_steps, int batch, int width, int has_entropy, float entropy_penalty, float* d_dprob,
+                                   void* stream) {
+    if (loss_shape_ok("mmg_loss_binary_vjp", n_steps, batch, width)) return -1;
+    if (!d_feat || !d_prob || !d_logs || !d_scores || !d_save || !d_dprob)
+        return fail("mmg_loss_binary_vjp: feat / prob / logs / scores / save / dprob must not be NULL");
+    hipLaunchKernelGGL(k_loss_binary_vjp, dim3(loss_flat_grid((size_t)n_steps * batch * width)), dim3(MMG_BLOCK), 0, (hipStream_t)stream,
+                       d_feat, d_prob, d_logs, d_scores, d_mask, d_save, d_dloss, d_dnegent, n_steps, batch, width,
+                       has_entropy ? 1 : 0, entropy_penalty, d_dprob);
+    return launch_check("k_loss_binary_vjp");
+}
+
+extern "C" int mmg_loss_bas_forward(const float* d_scores, const float* d_logs, const uint8_t* d_mask, int n_steps, int batch,
+                                    float* d_loss, double* d_save, void* stream) {
+    if (loss_shape_ok("mmg_loss_bas_forward", n_steps, batch, 1)) return -1;
+    if (!d_scores || !d_logs || !d_loss || !d_save) return fail("mmg_loss_bas_forward: scores / logs / loss / save must not be NULL");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_loss_bas_part, dim3(loss_slots(batch), n_steps), dim3(MMG_BLOCK), 0, st, d_scores, d_logs, d_mask, n_steps,
+                       batch, d_save);
+    hipLaunchKernelGGL(k_loss_finish<false>, dim3(1), dim3(MMG_BLOCK), 0, st, d_save, n_steps, batch, d_mask ? 1 : 0, 0, 0.f, d_loss,
+                       (float*)nullptr);
+    return launch_check("k_loss_bas");
+}
+
+extern "C" int mmg_loss_bas_vjp(const float* d_scores, const float* d_logs, const uint8_t* d_mask, const double* d_save,
+                                const float* d_dloss, int n_steps, int batch, float* d_dscores, void* stream) {
+    if (loss_shape_ok("mmg_loss_bas_vjp", n_steps, batch, 1)) return -1;
+    if (!d_scores || !d_logs || !d_save || !d_dscores) return fail("mmg_loss_bas_vjp: scores / logs / save / dscores must not be NULL");
+    hipLaunchKernelGGL(k_loss_bas_vjp, dim3(loss_flat_grid((size_t)n_steps * batch)), dim3(MMG_BLOCK), 0, (hipStream_t)stream, d_scores,
+                       d_logs, d_mask, d_save, d_dloss, n_steps, batch, d_dscores);
+    return launch_check("k_loss_bas_vjp");
+}
+
+extern "C" int mmg_rec_outp_forward(const float* d_y, const uint8_t* d_ymask, const int64_t* d_target, int n_steps, int batch,
+                                    int n_classes, float* d_outp, float* d_negent, float* d_logs, float* d_nll, double* d_save,
+                                    void* stream) {
+    if (loss_shape_ok("mmg_rec_outp_forward", n_steps, batch, n_classes)) return -1;
+    if (!d_y || !d_outp || !d_negent || !d_save) return fail("mmg_rec_outp_forward: y / outp / negent / save must not be NULL");
+    if (d_target && (!d_logs || !d_nll)) return fail("mmg_rec_outp_forward: with a target, logs and nll must not be NULL");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_rec_outp_part, dim3(loss_slots(batch), n_steps), dim3(MMG_BLOCK), 0, st, d_y, d_ymask, d_target, n_steps, batch,
+                       n_classes, d_outp, d_logs, d_save);
+    hipLaunchKernelGGL(k_rec_outp_finish, dim3(1), dim3(MMG_BLOCK), 0, st, (const double*)d_save, n_steps, batch, d_negent,
+                       d_target ? d_nll : (float*)nullptr);
+    return launch_check("k_rec_outp");
+}
+
+extern "C" int mmg_rec_outp_vjp(const float* d_y, const uint8_t* d_ymask, const int64_t* d_target, const float* d_doutp,
+                                const float* d_dnll, const float* d_dnegent, int n_steps, int batch, int n_classes, float* d_dy,
+                                void* stream) {
+    if (loss_shape_ok("mmg_rec_outp_vjp", n_steps, batch, n_classes)) return -1;
+    if (!d_y || !d_dy) return fail("mmg_rec_outp_vjp: y / dy must not be NULL");
+    const size_t blocks = ((size_t)n_steps * batch + MMG_BLOCK / 64 - 1) / (MMG_BLOCK / 64);
+    hipLaunchKernelGGL(k_rec_outp_vjp, dim3((int)(blocks > 65536 ? 65536 : blocks)), dim3(MMG_BLOCK), 0, (hipStream_t)stream, d_y, d_ymask,
+                       d_target, d_doutp, d_dnll, d_dnegent, n_steps, batch, n_classes, d_dy);
+    return launch_check("k_rec_outp_vjp");
 }

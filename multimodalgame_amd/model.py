@@ -14,7 +14,10 @@ import torch.nn.functional as F
 from . import flags as _flags
 from .agents import Baseline, Receiver, Sender
 from .flags import FLAGS
-from .game import Game, exchange, get_rec_outp
+from .game import Game, exchange
+# the reference's loss functions under their own names (model.py:571-577, 879-988), differentiable on the device
+from .losses import (calculate_loss_bas, calculate_loss_binary, get_rec_outp, loglikelihood,  # noqa: F401
+                     multistep_loss_bas, multistep_loss_binary)
 from .misc import (FileLogger, VisdomLogger, build_mask, cbow, embed, load_epoch, load_hdf5, read_data, torch_load, torch_save,
                    write_synthetic_dataset)
 from .sparks import sparks

@@ -2,11 +2,16 @@
 losses (oracle/cpu_ref helpers on CPU copies, model.py:1248-1305) and four backward() calls (model.py:1309-1328) -- against the
 same loop over the same parameters in plain PyTorch on the GPU.
 
-  python scripts/module_autograd_time.py [--configs c2,c5shard] [--iters 20] [--warmup 3]
+  python scripts/module_autograd_time.py [--configs c2,c5shard] [--iters 20] [--warmup 3] [--losses cpu|device|cpu,device]
 
 c2: configs[1] (Adaptive, binary, 30 classes, batch 64, max_exchange 10).  c5shard: one GPU's shard of configs[4] (Fixed,
 continuous, 1000 classes, 256 samples).  Prints one JSON line per config: wall ms per minibatch (forward + losses + backward,
-host time included, synchronised at the end of every minibatch) for the HIP modules and for plain PyTorch."""
+host time included, synchronised at the end of every minibatch) for the HIP modules and for plain PyTorch.
+
+--losses cpu (the default): the losses are oracle/cpu_ref's on CPU copies, as above.  --losses device: multimodalgame_amd.losses on
+the device (no copies).  --losses cpu,device measures both routes in one invocation: per config the two routes alternate in
+--rounds rounds of --iters minibatches each, and the line carries every round's time and the median per route
+(hip_ms_<route>); plain PyTorch is timed with the cpu route only."""
 import argparse
 import json
 import os
@@ -133,10 +138,16 @@ def losses(fl, out, target):
             "baseline_sen": cpu_ref.multistep_loss_bas(bs, logs, m_bas)}
 
 
-def minibatch(agents, params, fl, data, desc, target):
+def device_losses(fl, out, target):
+    """model.py:1248-1305 on the device: multimodalgame_amd.losses.training_losses, nothing is copied to the host."""
+    from multimodalgame_amd.losses import training_losses
+    return training_losses(out, target, fl)
+
+
+def minibatch(agents, params, fl, data, desc, target, route="cpu"):
     for p in params:
         p.grad = None
-    ls = losses(fl, module_exchange(agents, fl, data, desc, not fl.fixed_exchange), target)
+    ls = (device_losses if route == "device" else losses)(fl, module_exchange(agents, fl, data, desc, not fl.fixed_exchange), target)
     for k in ("receiver", "sender", "baseline_rec", "baseline_sen"):
         if k in ls:
             ls[k].backward()
@@ -152,7 +163,7 @@ def time_loop(fn, iters, warmup):
     return (time.perf_counter() - t0) * 1e3 / iters
 
 
-def run(name, iters, warmup, which):
+def run(name, iters, warmup, which, routes=("cpu",), rounds=1):
     from multimodalgame_amd.agents import Baseline, Receiver, Sender
     from multimodalgame_amd.game import Game
     kw, n_classes, batch = CONFIGS[name]
@@ -174,7 +185,19 @@ def run(name, iters, warmup, which):
         for m in agents:
             m.train()
         params = [p for m in agents for p in m.parameters()]
-        res["hip_ms"] = time_loop(lambda: minibatch(agents, params, fl, data, dsc, tgt), iters, warmup)
+        tgts = {"cpu": tgt, "device": tgt.to(dev)}
+        if routes == ("cpu",) and rounds == 1:
+            res["hip_ms"] = time_loop(lambda: minibatch(agents, params, fl, data, dsc, tgt), iters, warmup)
+        else:
+            per = {r: [] for r in routes}
+            for i in range(rounds):                                  # the routes alternate: both see the same machine state
+                for r in routes:
+                    per[r].append(time_loop(lambda: minibatch(agents, params, fl, data, dsc, tgts[r], r), iters, warmup if i == 0 else 1))
+            res["rounds"] = rounds
+            for r in routes:
+                res["hip_ms_%s_rounds" % r] = per[r]
+                res["hip_ms_%s" % r] = float(np.median(per[r]))
+            res["hip_ms"] = res["hip_ms_%s" % routes[0]]
     if which in ("both", "torch"):
         plain = {k: m.to(dev) for k, m in ref.items()}
         agents = (PlainSender(plain["sender"]), PlainReceiver(plain["receiver"]), plain["baseline_sen"], plain["baseline_rec"])
@@ -191,11 +214,16 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--which", choices=("both", "hip", "torch"), default="both")
+    ap.add_argument("--losses", default="cpu", help="cpu, device or cpu,device (both routes, alternating)")
+    ap.add_argument("--rounds", type=int, default=1, help="alternating rounds per route with --losses cpu,device")
     args = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
+    routes = tuple(args.losses.split(","))
+    if not routes or any(r not in ("cpu", "device") for r in routes):
+        ap.error("--losses takes cpu, device or cpu,device")
     for name in args.configs.split(","):
-        print(json.dumps(run(name, args.iters, args.warmup, args.which)), flush=True)
+        print(json.dumps(run(name, args.iters, args.warmup, args.which, routes, args.rounds)), flush=True)
 
 
 if __name__ == "__main__":
