@@ -65,7 +65,7 @@ struct JobBuilder {
 // ---------------------------------------------------------------------------------------------
 // job table: every parameter tensor's gradient is produced by exactly one GEMM / column-sum job
 // (two for the matrices whose input is a concatenation: y1, both baselines' linear1).
-// code_bias: which kernels leave the sender's code_bias operands behind (host_select.h: tile_path / fast_shape / neither).
+// code_bias: which kernels leave the sender's code_bias operands behind (host_select.h: the family -- FAM_TILE / FAM_FAST / the others).
 // ---------------------------------------------------------------------------------------------
 enum CodeBiasJob { CODE_BIAS_TILE, CODE_BIAS_FAST, CODE_BIAS_GENERIC };
 

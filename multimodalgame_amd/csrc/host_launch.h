@@ -1,11 +1,69 @@
-// host_launch.h -- host side of mmg.hip: the handle, the timing scope of a launch and the launch helpers that more than one
-// entry point uses.  Included by mmg.hip only (after the kernels and fail() / HIP_OK).
+// host_launch.h -- host side of mmg.hip: the handle with its Selection and LaunchPlan, the timing scope of a launch and the launch helpers that more
+// than one entry point uses.  Included by mmg.hip only (after the kernels and fail() / HIP_OK).
 #pragma once
 
 struct KernelTimer { std::string name; hipEvent_t t0, t1; };
 
-// What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes and the
-// co-residency budgets.  Constant until the next selection (mmg_create; error_gate after a timed-out dependency).
+// The D == 30 instantiations of the register-resident kernels (D = 30: own instantiation, other D <= 32: capacity 32): each
+// family picks its function once, selection and launch share the choice.
+static auto game_fast_fn(int D) { return D == 30 ? k_game_fast<30> : k_game_fast<32>; }
+static auto bwd_sample_fn(int D) { return D == 30 ? k_bwd_sample<64, 100, 30> : k_bwd_sample<64, 100, 32>; }
+// V == 100 has its own instantiation as well; every other width runs the V = 0 one (layout.h: fast_wide_v)
+template <bool STATS, bool DC> static auto bwd_conv_fast_fn(int D, int V) {
+    if (V != 100) return k_bwd_conv_fast<256, 32, 64, 0, 32, STATS, DC>;
+    return D == 30 ? k_bwd_conv_fast<256, 32, 64, 100, 30, STATS, DC> : k_bwd_conv_fast<256, 32, 64, 100, 32, STATS, DC>;
+}
+
+// Which kernel family serves the handle (host_select.h: select_family): the register-resident kernels of the small agents (the
+// former fast_shape) | the same agents with many classes (kernels_mc*.h) | sample tiles on the matrix cores | the per-sample kernels
+enum Family { FAM_FAST, FAM_MC, FAM_TILE, FAM_GENERIC };
+// How far a forward pass runs and what it keeps (the ABI's run_all_steps 0 / 1 / 2 / 3, mapped at the entry points: tape_mode)
+enum TapeMode { TAPE_TO_STOP, TAPE_ALL, TAPE_MINIMAL, TAPE_LOG };
+static TapeMode tape_mode(int v) { return v == 0 ? TAPE_TO_STOP : v == 2 ? TAPE_MINIMAL : v == 3 ? TAPE_LOG : TAPE_ALL; }
+// The sample tiles' forward, in fall-through order: class helpers | one workgroup per tile | one launch of co-resident roles
+// (per-sample or per-tile receiver roles) | the wide receiver as one role launch / per step | per-step launches
+enum TileFwd { TF_SPLIT, TF_WHOLE, TF_PERSIST_SAMPLE, TF_PERSIST_TILE, TF_RC_PERSIST, TF_RC_STEP, TF_STEP };
+enum BasKernel { BAS_TILE4, BAS_LIVE3, BAS_ALL2 };          // standalone baselines: k_baselines4 (after k_gemm_nt unless basehx rode along) / 3 / 2
+enum BwdRec { BR_SAMPLE, BR_TILE, BR_RC };                  // the tiles' receiver BPTT: k_bwd_sample / k_bwd_tile<512, 2|4|8> / k_rc_bwd
+enum DcKernel { DC_NONE, DC_TILE, DC_PLAIN };               // the class-side reduction left after the backward launch: none (class roles) / k_dC_tile / k_dC
+
+// The launch plan of a handle: every decision the per-minibatch launches need, taken ONCE by select_paths (host_select.h: plan_launches) from Dims, the switches and the
+// device's budgets.  The launch code of mmg.hip reads it and tests nothing else; the per-call inputs (train, tape mode, defer_bas, the corruption mask, ForwardState) join it at the call.
+struct LaunchPlan {
+    int tiles = 0, n_stats = 0, n_bas = 0, basehx_tiles = 0, nprep_hx = 0;      // sample tiles, statistics / baseline roles, basehx tiles, k_prep's blocks incl. h_x
+    TileFwd tile_fwd = TF_STEP;
+    decltype(&k_conv_tile<512>) conv_tile_fn = nullptr;
+    decltype(&k_conv_persist<512, true>) persist_fn = nullptr;
+    int rsample = 0, ns1 = 0, ns2 = 0;          // k_conv_persist: receiver-role level 0-3, sender roles per tile
+    int chunk_roles = 0, chunk_tiles = 0, n_chunk = 0;   // the chunked role launches (k_conv_persist with sample roles, k_rc_persist): roles per tile, tiles per launch, launches
+    bool basehx_rides = false;                  // ... whose single launch may carry the basehx tiles (at the call: train && !run_all)
+    bool skip_ok = false;                       // per-step launches may skip finished tiles (at the call: train && !run_all)
+    int s1_grid = 0, s2_grid = 0, rc_nj = 0, rc_njw = 0;
+    int mc_ntile = 0, mc_grid = 0, mc3p_grid = 0;
+    bool mc3p_wins = false;                     // the pair kernel needs fewer rounds (at the call: lean)
+    bool merge_prep = false, fwd_basehx = false;         // k_prep's blocks / the basehx tiles as roles of the conversation launch (basehx at the call: train && !all rows)
+    decltype(&k_conversation_fast3<256, 32, 64, 100, false>) fast_fn = nullptr;
+    decltype(&k_conversation<256>) conv_fn = nullptr;
+    const char *conv_name = "k_conversation", *bwd_name = "k_bwd_conv";
+    bool bas_defer_ok = false, bas_pending_ok = false;   // roles of the backward launch (fused step) / of k_bas_stats (phased step)
+    BasKernel bas_kernel = BAS_ALL2;
+    int bas2_z = 0;
+    bool row_map = false, zero_dead = false;    // k_wgrad walks the live-row list (conv_done: always); dead rows zeroed instead
+    bool merged_send = false, send_own = false, dhx_own = false;
+    int pre_bands = 1, pre_smem = 0, n_pre = 0, n_rowblk = 0, n_hbands = 0, dhx_blk = 0, dhx_grid = 0;
+    decltype(&k_bwd_pre<8>) pre_fn = nullptr;
+    decltype(&k_bwd_pre_send<8>) pre_send_fn = nullptr;
+    BwdRec bwd_rec = BR_TILE;
+    decltype(&k_bwd_tile<512, 2>) bwd_tile_fn = nullptr;
+    int mc_ngroup = 0, mc_nred = 0, dc_grid = 0, dc_slices = 1;
+    decltype(bwd_conv_fast_fn<true, true>(0, 0)) bwd_fast_fn = nullptr, bwd_fast_stats_fn = nullptr;
+    decltype(&k_bwd_conv<false>) bwd_conv_fn = nullptr;
+    int n_dbar = 0, n_class = 0;                // k_bwd_conv_fast: dbar tiles, class roles without the statistics
+    DcKernel dc = DC_NONE;
+};
+
+// What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes, the co-residency budgets, the
+// family and the launch plan.  Constant until the next selection (mmg_create; error_gate after a timed-out dependency).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
     bool sw_merge_bas = false;   // (= merge_roles) the baselines' forward pass rides in the backward / statistics launch; off: its own launch
@@ -45,6 +103,8 @@ struct Selection {
     // minus a margin): the role launches (k_conv_persist / k_conv_split / k_conversation_mc) spin on each other, so a launch
     // may never hold more roles than this
     int resident_budget = 0, split_budget = 0, n_cu = 0;
+    Family family = FAM_GENERIC;
+    LaunchPlan plan;
 };
 
 // What the last forward pass left for the later phases of the same minibatch (mmg_loss_stats / mmg_backward may be separate ABI
@@ -114,16 +174,6 @@ static int launch_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("launch of %s failed: %s", what, hipGetErrorString(e));
     return 0;
-}
-
-// The D == 30 instantiations of the register-resident kernels (D = 30: own instantiation, other D <= 32: capacity 32): each
-// family picks its function once, selection and launch share the choice.
-static auto game_fast_fn(int D) { return D == 30 ? k_game_fast<30> : k_game_fast<32>; }
-static auto bwd_sample_fn(int D) { return D == 30 ? k_bwd_sample<64, 100, 30> : k_bwd_sample<64, 100, 32>; }
-// V == 100 has its own instantiation as well; every other width runs the V = 0 one (layout.h: fast_wide_v)
-template <bool STATS, bool DC> static auto bwd_conv_fast_fn(int D, int V) {
-    if (V != 100) return k_bwd_conv_fast<256, 32, 64, 0, 32, STATS, DC>;
-    return D == 30 ? k_bwd_conv_fast<256, 32, 64, 100, 30, STATS, DC> : k_bwd_conv_fast<256, 32, 64, 100, 32, STATS, DC>;
 }
 
 static int launch_gemm_nt(mmg_handle* h, hipStream_t st, const char* name, const float* X, int ldx, const float* Wm, int ldw,

@@ -1,46 +1,201 @@
-// host_select.h -- host side of mmg.hip: launch geometry shared by the selection and the launches, the path predicates and
-// select_paths.  Included by mmg.hip only (after host_launch.h and host_jobs.h).
+// host_select.h -- host side of mmg.hip: select_paths decides, once per handle (and again for the no-roles fall-back), which kernels serve its shape
+// on this device: capability flags and budgets, then the family (select_family) and the launch plan (plan_launches: every launch of a minibatch with
+// its variant and grid), printed by print_plan (-DMMG_DEBUG_CREATE) and checked against the no-roles invariant in one place.  Included by mmg.hip only.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
-// Launch geometry: role / tile counts that select_paths proves co-resident and the launches use as their grids.  (The kernels
+// Launch geometry: role / tile counts that select_paths proves co-resident and the plan hands to the launches as their grids.  (The kernels
 // find their roles from the counts they are handed; what they compute themselves stays in the kernel headers.)
 // ---------------------------------------------------------------------------------------------
 inline int sample_tiles(int B) { return (B + MMG_TM - 1) / MMG_TM; }
 inline int stat_roles(int T) { return (5 * T + 2 + 3) / 4; }          // statistics roles: one (stream, step) pair per wave
 inline int bas_roles(const Dims& d) { return ((d.T * d.B + 15) / 16) * 2 * ((d.K + 63) / 64); }     // baseline roles: 16 live rows x 64 hidden units each
 inline int basehx_tiles(const Dims& d) { return ((d.B + 15) / 16) * ((d.K + 15) / 16); }
-// basehx tiles for k_baselines4 ride along a conversation launch as trailing workgroups (training minibatches of <= 64 samples)
-inline bool basehx_rides(const Dims& d, int nchunk, int train, int run_all, bool merge_roles) {
-    return nchunk == 1 && train && d.use_binary && !run_all && d.B <= 64 && !(d.H & 3) && merge_roles;
-}
 // roles per sample tile of the wide receiver's one-launch conversation (k_rc_persist)
 inline int rc_roles_per_tile(const Dims& d) {
     const int nj = d.R / 16, njw = d.W / 16;
     return (nj > njw ? nj : njw) + njw + (d.H + 63) / 64 + 1;
 }
 
-// register-resident kernels exist for the agent shape of BASELINE configs 1-3
-static bool fast_shape(const mmg_handle* h) {
-    const Dims& d = h->dm;
-    if (h->sel.tile_ok && h->sel.tile_force) return false;
-    return h->sel.use_fast && d.H == 256 && d.W == 32 && d.R == 64 && (d.V == 100 || fast_wide_v(d.V)) && d.D <= 32 && d.T <= 16;   // (D = 30: own instantiation, other D <= 32: capacity 32; V = 100 likewise, other V % 4 == 0: at run time)
-}
-// every other shape: sample tiles on the matrix cores (kernels_tile.h); the per-sample generic kernels remain for
-// dimensions whose tile does not fit the LDS and for the agent-level entry points
-// the small agents with many classes (32 < D <= 1024): register-resident conversation with class slices (kernels_mc.h) up to 2 048
-// samples per GPU (measured at D = 1000: 2 048 samples 1 064 us per minibatch against 1 113 on the sample tiles, 4 096 samples
-// 2 090 against 1 242 -- from 256 tiles on, the tiles fill the chip and a workgroup per sample is 16 waves of it;
-// MMG_TILE=1 forces the tiles)
-static bool mc_path(const mmg_handle* h) { return h->sel.mc_ok && !(h->sel.tile_ok && h->sel.tile_force) && (h->dm.B <= 2048 || !h->sel.tile_ok); }
-static bool tile_path(const mmg_handle* h) { return h->sel.tile_ok && !fast_shape(h) && !mc_path(h); }
-// continuous many-class path: the two-launch backward of kernels_mc.h
-static bool mc_bwd(const mmg_handle* h) { return mc_path(h) && !h->dm.use_binary; }
+// continuous many-class family: the two-launch backward of kernels_mc.h
+static bool mc_bwd(const mmg_handle* h) { return h->sel.family == FAM_MC && !h->dm.use_binary; }
 // single-GPU minibatch: the statistics run as extra roles of the backward launch (no all-reduce in between)
 static bool merge_stats(const mmg_handle* h) {
     if (mc_bwd(h)) return h->sel.merge_roles;            // (sum of rewards / hits only: one extra workgroup of k_bwd_mc2)
-    return fast_shape(h) && h->dm.use_binary && h->fwd.scores_in_parts && h->sel.merge_roles;
+    return h->sel.family == FAM_FAST && h->dm.use_binary && h->fwd.scores_in_parts && h->sel.merge_roles;
 }
+
+// The family.  FAM_FAST (fast_shape): register-resident kernels exist for the agent shape of BASELINE configs 1-3.  Every other shape: sample tiles on
+// the matrix cores (kernels_tile.h); the per-sample generic kernels remain for dimensions whose tile does not fit the LDS and for the agent-level entry
+// points.  The small agents with many classes (32 < D <= 1024): register-resident conversation with class slices (kernels_mc.h) up to 2 048 samples per
+// GPU (measured at D = 1000: 2 048 samples 1 064 us per minibatch against 1 113 on the sample tiles, 4 096 samples 2 090 against 1 242 -- from 256 tiles
+// on, the tiles fill the chip and a workgroup per sample is 16 waves of it; MMG_TILE=1 forces the tiles)
+static Family select_family(const Selection& s, const Dims& d) {
+    const bool forced = s.tile_ok && s.tile_force;
+    // (D = 30: own instantiation, other D <= 32: capacity 32; V = 100 likewise, other V % 4 == 0: at run time)
+    const bool fast = !forced && s.use_fast && d.H == 256 && d.W == 32 && d.R == 64 && (d.V == 100 || fast_wide_v(d.V)) && d.D <= 32 && d.T <= 16;
+    const bool mc = s.mc_ok && !forced && (d.B <= 2048 || !s.tile_ok);
+    return (s.tile_ok && !fast && !mc) ? FAM_TILE : mc ? FAM_MC : fast ? FAM_FAST : FAM_GENERIC;
+}
+
+// The launch plan (host_launch.h: LaunchPlan): which launches a minibatch of this handle enqueues and at what grid.  Everything here depends on
+// Dims, the switches and the budgets select_paths has just measured -- nothing on a call's arguments.
+static void plan_launches(mmg_handle* h) {
+    const Dims& d = h->dm;
+    Selection& s = h->sel;
+    LaunchPlan& p = s.plan;
+    const Family fam = s.family;
+    const int tiles = sample_tiles(d.B), TB = d.T * d.B;
+    p.tiles = tiles;
+    p.n_stats = stat_roles(d.T);
+    p.n_bas = bas_roles(d);
+    p.basehx_tiles = basehx_tiles(d);
+    p.nprep_hx = prep_blocks(d, s.prep_cpb, true);
+    // ---- forward, sample tiles (the order of the outcomes is the fall-through order) ----
+    p.conv_tile_fn = s.tile_nt == 512 ? k_conv_tile<512> : k_conv_tile<256>;
+    p.skip_ok = !d.fixed;
+    p.s1_grid = tiles * ((d.H + 15) / 16);
+    p.s2_grid = tiles * ((d.W + 15) / 16);
+    p.rc_nj = d.R / 16;
+    p.rc_njw = d.W / 16;
+    // all roles of a launch must be co-resident (`budget` workgroups, occupancy query above): as many whole tiles per launch
+    // as fit, the batch in consecutive launches (the conversations of different samples are independent)
+    auto chunks = [&](int per_tile, int budget) {
+        const int ct = budget / per_tile > 1 ? budget / per_tile : 1;
+        p.chunk_roles = per_tile;
+        p.n_chunk = (tiles + ct - 1) / ct;
+        p.chunk_tiles = (tiles + p.n_chunk - 1) / p.n_chunk;
+        p.basehx_rides = p.n_chunk == 1 && d.use_binary && d.B <= 64 && !(d.H & 3) && s.merge_roles;   // training minibatches of <= 64 samples
+    };
+    if (s.tile_split) p.tile_fwd = TF_SPLIT;
+    else if (!s.tile_ext) p.tile_fwd = TF_WHOLE;
+    else {
+        p.tile_fwd = !s.rc_fwd ? TF_STEP : s.rc_persist ? TF_RC_PERSIST : TF_RC_STEP;
+        if (s.tile_persist) {
+            p.ns1 = s.persist_ns1;
+            p.ns2 = s.persist_ns2;
+            // receiver shape of the register-resident kernels: one receiver role per SAMPLE (rs_role) beside the tiles' sender roles
+            int rs = s.rs_capable ? 1 : 0;
+            if (rs && d.W == 256 && s.sw_rmsg) rs = 2;          // ... which also form the receiver's message
+            if (rs == 2 && d.H % 64 == 0 && d.H / 64 <= 16 && s.sw_fused_s) { rs = 3; p.ns1 = d.H / 64; p.ns2 = d.W / 16; }   // fused sender roles (sa_role / sb_role)
+            const int per_tile = MMG_TM + p.ns1 + p.ns2, ct = s.resident_budget / per_tile > 1 ? s.resident_budget / per_tile : 1;
+            // (measured with config 4's agents: 256 samples in 4 launches 471 us against 858 us as per-step launches; 1024 samples
+            //  in 13 launches 1 723 against 1 544 -- beyond six launches the per-step GEMM launches over the whole batch win)
+            if (rs && (tiles + ct - 1) / ct <= 6 && per_tile <= s.resident_budget) {
+                p.tile_fwd = TF_PERSIST_SAMPLE;
+                p.rsample = rs;
+                p.persist_fn = (rs == 3 && s.persist_ll) ? k_conv_persist<512, true, true> : k_conv_persist<512, true>;
+                chunks(per_tile, s.resident_budget);
+            } else if (!rs && tiles * (1 + p.ns1 + p.ns2) <= s.resident_budget) {
+                p.tile_fwd = TF_PERSIST_TILE;
+                p.persist_fn = k_conv_persist<512, false>;
+                p.chunk_roles = 1 + p.ns1 + p.ns2;
+            }
+        }
+        // wide receiver, all roles co-resident: one launch for the whole conversation (kernels_rc.h: k_rc_persist)
+        if (p.tile_fwd == TF_RC_PERSIST) chunks(rc_roles_per_tile(d), s.rc_budget);
+    }
+    {   // ---- forward, many classes ----
+        const int ntile = p.mc_ntile = (d.B + 15) / 16, per16 = s.n_cu / 16 > 0 ? s.n_cu / 16 : 1, per128 = s.n_cu / 128 > 0 ? s.n_cu / 128 : 1;
+        p.mc_grid = s.mc_xcd ? ((ntile + 7) / 8) * 128 : ntile * 16;     // (mc_xcd assumes the 8 XCDs of an unpartitioned MI355X; select_paths clears it otherwise)
+        // the pair kernel (kernels_mc3p.h) when it needs fewer rounds: a round of 16 pairs takes ~1.55x a round of 16 single tiles (measured,
+        // scripts/mc3p_ab.py: 768 samples = 24 pairs = two rounds lose to three rounds of single tiles, every other multiple of 256 from 512 on wins)
+        const int npair = (ntile + 1) / 2, mc3p_rounds = (npair + s.n_cu / 16 - 1) / per16, mc3_rounds = (ntile * 16 + s.n_cu - 1) / s.n_cu;
+        p.mc3p_wins = s.mc3_ok && s.mc3p_ok && 31 * mc3p_rounds < 20 * mc3_rounds;
+        // 128 consecutive workgroups = 8 pairs of tiles x 16 members; one workgroup per CU: the launch is persistent
+        p.mc3p_grid = 128 * ((npair + 7) / 8 > s.n_cu / 128 ? per128 : (npair + 7) / 8);
+    }
+    // ---- forward, register-resident / generic ----
+    // k_prep's blocks run as leading roles of k_conversation_fast3's launch -- when every prep and sample role has a CU of its own
+    // (the launch holds ONE workgroup per CU: with 512 samples the 531 prep roles would be two more rounds of workgroups ahead of
+    // the conversations: 318 us per minibatch against 306 with k_prep as its own launch)
+    p.merge_prep = s.sw_merge_prep && fam == FAM_FAST && s.prep_smem <= fast3_lds_bytes() && p.nprep_hx + d.B <= s.n_cu;
+    p.fwd_basehx = fam == FAM_FAST && d.use_binary && s.merge_roles;
+    const bool wide = fam == FAM_FAST && d.V != 100;
+    p.fast_fn = wide ? (p.merge_prep ? k_conversation_fast3<256, 32, 64, 0, true> : k_conversation_fast3<256, 32, 64, 0, false>)
+                     : (p.merge_prep ? k_conversation_fast3<256, 32, 64, 100, true> : k_conversation_fast3<256, 32, 64, 100, false>);
+    p.conv_fn = s.conv_threads == 512 ? k_conversation<512> : k_conversation<256>;
+    p.conv_name = wide ? "k_conversation_wv" : "k_conversation";
+    p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
+    // ---- baselines (training minibatch that did not run all rows) ----
+    // Fused step: the baselines' live-row pass (k_baselines3's body) as workgroup roles of the backward launch, beside the sample
+    // roles' statistics-independent prologue (kernels_fast.h) -- one launch less.  (The sample and statistics roles of that launch
+    // sit ahead of these producers and spin: only with CUs to spare.  Adaptive conversations only: Fixed mode keeps all 640 rows
+    // live and the backward kernel holds ONE workgroup per CU -- measured at config 3: 101.3 us per minibatch with the roles
+    // against 94.6 with k_baselines3 as its own launch; config 2: 66.0 against 72.1.)  Phased step: as roles of mmg_loss_stats'
+    // launch, beside the statistics roles that consume their scores (k_bas_stats) -- one launch less before the statistics all-reduce
+    const bool bas_roles_ok = p.fwd_basehx && d.B <= 64 && (d.K + 63) / 64 <= 8 && s.sw_merge_bas;
+    p.bas_defer_ok = bas_roles_ok && !d.fixed && s.n_cu >= 2 * (d.B + p.n_stats);
+    p.bas_pending_ok = bas_roles_ok && s.n_cu >= 2 * p.n_stats;
+    // any message / state width on the tiles: basehx as a GEMM launch, then one MFMA pass over the live rows (kernels_tile.h); register-resident agents:
+    // k_baselines3 over the live (step, sample) rows; else every row (grid.z = 2 baselines x 2 step ranges: 128 workgroups at config 1 instead of 64)
+    p.bas_kernel = (fam == FAM_TILE && d.B <= 64 && !(d.H & 3)) ? BAS_TILE4 : (p.fwd_basehx && d.B <= 64) ? BAS_LIVE3 : BAS_ALL2;
+    p.bas2_z = 2 * (d.T >= 4 ? 2 : 1);
+    // ---- backward ----
+    p.n_rowblk = sample_tiles(TB);
+    p.n_hbands = (d.H + 63) / 64;
+    p.dhx_blk = (d.B * (d.H / 4) + MMG_BLOCK - 1) / MMG_BLOCK;
+    p.dhx_grid = p.dhx_blk + (d.H / 4 + 63) / 64;
+    if (fam == FAM_TILE) {
+        p.row_map = TB <= 2048;   // k_wgrad keeps the live-row list in LDS (2048 entries)
+        p.zero_dead = !p.row_map && !d.fixed;
+        // the sender's backward rides in the same launch as k_bwd_pre (independent latency chains side by side) while the row
+        // blocks are few: it then walks all T * B rows instead of the live-row list (MMG_NO_MERGE=1: separate launches)
+        p.merged_send = d.use_binary && s.merge_roles && TB <= 2048;
+        const bool rc = s.rc_fwd && s.rc_bwd;
+        // wide receiver whose reverse-time loop runs as roles (k_rc_bwd adds the partials): four column bands per (step, tile)
+        p.pre_bands = (p.merged_send && rc && d.R == 256) ? 4 : 1;
+        p.n_pre = d.T * tiles * p.pre_bands;
+        p.pre_smem = bwd_pre_lds_floats(d) * 4;
+        if (p.merged_send && s.send_bwd_smem > p.pre_smem) p.pre_smem = s.send_bwd_smem;
+        if (p.merged_send) p.pre_send_fn = d.R <= 128 ? k_bwd_pre_send<8> : k_bwd_pre_send<16>;
+        else if (d.use_binary) p.pre_fn = d.R <= 128 ? k_bwd_pre<8> : k_bwd_pre<16>;
+        // receiver shape of the register-resident kernels: one workgroup per sample; else the tile's recurrence with 2 / 4 / 8
+        // tape registers per thread, or the wide receiver's reverse-time loop as roles over 16-unit slices (kernels_rc.h)
+        p.bwd_rec = s.rs_capable ? BR_SAMPLE : (d.R > 128 && rc) ? BR_RC : BR_TILE;
+        p.bwd_tile_fn = d.R <= 64 ? k_bwd_tile<512, 2> : d.R <= 128 ? k_bwd_tile<512, 4> : k_bwd_tile<512, 8>;
+        p.send_own = !p.merged_send;
+        p.dhx_own = !(p.bwd_rec == BR_SAMPLE && p.merged_send);     // (k_bwd_sample carries k_dhx's blocks when the sender's backward already ran)
+        const int RL = d.R < MMG_BLOCK ? d.R : MMG_BLOCK, CPB = MMG_BLOCK / RL;
+        p.dc = DC_TILE;
+        p.dc_grid = (d.D + CPB - 1) / CPB;
+        p.dc_slices = dc_slices(d.B);
+    } else if (mc_bwd(h)) {
+        // one sample tile per workgroup up to 16 groups (measured at 256 samples: 4 groups 26 us, 8: 15, 16: 10)
+        p.mc_ngroup = p.mc_ntile > 16 ? 16 : p.mc_ntile;
+        p.mc_nred = (2 * d.D * d.R / 4 + MMG_BLOCK - 1) / MMG_BLOCK;
+    } else {
+        const bool fast = fam == FAM_FAST, merge_dc = fast && s.merge_roles;
+        p.row_map = merge_dc && TB <= 2048;   // class role 0 lists the live (step, sample) rows for k_wgrad
+        p.zero_dead = !p.row_map;
+        // k_conversation_fast3 stores softmax rows, not dbar = softmax(y) . desc: trailing workgroups form it (16 rows each); class roles: k_dC's work inside the launch
+        p.n_dbar = (fast && d.use_binary) ? (TB + 15) / 16 : 0;
+        p.n_class = merge_dc ? d.D : 0;
+        if (fast) {
+            p.bwd_fast_stats_fn = bwd_conv_fast_fn<true, true>(d.D, d.V);
+            p.bwd_fast_fn = merge_dc ? bwd_conv_fast_fn<false, true>(d.D, d.V) : bwd_conv_fast_fn<false, false>(d.D, d.V);
+        }
+        p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true> : k_bwd_conv<false>;
+        p.dc = merge_dc ? DC_NONE : DC_PLAIN;
+    }
+}
+
+#ifdef MMG_DEBUG_CREATE                                  // (compile with -DMMG_DEBUG_CREATE: what select_paths decided)
+static void print_plan(const mmg_handle* h, int wgrad_resident) {
+    const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    fprintf(stderr, "mmg_create: family %d (0 fast, 1 mc, 2 tile, 3 generic) no_roles %d n_cu %d game_ok %d game_nbas %d wgrad_stride %d (gemm tiles %d) wgrad_opt_ok %d (blocks %d, resident %d x %d)\n",
+            (int)s.family, (int)h->no_roles, s.n_cu, (int)s.game_ok, s.game_nbas, s.wgrad_stride, h->jt.gemm_tiles, (int)s.wgrad_opt_ok, h->jt.n_wblocks + 5, wgrad_resident, s.n_cu);
+    fprintf(stderr, "mmg_create: tile_ok %d tile_nt %d tile_smem %d tile_ext %d tile_persist %d persist_smem %d resident_budget %d tile_bwd_smem %d bwd_pre %d send_bwd %d split %d mc %d fast %d rc %d rc_persist %d rc_budget %d rc_bwd %d\n",
+            (int)s.tile_ok, s.tile_nt, s.tile_smem, (int)s.tile_ext, (int)s.tile_persist, s.persist_smem, s.resident_budget, s.tile_bwd_smem,
+            bwd_pre_lds_floats(h->dm) * 4, s.send_bwd_smem, (int)s.tile_split, (int)s.mc_ok, (int)s.use_fast, (int)s.rc_fwd, (int)s.rc_persist, s.rc_budget, (int)s.rc_bwd);
+    fprintf(stderr, "mmg_create: tile forward %d (0 split, 1 whole, 2 persist/sample, 3 persist/tile, 4 rc persist, 5 rc step, 6 step) rsample %d ns1 %d ns2 %d roles per tile %d tiles per launch %d launches %d basehx rides %d skip %d\n",
+            (int)p.tile_fwd, p.rsample, p.ns1, p.ns2, p.chunk_roles, p.chunk_tiles, p.n_chunk, (int)p.basehx_rides, (int)p.skip_ok);
+    fprintf(stderr, "mmg_create: mc grid %d xcd %d mc3 %d mc3p %d wins %d grid %d | merge_prep %d nprep %d fwd_basehx %d | baselines: defer %d pending %d kernel %d (0 tile4, 1 live3, 2 all2)\n",
+            p.mc_grid, s.mc_xcd, (int)s.mc3_ok, (int)s.mc3p_ok, (int)p.mc3p_wins, p.mc3p_grid, (int)p.merge_prep, p.nprep_hx, (int)p.fwd_basehx, (int)p.bas_defer_ok, (int)p.bas_pending_ok, (int)p.bas_kernel);
+    fprintf(stderr, "mmg_create: backward: row_map %d zero_dead %d merged_send %d pre_bands %d receiver %d (0 sample, 1 tile, 2 rc) n_dbar %d class roles %d k_dC %d (0 none, 1 tile, 2 plain) mc groups %d\n",
+            (int)p.row_map, (int)p.zero_dead, (int)p.merged_send, p.pre_bands, (int)p.bwd_rec, p.n_dbar, p.n_class, (int)p.dc, p.mc_ngroup);
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create and again when the library
@@ -48,9 +203,7 @@ static bool merge_stats(const mmg_handle* h) {
 // cannot hold the role launches, or MMG_NO_ROLES=1).  Environment switches are read here only -- never on the per-minibatch path.
 // ---------------------------------------------------------------------------------------------
 static int select_paths(mmg_handle* h) {
-    const mmg_config& cfg = h->cfg;
-    const Dims& d = h->dm;
-    const bool no_roles = h->no_roles;
+    const mmg_config& cfg = h->cfg; const Dims& d = h->dm; const bool no_roles = h->no_roles;
     h->sel = Selection();
     Selection& s = h->sel;
     s.use_fast = !getenv("MMG_NO_FAST"); s.merge_roles = !getenv("MMG_NO_MERGE") && !no_roles;
@@ -79,10 +232,10 @@ static int select_paths(mmg_handle* h) {
         const int total = nb * n_cu;
         return total - (total + 15) / 16;
     };
-    // raises a kernel's dynamic LDS limit; e keeps the first error (reported once, below)
+    // raises the dynamic LDS limit of the kernels named after `bytes`; e keeps the first error (reported once, below)
     hipError_t e = hipSuccess;
-    auto raise_lds = [&](const void* fn, int bytes) {
-        if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    auto raise_lds = [&](int bytes, auto... fns) {
+        for (const void* fn : {(const void*)fns...}) if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     };
     s.n_cu = n_cu;
     // few samples and large sender matrices or class tables: 512-thread variant of the generic conversation kernel
@@ -131,7 +284,7 @@ static int select_paths(mmg_handle* h) {
             const int a = tile_lds(d, 512 / 64, true, s.split_per).total * 4, b = helper_lds(d, 512 / 64, s.split_per).total * 4;
             s.split_smem = a > b ? a : b;
             if (s.split_smem > 160 * 1024) s.tile_split = false;
-            else raise_lds((const void*)k_conv_split<512>, s.split_smem);
+            else raise_lds(s.split_smem, k_conv_split<512>);
             if (s.tile_split && e == hipSuccess) {
                 s.split_budget = budget_of((const void*)k_conv_split<512>, 512, s.split_smem);
                 if (tiles * (1 + s.split_nh) > s.split_budget) s.tile_split = false;     // not all co-resident here: k_conv_tile instead
@@ -149,11 +302,7 @@ static int select_paths(mmg_handle* h) {
             const int a = tile_lds(d, 512 / 64, false).total * 4, b = srole_lds(d, 512 / 64).total * 4;
             s.persist_smem = a > b ? a : b;
             if (s.persist_smem > 160 * 1024) s.tile_persist = false;
-            else {
-                raise_lds((const void*)k_conv_persist<512, true>, s.persist_smem);
-                raise_lds((const void*)k_conv_persist<512, false>, s.persist_smem);
-                raise_lds((const void*)k_conv_persist<512, true, true>, s.persist_smem);
-            }
+            else raise_lds(s.persist_smem, k_conv_persist<512, true>, k_conv_persist<512, false>, k_conv_persist<512, true, true>);
             if (s.tile_persist && e == hipSuccess) {
                 s.resident_budget = rs_capable ? budget_of((const void*)k_conv_persist<512, true>, 512, s.persist_smem)
                                                : budget_of((const void*)k_conv_persist<512, false>, 512, s.persist_smem);
@@ -167,20 +316,10 @@ static int select_paths(mmg_handle* h) {
         s.send_bwd_smem = (MMG_TM * ld16(d.W) + 7 * 64 + 16 + tile_raw_floats_nn(64, MMG_BLOCK / 64)) * 4;
         if (s.tile_bwd_smem > 160 * 1024 || d.W > 256 || d.R > 256) s.tile_ok = false;     // (k_bwd_tile keeps a step's GRU tape in 4 registers per thread per 32 hidden units)
         const int pre_smem = bwd_pre_lds_floats(d) * 4, pre_send_smem = pre_smem > s.send_bwd_smem ? pre_smem : s.send_bwd_smem;
-        if (s.tile_ok && s.tile_bwd_smem > 48 * 1024) {
-            raise_lds((const void*)k_bwd_tile<512, 2>, s.tile_bwd_smem);
-            raise_lds((const void*)k_bwd_tile<512, 4>, s.tile_bwd_smem);
-            raise_lds((const void*)k_bwd_tile<512, 8>, s.tile_bwd_smem);
-        }
-        if (s.tile_ok && pre_smem > 48 * 1024) {
-            raise_lds((const void*)k_bwd_pre<8>, pre_smem);
-            raise_lds((const void*)k_bwd_pre<16>, pre_smem);
-        }
-        if (s.tile_ok && s.send_bwd_smem > 48 * 1024) raise_lds((const void*)k_send_bwd, s.send_bwd_smem);
-        if (s.tile_ok && pre_send_smem > 48 * 1024) {
-            raise_lds((const void*)k_bwd_pre_send<8>, pre_send_smem);
-            raise_lds((const void*)k_bwd_pre_send<16>, pre_send_smem);
-        }
+        if (s.tile_ok && s.tile_bwd_smem > 48 * 1024) raise_lds(s.tile_bwd_smem, k_bwd_tile<512, 2>, k_bwd_tile<512, 4>, k_bwd_tile<512, 8>);
+        if (s.tile_ok && pre_smem > 48 * 1024) raise_lds(pre_smem, k_bwd_pre<8>, k_bwd_pre<16>);
+        if (s.tile_ok && s.send_bwd_smem > 48 * 1024) raise_lds(s.send_bwd_smem, k_send_bwd);
+        if (s.tile_ok && pre_send_smem > 48 * 1024) raise_lds(pre_send_smem, k_bwd_pre_send<8>, k_bwd_pre_send<16>);
         if (!s.tile_ok) s.rc_fwd = false;
         if (s.rc_fwd && e == hipSuccess)
             s.rc_bwd = tiles <= 64 && tiles * (d.R / 16) <= budget_of((const void*)k_rc_bwd, 256, 0) && !getenv("MMG_NO_RC_BWD") && !no_roles;
@@ -191,10 +330,7 @@ static int select_paths(mmg_handle* h) {
             const int ct = s.rc_budget / rc_roles_per_tile(d);
             s.rc_persist = !(d.H & 15) && d.H <= 1024 && tiles <= 15 && ct >= 1 && (tiles + ct - 1) / ct <= 2 && !getenv("MMG_NO_RC_PERSIST") && !no_roles;
         }
-        if (s.tile_ok && s.tile_smem > 48 * 1024 && !s.rc_fwd) {
-            raise_lds((const void*)k_conv_tile<256>, s.tile_smem);
-            raise_lds((const void*)k_conv_tile<512>, s.tile_smem);
-        }
+        if (s.tile_ok && s.tile_smem > 48 * 1024 && !s.rc_fwd) raise_lds(s.tile_smem, k_conv_tile<256>, k_conv_tile<512>);
     }
     if (s.mc_ok) {
         // k_conversation_mc's 16 workgroups per tile spin on each other: with the per-XCD mapping a tile's members are 16 of 128
@@ -205,29 +341,25 @@ static int select_paths(mmg_handle* h) {
         if (mc_budget < 16) s.mc_ok = false;
         s.mc3_ok = s.mc_ok && !d.use_binary;
         if (s.mc3_ok) {
-            raise_lds((const void*)(k_conversation_mc3<256, 32, 64, 100, 64>), mc3_lds_bytes());
+            raise_lds(mc3_lds_bytes(), k_conversation_mc3<256, 32, 64, 100, 64>);
             const int b3 = budget_of((const void*)(k_conversation_mc3<256, 32, 64, 100, 64>), 256, mc3_lds_bytes());
             if (b3 < (s.mc_xcd ? 128 : 16)) s.mc3_ok = false;
             // two tiles per workgroup (kernels_mc3p.h): from 512 samples on, where the one-tile kernel needs several rounds of workgroups
             if (s.mc3_ok && s.mc_xcd && mc3p_shape(d.B, d.T, d.D) && !getenv("MMG_NO_MC3P")) {
-                raise_lds((const void*)(k_conversation_mc3p<256, 32, 64, 100, 64>), mc3p_lds_bytes(d.T));
+                raise_lds(mc3p_lds_bytes(d.T), k_conversation_mc3p<256, 32, 64, 100, 64>);
                 s.mc3p_ok = e == hipSuccess && budget_of((const void*)(k_conversation_mc3p<256, 32, 64, 100, 64>), 256, mc3p_lds_bytes(d.T)) >= 128;
             }
         }
     }
-    raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 100, false>), fast3_lds_bytes());
-    raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 100, true>), fast3_lds_bytes());
-    if (fast_wide_v(d.V)) {
-        raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 0, false>), fast3_lds_bytes());
-        raise_lds((const void*)(k_conversation_fast3<256, 32, 64, 0, true>), fast3_lds_bytes());
-    }
+    raise_lds(fast3_lds_bytes(), k_conversation_fast3<256, 32, 64, 100, false>, k_conversation_fast3<256, 32, 64, 100, true>);
+    if (fast_wide_v(d.V)) raise_lds(fast3_lds_bytes(), k_conversation_fast3<256, 32, 64, 0, false>, k_conversation_fast3<256, 32, 64, 0, true>);
     {
         const bool shape = s.use_fast && s.merge_roles && s.sw_merge_prep && s.sw_merge_bas && d.H == 256 && d.W == 32 && d.R == 64 && d.V == 100 &&
                            d.D <= 32 && d.T <= 15 && d.B <= 64 && d.use_binary && !d.fixed && (d.K + 63) / 64 <= 8 && d.K <= 512 &&
                            !(s.tile_ok && s.tile_force) && s.prep_cpb == 1 && s.prep_smem <= game_lds_bytes() && !getenv("MMG_NO_GAME") && !no_roles;
         if (shape && e == hipSuccess) {
             const void* fn = (const void*)game_fast_fn(d.D);
-            raise_lds(fn, game_lds_bytes());
+            raise_lds(game_lds_bytes(), fn);
             if (e == hipSuccess) {
                 // every spinning role must be resident together with the sample roles (the sample roles wait for the statistics roles,
                 // those for the baseline roles): B + n_stats + n_bas + D workgroups inside the co-residency budget of this device
@@ -242,25 +374,14 @@ static int select_paths(mmg_handle* h) {
             }
         }
     }
-#ifdef MMG_DEBUG_CREATE                                  // (compile with -DMMG_DEBUG_CREATE: what select_paths decided)
-    fprintf(stderr, "mmg_create: game_ok %d game_nbas %d\n", (int)s.game_ok, s.game_nbas);
-    fprintf(stderr, "mmg_create: tile_ok %d tile_nt %d tile_smem %d tile_ext %d tile_persist %d persist_smem %d resident_budget %d tile_bwd_smem %d bwd_pre %d send_bwd %d split %d mc %d fast %d rc %d rc_persist %d rc_budget %d rc_bwd %d\n",
-            (int)s.tile_ok, s.tile_nt, s.tile_smem, (int)s.tile_ext, (int)s.tile_persist, s.persist_smem, s.resident_budget, s.tile_bwd_smem,
-            bwd_pre_lds_floats(d) * 4, s.send_bwd_smem, (int)s.tile_split, (int)s.mc_ok, (int)s.use_fast, (int)s.rc_fwd, (int)s.rc_persist, s.rc_budget, (int)s.rc_bwd);
-#endif
-    if (s.conv_smem > 48 * 1024) {
-        raise_lds((const void*)k_conversation<256>, s.conv_smem);
-        raise_lds((const void*)k_conversation<512>, s.conv_smem);
-    }
-    if (s.bwd_smem > 48 * 1024) {
-        raise_lds((const void*)k_bwd_conv<false>, s.bwd_smem);
-        raise_lds((const void*)k_bwd_conv<true>, s.bwd_smem);
-    }
+    if (s.conv_smem > 48 * 1024) raise_lds(s.conv_smem, k_conversation<256>, k_conversation<512>);
+    if (s.bwd_smem > 48 * 1024) raise_lds(s.bwd_smem, k_bwd_conv<false>, k_bwd_conv<true>);
     if (e != hipSuccess) return fail("device init failed: %s", hipGetErrorString(e));
-    if (plan_jobs(h, tile_path(h) ? CODE_BIAS_TILE : fast_shape(h) ? CODE_BIAS_FAST : CODE_BIAS_GENERIC)) return -1;
+    s.family = select_family(s, d);
+    if (plan_jobs(h, s.family == FAM_TILE ? CODE_BIAS_TILE : s.family == FAM_FAST ? CODE_BIAS_FAST : CODE_BIAS_GENERIC)) return -1;
+    int nb = 0;
     {
         // the optimizer inside k_wgrad: its blocks spin on the norm role of the same launch, so ALL of them must be resident together
-        int nb = 0;
         s.wgrad_opt_ok = !s.any_split && d.use_binary && h->d_err != nullptr && !getenv("MMG_NO_WGRAD_OPT") && !no_roles &&
                          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_wgrad<true>, MMG_BLOCK, 0) == hipSuccess &&
                          h->jt.n_wblocks + 5 <= nb * n_cu - 8;
@@ -273,15 +394,18 @@ static int select_paths(mmg_handle* h) {
             //  a balanced stride (tiles / rounds) gave the gain away again: as many workgroups as are resident)
             if (h->jt.gemm_tiles > slots && slots >= 64 && h->jt.gemm_tiles <= 6 * slots) s.wgrad_stride = slots;
         }
-#ifdef MMG_DEBUG_CREATE
-        fprintf(stderr, "mmg_create: wgrad_stride %d (gemm tiles %d)\n", s.wgrad_stride, h->jt.gemm_tiles);
-        fprintf(stderr, "mmg_create: wgrad_opt_ok %d (blocks %d, resident %d x %d)\n", (int)s.wgrad_opt_ok, h->jt.n_wblocks + 5, nb, n_cu);
-#endif
     }
+    plan_launches(h);
+#ifdef MMG_DEBUG_CREATE
+    print_plan(h, nb);
+#endif
     if (no_roles) {
         // nothing that spins on another workgroup of its own launch: per-step / per-phase launches only
-        //   (MMG_NO_MERGE + MMG_NO_MERGE_PREP + MMG_NO_GAME + MMG_NO_WGRAD_OPT + MMG_NO_PERSIST + MMG_NO_SPLIT + MMG_NO_MC + MMG_NO_RC_PERSIST + MMG_NO_RC_BWD)
-        if (s.game_ok || s.wgrad_opt_ok || s.tile_persist || s.tile_split || s.mc_ok || s.rc_persist || s.rc_bwd || s.merge_roles || s.sw_merge_prep)
+        //   (MMG_NO_MERGE + MMG_NO_MERGE_PREP + MMG_NO_GAME + MMG_NO_WGRAD_OPT + MMG_NO_PERSIST + MMG_NO_SPLIT + MMG_NO_MC + MMG_NO_RC_PERSIST + MMG_NO_RC_BWD) -- in the switches and in every role launch of the plan
+        const LaunchPlan& p = s.plan; const TileFwd tf = p.tile_fwd;
+        if (s.game_ok || s.wgrad_opt_ok || s.tile_persist || s.tile_split || s.mc_ok || s.rc_persist || s.rc_bwd || s.merge_roles || s.sw_merge_prep ||
+            s.family == FAM_MC || tf == TF_SPLIT || tf == TF_PERSIST_SAMPLE || tf == TF_PERSIST_TILE || tf == TF_RC_PERSIST || p.basehx_rides ||
+            p.merge_prep || p.fwd_basehx || p.bas_defer_ok || p.bas_pending_ok || p.merged_send || p.bwd_rec == BR_RC || p.n_class)
             return fail("internal: a role launch survived the no-roles selection");
     }
     return 0;

@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -40,9 +41,9 @@ static int fail(const char* fmt, ...) {
     do { hipError_t e_ = (expr);                                                          \
          if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
-#include "host_launch.h"       // the handle, Scope, launch helpers shared between entry points
+#include "host_launch.h"       // the handle with its Selection and LaunchPlan, Scope, launch helpers shared between entry points
 #include "host_jobs.h"         // k_wgrad's job tables
-#include "host_select.h"       // launch geometry, path predicates, select_paths
+#include "host_select.h"       // launch geometry, select_paths: capabilities, family, launch plan
 
 // ---------------------------------------------------------------------------------------------
 // Fail-soft (round 6).  An in-launch dependency wait that hits its spin bound (fewer compute units than the launch's roles
@@ -283,250 +284,156 @@ static int launch_baselines_fused(mmg_handle* h, hipStream_t st) {
     return launch_check("k_baselines");
 }
 
+// The whole-conversation launch arguments every forward starts from (the fused step included)
+static ConvArgs conv_args(const mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, const float* d_u_z,
+                          const float* d_u_s, const float* d_u_w, uint64_t seed, int train, int run_all) {
+    ConvArgs ar; memset(&ar, 0, sizeof(ar));
+    ar.x = d_x; ar.target = d_target; ar.desc = d_desc; ar.u_z = d_u_z; ar.u_s = d_u_s; ar.u_w = d_u_w; ar.seed = seed;
+    ar.train = train; ar.run_all = run_all; ar.t_begin = 0; ar.t_end = h->dm.T; ar.phases = 3; ar.sprod_first = 1;
+    return ar;
+}
+
+// FAM_TILE: one of the plan's seven outcomes (host_select.h: plan_launches).  The outcome is known BEFORE a timing scope opens.
 static int launch_conv_tile(mmg_handle* h, hipStream_t st, ConvArgs ar) {
-    const Dims& d = h->dm;
-    const int tiles = sample_tiles(d.B);
-    auto conv = [&](const ConvArgs& a) {
-        if (h->sel.tile_nt == 512) hipLaunchKernelGGL(k_conv_tile<512>, dim3(tiles), dim3(512), h->sel.tile_smem, st, h->dm, h->P, h->tp, a);
-        else hipLaunchKernelGGL(k_conv_tile<256>, dim3(tiles), dim3(256), h->sel.tile_smem, st, h->dm, h->P, h->tp, a);
-    };
-    if (h->sel.tile_split) {
+    const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    const int tiles = p.tiles, free_run = (ar.train && !ar.run_all) ? 1 : 0;
+    const int bt = (p.basehx_rides && free_run) ? p.basehx_tiles : 0; const int skip = (p.skip_ok && free_run) ? 1 : 0;   // bt: basehx tiles for k_baselines4 as trailing workgroups
+    ar.ns1 = p.ns1; ar.ns2 = p.ns2; ar.rsample = p.rsample;
+    switch (p.tile_fwd) {
+    case TF_SPLIT: {
         Scope sc(h, st, "k_conv_split");
-        ar.phases = 3; ar.t_begin = 0; ar.t_end = d.T; ar.nhelp = h->sel.split_nh; ar.per = h->sel.split_per;
-        hipLaunchKernelGGL(k_conv_split<512>, dim3(tiles * (1 + ar.nhelp)), dim3(512), h->sel.split_smem, st, h->dm, h->P, h->tp, ar, tiles);
+        ar.nhelp = s.split_nh; ar.per = s.split_per;
+        hipLaunchKernelGGL(k_conv_split<512>, dim3(tiles * (1 + ar.nhelp)), dim3(512), s.split_smem, st, h->dm, h->P, h->tp, ar, tiles);
         return launch_check("k_conv_split");
     }
-    if (!h->sel.tile_ext) {
+    case TF_WHOLE: {
         Scope sc(h, st, "k_conv_tile");
-        ar.phases = 3; ar.t_begin = 0; ar.t_end = d.T;
-        conv(ar);
+        hipLaunchKernelGGL(p.conv_tile_fn, dim3(tiles), dim3(s.tile_nt), s.tile_smem, st, h->dm, h->P, h->tp, ar);
         return launch_check("k_conv_tile");
     }
-    if (h->sel.tile_persist) {
-        ar.phases = 2; ar.t_begin = 0; ar.t_end = d.T; ar.persist = 1; ar.ns1 = h->sel.persist_ns1; ar.ns2 = h->sel.persist_ns2;
-        // receiver shape of the register-resident kernels: one receiver role per SAMPLE (rs_role) beside the tiles' sender roles
-        ar.rsample = (h->sel.rs_capable) ? 1 : 0;
-        if (ar.rsample && d.W == 256 && h->sel.sw_rmsg) ar.rsample = 2;      // ... which also form the receiver's message
-        if (ar.rsample == 2 && d.H % 64 == 0 && d.H / 64 <= 16 && h->sel.sw_fused_s) {
-            ar.rsample = 3;                                 // fused sender roles (sa_role / sb_role)
-            ar.ns1 = d.H / 64; ar.ns2 = d.W / 16;
+    case TF_PERSIST_SAMPLE: case TF_PERSIST_TILE: {
+        Scope sc(h, st, "k_conv_persist");
+        ar.phases = 2; ar.persist = 1;
+        const int span = p.chunk_tiles * MMG_TM;
+        if (p.tile_fwd == TF_PERSIST_TILE)               // every tile's roles in one launch
+            hipLaunchKernelGGL(p.persist_fn, dim3(tiles * p.chunk_roles), dim3(512), s.persist_smem, st, h->dm, h->P, h->tp, ar, tiles);
+        else for (int c = 0; c < p.n_chunk && c * span < d.B; ++c) {      // per-sample receiver roles: consecutive launches over sample ranges
+            ar.b_begin = c * span; ar.b_count = std::min(d.B - ar.b_begin, span);
+            hipLaunchKernelGGL(p.persist_fn, dim3(ar.b_count + sample_tiles(ar.b_count) * (ar.ns1 + ar.ns2) + bt), dim3(512), s.persist_smem, st, h->dm, h->P, h->tp, ar, tiles);
         }
-        // all roles of a launch must be co-resident (resident_budget workgroups, occupancy query at mmg_create): as many whole
-        // tiles per launch as fit, the batch in consecutive launches (the conversations of different samples are independent).
-        // The path is chosen BEFORE the timing scope opens (a fall-back to the per-step launches leaves no empty timer).
-        const int per_tile = MMG_TM + ar.ns1 + ar.ns2;
-        int ct = h->sel.resident_budget / per_tile;
-        if (ct < 1) ct = 1;
-        const int nchunk = (tiles + ct - 1) / ct;
-        ct = (tiles + nchunk - 1) / nchunk;
-        // (measured with config 4's agents: 256 samples in 4 launches 471 us against 858 us as per-step launches; 1024 samples
-        //  in 13 launches 1 723 against 1 544 -- beyond six launches the per-step GEMM launches over the whole batch win)
-        const bool sample_roles = ar.rsample && nchunk <= 6 && per_tile <= h->sel.resident_budget;
-        const bool tile_roles = !ar.rsample && tiles * (1 + ar.ns1 + ar.ns2) <= h->sel.resident_budget;
-        if (sample_roles) {
-            Scope sc(h, st, "k_conv_persist");
-            const bool want_base = basehx_rides(d, nchunk, ar.train, ar.run_all, h->sel.merge_roles);
-            const int bt = want_base ? basehx_tiles(d) : 0;
-            for (int c = 0; c < nchunk; ++c) {
-                ar.b_begin = c * ct * MMG_TM;
-                ar.b_count = (d.B - ar.b_begin < ct * MMG_TM) ? d.B - ar.b_begin : ct * MMG_TM;
-                if (ar.b_count <= 0) break;
-                const int ctiles = sample_tiles(ar.b_count);
-                if (ar.rsample == 3 && h->sel.persist_ll)
-                    hipLaunchKernelGGL((k_conv_persist<512, true, true>), dim3(ar.b_count + ctiles * (ar.ns1 + ar.ns2) + bt), dim3(512), h->sel.persist_smem, st, h->dm, h->P, h->tp, ar, tiles);
-                else
-                hipLaunchKernelGGL((k_conv_persist<512, true>), dim3(ar.b_count + ctiles * (ar.ns1 + ar.ns2) + bt), dim3(512), h->sel.persist_smem, st, h->dm, h->P, h->tp, ar, tiles);
+        h->fwd.basehx_ready = bt > 0;
+        return launch_check("k_conv_persist");
+    }
+    case TF_RC_PERSIST: case TF_RC_STEP: {
+        Scope sc(h, st, "k_conv_rc");
+        ar.phases = 2;
+        if (p.tile_fwd == TF_RC_PERSIST) {               // all roles co-resident: up to two consecutive launches over tile ranges
+            for (int t0 = 0; t0 < tiles; t0 += p.chunk_tiles) {
+                const int nt = std::min(tiles - t0, p.chunk_tiles);
+                hipLaunchKernelGGL(k_rc_persist, dim3(nt * p.chunk_roles + bt), dim3(256), 0, st, h->dm, h->P, h->tp, ar, nt, t0);
             }
-            h->fwd.basehx_ready = want_base;
-            return launch_check("k_conv_persist");
+            h->fwd.basehx_ready = bt > 0;
+            return launch_check("k_rc_persist");
         }
-        if (tile_roles) {
-            Scope sc(h, st, "k_conv_persist");
-            const int roles = 1 + ar.ns1 + ar.ns2;
-            hipLaunchKernelGGL((k_conv_persist<512, false>), dim3(tiles * roles), dim3(512), h->sel.persist_smem, st, h->dm, h->P, h->tp, ar, tiles);
-            return launch_check("k_conv_persist");
-        }
-    }
-    // per-step launches: no co-residency needed (any device, any batch)
-    ar.persist = 0; ar.rsample = 0;
-    const int skip = (!ar.run_all && !d.fixed && ar.train) ? 1 : 0;
-    if (h->sel.rc_fwd && h->sel.rc_persist) {
-        // wide receiver, all roles co-resident: one launch for the whole conversation (kernels_rc.h: k_rc_persist)
-        Scope sc(h, st, "k_conv_rc");
-        const int per_tile = rc_roles_per_tile(d);
-        ar.phases = 2;
-        int ct = h->sel.rc_budget / per_tile;
-        const int nchunk = (tiles + ct - 1) / ct;
-        ct = (tiles + nchunk - 1) / nchunk;
-        const bool want_base = basehx_rides(d, nchunk, ar.train, ar.run_all, h->sel.merge_roles);
-        const int bt = want_base ? basehx_tiles(d) : 0;
-        for (int c = 0; c < nchunk; ++c) {
-            const int t0 = c * ct, nt = (tiles - t0 < ct) ? tiles - t0 : ct;
-            if (nt <= 0) break;
-            hipLaunchKernelGGL(k_rc_persist, dim3(nt * per_tile + bt), dim3(256), 0, st, h->dm, h->P, h->tp, ar, nt, t0);
-        }
-        h->fwd.basehx_ready = want_base;
-        return launch_check("k_rc_persist");
-    }
-    if (h->sel.rc_fwd) {
-        // wide receiver: the receiver step of a tile as three launches over 16-unit / 16-bit slices (kernels_rc.h)
-        Scope sc(h, st, "k_conv_rc");
-        const int nj = d.R / 16, njw = d.W / 16;
-        ar.phases = 2;
-        for (int t = 0; t < d.T; ++t) {
-            hipLaunchKernelGGL(k_send_s1, dim3(tiles * ((d.H + 15) / 16)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, t, skip);
-            hipLaunchKernelGGL(k_send_s2, dim3(tiles * ((d.W + 15) / 16)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ar, t, skip);
-            hipLaunchKernelGGL(k_rc_gru, dim3(tiles * nj), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
-            hipLaunchKernelGGL(k_rc_heads, dim3(tiles * nj), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
-            hipLaunchKernelGGL(k_rc_query, dim3(tiles * njw), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
+        for (int t = 0; t < d.T; ++t) {                  // the receiver step of a tile as three launches over 16-unit / 16-bit slices
+            hipLaunchKernelGGL(k_send_s1, dim3(p.s1_grid), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, t, skip);
+            hipLaunchKernelGGL(k_send_s2, dim3(p.s2_grid), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ar, t, skip);
+            hipLaunchKernelGGL(k_rc_gru, dim3(tiles * p.rc_nj), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
+            hipLaunchKernelGGL(k_rc_heads, dim3(tiles * p.rc_nj), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
+            hipLaunchKernelGGL(k_rc_query, dim3(tiles * p.rc_njw), dim3(256), 0, st, h->dm, h->P, h->tp, ar, t, skip);
         }
         hipLaunchKernelGGL(k_rc_tail, dim3(tiles), dim3(256), 0, st, h->dm, h->P, h->tp, ar);
         return launch_check("k_conv_rc");
     }
-    for (int t = 0; t < d.T; ++t) {
-        {
-            Scope sc(h, st, "k_send_s1");
-            hipLaunchKernelGGL(k_send_s1, dim3(tiles * ((d.H + 15) / 16)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, t, skip);
-        }
-        {
-            Scope sc(h, st, "k_send_s2");
-            hipLaunchKernelGGL(k_send_s2, dim3(tiles * ((d.W + 15) / 16)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ar, t, skip);
-        }
-        {
-            Scope sc(h, st, "k_conv_tile");
+    case TF_STEP:                                        // per-step launches: no co-residency needed (any device, any batch)
+        for (int t = 0; t < d.T; ++t) {
+            { Scope sc(h, st, "k_send_s1"); hipLaunchKernelGGL(k_send_s1, dim3(p.s1_grid), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, t, skip); }
+            { Scope sc(h, st, "k_send_s2"); hipLaunchKernelGGL(k_send_s2, dim3(p.s2_grid), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ar, t, skip); }
             ar.phases = 2; ar.t_begin = t; ar.t_end = t + 1;
-            conv(ar);
+            { Scope sc(h, st, "k_conv_tile"); hipLaunchKernelGGL(p.conv_tile_fn, dim3(tiles), dim3(s.tile_nt), s.tile_smem, st, h->dm, h->P, h->tp, ar); }
+            if (launch_check("k_conv_tile (step)")) return -1;
         }
-        if (launch_check("k_conv_tile (step)")) return -1;
     }
     return 0;
 }
 
-static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
-                                 const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed,
-                                 int train, int run_all_steps, void* stream, bool defer_bas = false) {
-    // defer_bas (the fused step's forward): the baselines may ride in the backward launch
+// FAM_MC.  lean: the training-minimal continuous pass, the only one the pair kernel serves
+static int launch_conv_mc(mmg_handle* h, hipStream_t st, ConvArgs ar) {
+    const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    Scope sc(h, st, "k_conversation_mc");
+    ar.per = s.mc_per; ar.l2_handoff = (s.mc_xcd && h->xcd_rule_ok) ? 1 : 0;
+    if (p.mc3p_wins && ar.lean)      // two sample tiles per workgroup, half a step apart (kernels_mc3p.h)
+        hipLaunchKernelGGL((k_conversation_mc3p<256, 32, 64, 100, 64>), dim3(p.mc3p_grid), dim3(256), mc3p_lds_bytes(h->dm.T), st, h->dm, h->P, h->tp, ar, p.mc_ntile, ar.y_last_only);
+    else if (s.mc3_ok)
+        hipLaunchKernelGGL((k_conversation_mc3<256, 32, 64, 100, 64>), dim3(p.mc_grid), dim3(256), mc3_lds_bytes(), st, h->dm, h->P, h->tp, ar, p.mc_ntile, s.mc_xcd, ar.y_last_only);
+    else
+        hipLaunchKernelGGL((k_conversation_mc<256, 32, 64, 100, 64>), dim3(p.mc_grid), dim3(512), 0, st, h->dm, h->P, h->tp, ar, p.mc_ntile, s.mc_xcd, ar.y_last_only);
+    return launch_check("k_conversation_mc");
+}
+
+// FAM_FAST (k_conversation_fast3 with its optional prep / basehx roles) and FAM_GENERIC (k_conversation)
+static int launch_conv_sample(mmg_handle* h, hipStream_t st, ConvArgs ar, bool base_ready) {
+    const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    Scope sc(h, st, p.conv_name);
+    if (s.family == FAM_FAST) {
+        ar.nprep = p.merge_prep ? p.nprep_hx : 0; ar.prep_cpb = s.prep_cpb; ar.nbase = base_ready ? p.basehx_tiles : 0;
+        hipLaunchKernelGGL(p.fast_fn, dim3(d.B + ar.nbase + (p.merge_prep ? ar.nprep + 1 : 0)), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
+    } else
+        hipLaunchKernelGGL(p.conv_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar);
+    return launch_check("k_conversation");
+}
+
+// The baselines of a training forward.  all_rows (exchange()): every row, scores materialised directly; else over the live rows --
+// left to the backward launch (fused step) or to k_bas_stats (phased step) where the plan allows, or the plan's standalone kernel
+static int launch_baselines(mmg_handle* h, hipStream_t st, bool all_rows, bool defer_bas, bool base_ready) {
+    const Dims& d = h->dm; const LaunchPlan& p = h->sel.plan;
+    if (all_rows) return launch_baselines_fused(h, st);
+    h->fwd.scores_in_parts = true;
+    if (base_ready && defer_bas && p.bas_defer_ok) { h->fwd.bas_deferred = true; return 0; }
+    if (base_ready && !defer_bas && p.bas_pending_ok) { h->fwd.bas_pending = true; return 0; }
+    Scope sc(h, st, "k_baselines");
+    if (p.bas_kernel == BAS_TILE4 && !h->fwd.basehx_ready)     // basehx did not ride along the conversation: a GEMM launch first
+        hipLaunchKernelGGL(k_gemm_nt, dim3(p.basehx_tiles), dim3(MMG_BLOCK), 0, st, (const float*)h->tp.hx, d.H, (const float*)h->P.p[BS_L1_W], d.H + d.W, (const float*)nullptr, h->tp.basehx, d.K, d.B, d.K, d.H);
+    if (p.bas_kernel == BAS_ALL2)
+        hipLaunchKernelGGL(k_baselines2, dim3((d.B + 15) / 16, (d.K + 63) / 64, p.bas2_z), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, 1, base_ready ? 1 : 0);
+    else
+        hipLaunchKernelGGL(p.bas_kernel == BAS_TILE4 ? k_baselines4 : k_baselines3, dim3((d.T * d.B + 15) / 16, (d.K + 63) / 64, 2), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
+    return launch_check("k_baselines");
+}
+
+// defer_bas (the fused step's forward): the baselines may ride in the backward launch
+static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, const float* d_u_z,
+                                 const float* d_u_s, const float* d_u_w, uint64_t seed, int train, TapeMode mode, void* stream, bool defer_bas = false) {
     if (!d_x || !d_desc) return fail("x / desc must not be NULL");
     hipStream_t st = (hipStream_t)stream;
-    const Dims& d = h->dm;
-    // register-resident forward (k_conversation_fast3): k_prep's blocks run as leading roles of the conversation's launch -- when
-    // every prep and sample role has a CU of its own (the launch holds ONE workgroup per CU: with 512 samples the 531 prep roles would be two
-    // more rounds of workgroups ahead of the conversations: 318 us per minibatch against 306 with k_prep as its own launch)
-    const bool merge_prep = h->sel.sw_merge_prep && !tile_path(h) && !mc_path(h) && fast_shape(h) &&
-                            h->sel.prep_smem <= fast3_lds_bytes() &&
-                            prep_blocks(d, h->sel.prep_cpb, true) + d.B <= h->sel.n_cu;
-    if (!merge_prep && launch_prep(h, st, d_desc, d_x, train ? 1 : 0)) return -1;
-    const bool bas = train && d.use_binary;
-    ConvArgs ar;
-    memset(&ar, 0, sizeof(ar));
-    ar.x = d_x; ar.target = d_target; ar.desc = d_desc; ar.u_z = d_u_z; ar.u_s = d_u_s; ar.u_w = d_u_w; ar.seed = seed;
-    // run_all_steps == 2: training-minimal (as 0; the class logits y[t] of the steps before the output step are not kept)
-    const int y_last_only = (run_all_steps == 2 && d.fixed) ? 1 : 0;
-    const int lean = (run_all_steps == 2 && !d.use_binary) ? 1 : 0;
-    if (run_all_steps == 2) run_all_steps = 0;
-    // run_all_steps == 3 (the minibatches whose log block reads the whole tape): the CONVERSATION runs every sample through all
-    // steps, everything else is the training step's -- the baselines over the live rows only, in the statistics / backward launch
-    // (the log block prints no baseline score; the generic all-rows baselines launch of mode 1 costs 55 us at config 2).
-    // Register-resident agents of a training pass only: other paths take it as mode 1.
-    const bool tape_all = run_all_steps == 3 && train && d.use_binary && fast_shape(h) && !tile_path(h) && !mc_path(h);
-    if (run_all_steps == 3) run_all_steps = tape_all ? 0 : 1;
-    ar.y_last_only = y_last_only; ar.lean = lean;
-    ar.train = train; ar.run_all = (run_all_steps || tape_all) ? 1 : 0; ar.t_begin = 0; ar.t_end = d.T; ar.phases = 3; ar.sprod_first = 1;
-    if (h->corrupt_on) {
-        if (train) return fail("a message corruption mask is set: training conversations are not corrupted (mmg_set_message_corruption(h, NULL, 0) clears it)");
-        ar.corrupt_on = 1;
-        memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt));
-    }
-    bool base_ready = false;
+    const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    if (!p.merge_prep && launch_prep(h, st, d_desc, d_x, train ? 1 : 0)) return -1;
+    if (h->corrupt_on && train) return fail("a message corruption mask is set: training conversations are not corrupted (mmg_set_message_corruption(h, NULL, 0) clears it)");
+    // TAPE_LOG (the minibatches whose log block reads the whole tape): the CONVERSATION runs every sample through all steps, everything else
+    // is the training step's -- the baselines over the live rows only, in the statistics / backward launch (the log block prints no baseline score;
+    // the all-rows baselines launch of TAPE_ALL costs 55 us at config 2).  Register-resident agents of a training pass only: other paths take it as TAPE_ALL.
+    const bool bas = train && d.use_binary, tape_all = mode == TAPE_LOG && bas && s.family == FAM_FAST;
+    const bool all_rows = mode == TAPE_ALL || (mode == TAPE_LOG && !tape_all);
+    ConvArgs ar = conv_args(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, train, (all_rows || tape_all) ? 1 : 0);
+    // TAPE_MINIMAL: as TAPE_TO_STOP, and the class logits y[t] of the steps before the output step are not kept
+    ar.y_last_only = (mode == TAPE_MINIMAL && d.fixed) ? 1 : 0;
+    ar.lean = (mode == TAPE_MINIMAL && !d.use_binary) ? 1 : 0;
+    if (h->corrupt_on) { ar.corrupt_on = 1; memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt)); }
     h->fwd = ForwardState();
-    if (tile_path(h)) {
-        if (launch_conv_tile(h, st, ar)) return -1;
-    } else if (mc_path(h)) {
-        Scope sc(h, st, "k_conversation_mc");
-        const int ntile = (d.B + 15) / 16;
-        ar.per = h->sel.mc_per;
-        ar.l2_handoff = (h->sel.mc_xcd && h->xcd_rule_ok) ? 1 : 0;
-        const int grid = h->sel.mc_xcd ? ((ntile + 7) / 8) * 128 : ntile * 16;     // (mc_xcd assumes the 8 XCDs of an unpartitioned MI355X; mmg_create clears it otherwise)
-        // ... when it needs fewer rounds: a round of 16 pairs takes ~1.55x a round of 16 single tiles (measured, scripts/mc3p_ab.py:
-        // 768 samples = 24 pairs = two rounds lose to three rounds of single tiles, every other multiple of 256 from 512 on wins)
-        const int mc3p_rounds = (((ntile + 1) / 2) + h->sel.n_cu / 16 - 1) / (h->sel.n_cu / 16 > 0 ? h->sel.n_cu / 16 : 1), mc3_rounds = (ntile * 16 + h->sel.n_cu - 1) / h->sel.n_cu;
-        if (h->sel.mc3_ok && h->sel.mc3p_ok && lean && 31 * mc3p_rounds < 20 * mc3_rounds) {
-            // two sample tiles per workgroup, half a step apart (kernels_mc3p.h): 128 consecutive workgroups = 8 pairs of tiles x 16 members
-            const int npair = (ntile + 1) / 2;
-            int nblk = (npair + 7) / 8;                     // blocks of 128 workgroups = 8 pairs x 16 members; one workgroup per CU: the launch is persistent
-            if (nblk > h->sel.n_cu / 128) nblk = h->sel.n_cu / 128 > 0 ? h->sel.n_cu / 128 : 1;
-            hipLaunchKernelGGL((k_conversation_mc3p<256, 32, 64, 100, 64>), dim3(nblk * 128), dim3(256), mc3p_lds_bytes(d.T), st, h->dm, h->P, h->tp, ar, ntile, y_last_only);
-        } else if (h->sel.mc3_ok)
-            hipLaunchKernelGGL((k_conversation_mc3<256, 32, 64, 100, 64>), dim3(grid), dim3(256), mc3_lds_bytes(), st, h->dm, h->P, h->tp, ar, ntile, h->sel.mc_xcd, y_last_only);
-        else
-            hipLaunchKernelGGL((k_conversation_mc<256, 32, 64, 100, 64>), dim3(grid), dim3(512), 0, st, h->dm, h->P, h->tp, ar, ntile, h->sel.mc_xcd, y_last_only);
-        if (launch_check("k_conversation_mc")) return -1;
-    } else {
-        const bool fast = fast_shape(h), wide = fast && d.V != 100;
-        Scope sc(h, st, wide ? "k_conversation_wv" : "k_conversation");
-        base_ready = fast && bas && !run_all_steps && h->sel.merge_roles;
-        const int base_tiles = base_ready ? basehx_tiles(d) : 0;
-        if (fast) {
-            ar.nprep = merge_prep ? prep_blocks(d, h->sel.prep_cpb, true) : 0; ar.prep_cpb = h->sel.prep_cpb; ar.nbase = base_tiles;
-            if (wide && merge_prep) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 0, true>), dim3(ar.nprep + d.B + base_tiles + 1), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
-            else if (wide) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 0, false>), dim3(d.B + base_tiles), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
-            else if (merge_prep) hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 100, true>), dim3(ar.nprep + d.B + base_tiles + 1), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
-            else hipLaunchKernelGGL((k_conversation_fast3<256, 32, 64, 100, false>), dim3(d.B + base_tiles), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
-        }
-        else
-            if (h->sel.conv_threads == 512)
-                hipLaunchKernelGGL(k_conversation<512>, dim3(d.B), dim3(512), h->sel.conv_smem, st, h->dm, h->P, h->tp, ar);
-            else
-                hipLaunchKernelGGL(k_conversation<256>, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem, st, h->dm, h->P, h->tp, ar);
-        if (launch_check("k_conversation")) return -1;
+    const bool base_ready = p.fwd_basehx && bas && !all_rows;
+    switch (s.family) {
+    case FAM_TILE: if (launch_conv_tile(h, st, ar)) return -1; break;
+    case FAM_MC: if (launch_conv_mc(h, st, ar)) return -1; break;
+    default: if (launch_conv_sample(h, st, ar, base_ready)) return -1;
     }
-    if (bas) {
-        if (run_all_steps) {                         // exchange(): every row, scores materialised directly
-            if (launch_baselines_fused(h, st)) return -1;
-        } else if (defer_bas && base_ready && d.B <= 64 && (d.K + 63) / 64 <= 8 && h->sel.sw_merge_bas && !d.fixed &&
-                   h->sel.n_cu >= 2 * (d.B + stat_roles(d.T))) {
-            // fused step, register-resident kernels: the baselines' live-row pass (k_baselines3's body) runs as workgroup roles of
-            // the backward launch, beside the sample roles' statistics-independent prologue (kernels_fast.h) -- one launch less.
-            // (The sample and statistics roles of that launch sit ahead of these producers and spin: only with CUs to spare.
-            //  Adaptive conversations only: with early stopping ~140 of the 640 (step, sample) rows are live = ~144 baseline roles;
-            //  Fixed mode keeps all 640 rows live and the backward kernel holds ONE workgroup per CU -- measured at config 3:
-            //  101.3 us per minibatch with the roles against 94.6 with k_baselines3 as its own launch; config 2: 66.0 against 72.1.)
-            h->fwd.bas_deferred = true;
-            h->fwd.scores_in_parts = true;
-        } else if (!defer_bas && base_ready && d.B <= 64 && (d.K + 63) / 64 <= 8 && h->sel.sw_merge_bas &&
-                   h->sel.n_cu >= 2 * stat_roles(d.T)) {
-            // phased (data-parallel) step, register-resident kernels: the baselines run in mmg_loss_stats' launch, as roles beside
-            // the statistics roles that consume their scores (k_bas_stats) -- one launch instead of two before the statistics all-reduce
-            h->fwd.bas_pending = true;
-            h->fwd.scores_in_parts = true;
-        } else {
-            Scope sc(h, st, "k_baselines");
-            const bool live_rows = base_ready && d.B <= 64;      // k_baselines3: live (step, sample) rows only
-            if (tile_path(h) && d.B <= 64 && !(d.H & 3)) {
-                // any message / state width: basehx as a GEMM launch, then one MFMA pass over the live rows (kernels_tile.h)
-                if (!h->fwd.basehx_ready)
-                    hipLaunchKernelGGL(k_gemm_nt, dim3(basehx_tiles(d)), dim3(MMG_BLOCK), 0, st, (const float*)h->tp.hx, d.H, (const float*)h->P.p[BS_L1_W], d.H + d.W,
-                                       (const float*)nullptr, h->tp.basehx, d.K, d.B, d.K, d.H);
-                hipLaunchKernelGGL(k_baselines4, dim3((d.T * d.B + 15) / 16, (d.K + 63) / 64, 2), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
-            } else if (live_rows) {
-                hipLaunchKernelGGL(k_baselines3, dim3((d.T * d.B + 15) / 16, (d.K + 63) / 64, 2), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
-            } else {
-                // grid.z = 2 baselines x 2 step ranges: 128 workgroups at config 1 instead of 64
-                hipLaunchKernelGGL(k_baselines2, dim3((d.B + 15) / 16, (d.K + 63) / 64, 2 * (d.T >= 4 ? 2 : 1)), dim3(MMG_BLOCK), 0, st,
-                                   h->dm, h->P, h->tp, 1, base_ready ? 1 : 0);
-            }
-            if (launch_check("k_baselines")) return -1;
-            h->fwd.scores_in_parts = true;
-        }
-    }
-    return 0;
+    return bas ? launch_baselines(h, st, all_rows, defer_bas, base_ready) : 0;
 }
 
 extern "C" int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                                     const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed,
                                     int train, int run_all_steps, void* stream) {
     if (!h) return fail("NULL handle");
-    auto fwd = [&](int64_t) { return exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, train, run_all_steps, stream); };
+    auto fwd = [&](int64_t) { return exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, train, tape_mode(run_all_steps), stream); };
     if (!train) return fwd(0);
     if (begin_minibatch(h, "mmg_exchange_forward(train = 1)")) return -1;
     return run_minibatches(h, 1, stream, fwd);             // a training forward pass starts a minibatch
@@ -554,7 +461,7 @@ extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_
     const int nsb = eval_sample_blocks(d.B);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t* tgt = d_target + (size_t)i * d.B;
-        if (exchange_forward_impl(h, d_x + (size_t)i * d.B * d.F, tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, 1, stream)) return -1;
+        if (exchange_forward_impl(h, d_x + (size_t)i * d.B * d.F, tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, TAPE_ALL, stream)) return -1;
         Scope sc(h, st, "k_eval_reduce");
         hipLaunchKernelGGL(k_eval_reduce, dim3(nsb + 2 * d.T), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_acc,
                            d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
@@ -587,9 +494,8 @@ extern "C" int mmg_loss_stats(mmg_handle* h, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (h->fwd.bas_pending) {
         Scope sc(h, st, "k_bas_stats");
-        const Dims& d = h->dm;
-        const int n_stats = stat_roles(d.T), n_bas = bas_roles(d);
-        hipLaunchKernelGGL(k_bas_stats, dim3(n_stats + n_bas), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, n_stats);
+        const LaunchPlan& p = h->sel.plan;
+        hipLaunchKernelGGL(k_bas_stats, dim3(p.n_stats + p.n_bas), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, p.n_stats);
         h->fwd.bas_pending = false;
         return launch_check("k_bas_stats");
     }
@@ -598,104 +504,74 @@ extern "C" int mmg_loss_stats(mmg_handle* h, void* stream) {
     return launch_check("k_stats");
 }
 
-// with_opt: this step's k_wgrad carries the optimizer (no k_opt launch).  conv_done: the fused step -- k_game_fast ran the forward
-// and the reverse pass, so no k_prep committed the minibatch counter / launch epoch: the optimizer does
+// FAM_TILE: the dh-independent part of the receiver's BPTT (seeds, dgpre, dhin) for all (step, sample) rows -- with the sender's
+// backward in the same launch where the plan merged them --, the recurrence, then what is left of the sender's backward
+static int launch_bwd_tile(mmg_handle* h, hipStream_t st, const int64_t* d_target) {
+    const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    const int zd = p.zero_dead ? 1 : 0, map = p.row_map ? 1 : 0;
+    {
+        Scope sc(h, st, "k_bwd_tile");
+        if (p.pre_send_fn) hipLaunchKernelGGL(p.pre_send_fn, dim3(p.n_pre + p.n_rowblk * p.n_hbands), dim3(MMG_BLOCK), p.pre_smem, st, h->dm, h->P, h->tp, zd, p.n_pre, p.n_hbands, p.pre_bands);
+        else if (p.pre_fn) hipLaunchKernelGGL(p.pre_fn, dim3(p.n_pre), dim3(MMG_BLOCK), p.pre_smem, st, h->dm, h->P, h->tp, zd);
+        switch (p.bwd_rec) {
+        case BR_SAMPLE:                                  // one workgroup per sample (+ one for the live-row list) (+ k_dhx's blocks)
+            hipLaunchKernelGGL(bwd_sample_fn(d.D), dim3(d.B + 1 + (p.dhx_own ? 0 : p.dhx_grid)), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, zd, map, p.dhx_blk);
+            break;
+        case BR_TILE:
+            hipLaunchKernelGGL(p.bwd_tile_fn, dim3(p.tiles), dim3(512), s.tile_bwd_smem, st, h->dm, h->P, h->tp, d_target, zd, map);
+            break;
+        case BR_RC:                                      // the output-step prelude and the reverse-time loop as roles over 16-unit slices
+            if (!d.use_binary) hipMemsetAsync(h->tp.rcflags, 0, 64 * 64 * sizeof(uint32_t), st);   // (binary mode: zeroed by k_bwd_pre)
+            hipLaunchKernelGGL(k_rc_bwd, dim3(p.tiles * p.rc_nj), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, zd, p.pre_bands, p.row_map ? 3 : 1);
+        }
+        if (launch_check("k_bwd_tile")) return -1;
+    }
+    if (d.use_binary) {
+        Scope sc(h, st, "k_send_bwd");
+        if (p.send_own)
+            hipLaunchKernelGGL(k_send_bwd, dim3(p.n_rowblk, p.n_hbands), dim3(MMG_BLOCK), s.send_bwd_smem, st, h->dm, h->P, h->tp, (const int*)(p.row_map ? h->tp.rmap : nullptr), (const int*)(p.row_map ? h->tp.rcount : nullptr));
+        if (p.dhx_own) hipLaunchKernelGGL(k_dhx, dim3(p.dhx_grid), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, p.dhx_blk);
+        if (launch_check("k_send_bwd")) return -1;
+    }
+    return 0;
+}
+
+// FAM_MC, continuous messages: the two launches of kernels_mc.h (with_stats: one extra workgroup of k_bwd_mc2)
+static int launch_bwd_mc(mmg_handle* h, hipStream_t st, const int64_t* d_target, bool with_stats) {
+    const Dims& d = h->dm; const LaunchPlan& p = h->sel.plan;
+    Scope sc(h, st, "k_bwd_mc");
+    hipLaunchKernelGGL((k_bwd_mc1<64, 64>), dim3(16 * p.mc_ngroup), dim3(512), 0, st, h->dm, h->P, h->tp, d_target, h->sel.mc_per, p.mc_ntile, p.mc_ngroup);
+    hipLaunchKernelGGL((k_bwd_mc2<64, 100>), dim3(d.B + p.mc_nred + (with_stats ? 1 : 0)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, p.mc_ngroup, p.mc_nred, with_stats ? 1 : 0);
+    return launch_check("k_bwd_mc");
+}
+
+// FAM_FAST (sample roles + statistics / class / dbar / deferred baseline roles) and the per-sample k_bwd_conv of every other shape
+static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_target, bool with_stats) {
+    const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    Scope sc(h, st, p.bwd_name);
+    if (s.family == FAM_FAST) {      // (a 512-thread variant of this kernel measured slower: 31.8 vs 28.8 us -- it is not issue-bound)
+        const int n_stats = with_stats ? p.n_stats : 0, n_bas = (with_stats && h->fwd.bas_deferred) ? p.n_bas : 0, n_class = with_stats ? d.D : p.n_class;
+        hipLaunchKernelGGL(with_stats ? p.bwd_fast_stats_fn : p.bwd_fast_fn, dim3(n_stats + d.B + n_class + p.n_dbar + n_bas), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, n_stats, p.zero_dead ? 1 : 0, p.n_dbar, n_bas);
+    } else
+        hipLaunchKernelGGL(p.bwd_conv_fn, dim3(d.B), dim3(MMG_BLOCK), s.bwd_smem, st, h->dm, h->P, h->tp, d_target);
+    return launch_check("k_bwd_conv");
+}
+
+// with_opt: this step's k_wgrad carries the optimizer (no k_opt launch).  conv_done: the fused step -- k_game_fast ran the forward and the
+// reverse pass (its first class role listed the live rows), so no k_prep committed the minibatch counter / launch epoch: the optimizer does
 static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, hipStream_t st, bool with_stats,
                          bool with_opt = false, bool conv_done = false) {
-    const Dims& d = h->dm;
-    bool row_map = false;
-    if (conv_done) {
-        row_map = true;                                  // k_game_fast ran the reverse pass and its first class role listed the live rows
-    } else if (tile_path(h)) {
-        row_map = d.T * d.B <= 2048;                     // k_wgrad keeps the live-row list in LDS (2048 entries)
-        const int zero_dead = (!row_map && !d.fixed) ? 1 : 0;
-        const int tiles = sample_tiles(d.B);
-        // the sender's backward rides in the same launch as k_bwd_pre (independent latency chains side by side) while the row
-        // blocks are few: it then walks all T * B rows instead of the live-row list (MMG_NO_MERGE=1: separate launches)
-        const bool merged_send = d.use_binary && h->sel.merge_roles && d.T * d.B <= 2048;
-        bool dhx_done = false;
-        {
-            Scope sc(h, st, "k_bwd_tile");
-            // the dh-independent part of the receiver's BPTT (seeds, dgpre, dhin) for all (step, sample) rows, then the recurrence
-            // wide receiver whose reverse-time loop runs as roles (k_rc_bwd adds the partials): four column bands per (step, tile)
-            const int pre_bands = (h->sel.rc_fwd && h->sel.rc_bwd && d.R == 256) ? 4 : 1;
-            if (d.use_binary && merged_send) {
-                const int nbands = (d.H + 63) / 64, nrb = sample_tiles(d.T * d.B);
-                const int smem = bwd_pre_lds_floats(d) * 4 > h->sel.send_bwd_smem ? bwd_pre_lds_floats(d) * 4 : h->sel.send_bwd_smem;
-                if (d.R <= 128) hipLaunchKernelGGL(k_bwd_pre_send<8>, dim3(d.T * tiles + nrb * nbands), dim3(MMG_BLOCK), smem, st, h->dm, h->P, h->tp, zero_dead, d.T * tiles, nbands, 1);
-                else hipLaunchKernelGGL(k_bwd_pre_send<16>, dim3(d.T * tiles * pre_bands + nrb * nbands), dim3(MMG_BLOCK), smem, st, h->dm, h->P, h->tp, zero_dead, d.T * tiles * pre_bands, nbands, pre_bands);
-            } else if (d.use_binary) {
-                if (d.R <= 128) hipLaunchKernelGGL(k_bwd_pre<8>, dim3(d.T * tiles), dim3(MMG_BLOCK), bwd_pre_lds_floats(d) * 4, st, h->dm, h->P, h->tp, zero_dead);
-                else hipLaunchKernelGGL(k_bwd_pre<16>, dim3(d.T * tiles), dim3(MMG_BLOCK), bwd_pre_lds_floats(d) * 4, st, h->dm, h->P, h->tp, zero_dead);
-            }
-            if (h->sel.rs_capable) {
-                // receiver shape of the register-resident kernels: one workgroup per sample (+ one for the live-row list)
-                // (+ k_dhx's blocks when the sender's backward already ran: its dpre is complete)
-                const int nblk = (d.B * (d.H / 4) + MMG_BLOCK - 1) / MMG_BLOCK, ndhx = merged_send ? nblk + (d.H / 4 + 63) / 64 : 0;
-                dhx_done = merged_send;
-                hipLaunchKernelGGL(bwd_sample_fn(d.D), dim3(d.B + 1 + ndhx), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, zero_dead, row_map ? 1 : 0, nblk);
-            } else if (d.R <= 64)
-                hipLaunchKernelGGL((k_bwd_tile<512, 2>), dim3(tiles), dim3(512), h->sel.tile_bwd_smem, st, h->dm, h->P, h->tp, d_target, zero_dead, row_map ? 1 : 0);
-            else if (d.R <= 128)
-                hipLaunchKernelGGL((k_bwd_tile<512, 4>), dim3(tiles), dim3(512), h->sel.tile_bwd_smem, st, h->dm, h->P, h->tp, d_target, zero_dead, row_map ? 1 : 0);
-            else if (h->sel.rc_fwd && h->sel.rc_bwd) {
-                // wide receiver: the output-step prelude and the reverse-time loop as roles over 16-unit slices (kernels_rc.h)
-                if (!d.use_binary) hipMemsetAsync(h->tp.rcflags, 0, 64 * 64 * sizeof(uint32_t), st);   // (binary mode: zeroed by k_bwd_pre)
-                hipLaunchKernelGGL(k_rc_bwd, dim3(tiles * (d.R / 16)), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, zero_dead,
-                                   (d.use_binary && merged_send) ? pre_bands : 1, row_map ? 3 : 1);
-            } else
-                hipLaunchKernelGGL((k_bwd_tile<512, 8>), dim3(tiles), dim3(512), h->sel.tile_bwd_smem, st, h->dm, h->P, h->tp, d_target, zero_dead, row_map ? 1 : 0);
-            if (launch_check("k_bwd_tile")) return -1;
+    const LaunchPlan& p = h->sel.plan;
+    if (!conv_done) {
+        if (h->sel.family == FAM_TILE ? launch_bwd_tile(h, st, d_target) : mc_bwd(h) ? launch_bwd_mc(h, st, d_target, with_stats)
+                                                                                     : launch_bwd_sample(h, st, d_target, with_stats)) return -1;
+        if (p.dc != DC_NONE) {
+            Scope sc(h, st, "k_dC");
+            if (p.dc == DC_PLAIN) hipLaunchKernelGGL(k_dC, dim3(h->dm.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
+            else hipLaunchKernelGGL(k_dC_tile, dim3(p.dc_grid, p.dc_slices), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, p.dc_slices, 0);
+            if (p.dc == DC_TILE && p.dc_slices > 1) hipLaunchKernelGGL(k_dC_tile, dim3(p.dc_grid, 1), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, p.dc_slices, 1);
+            if (launch_check("k_dC")) return -1;
         }
-        if (d.use_binary) {
-            Scope sc(h, st, "k_send_bwd");
-            if (!merged_send)
-                hipLaunchKernelGGL(k_send_bwd, dim3(sample_tiles(d.T * d.B), (d.H + 63) / 64), dim3(MMG_BLOCK), h->sel.send_bwd_smem, st,
-                                   h->dm, h->P, h->tp, (const int*)(row_map ? h->tp.rmap : nullptr), (const int*)(row_map ? h->tp.rcount : nullptr));
-            const int nblk = (d.B * (d.H / 4) + MMG_BLOCK - 1) / MMG_BLOCK;
-            if (!dhx_done) hipLaunchKernelGGL(k_dhx, dim3(nblk + (d.H / 4 + 63) / 64), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, nblk);
-            if (launch_check("k_send_bwd")) return -1;
-        }
-    } else if (mc_bwd(h)) {
-        Scope sc(h, st, "k_bwd_mc");
-        const int ntile = (d.B + 15) / 16;
-        int ngroup = ntile;                              // one sample tile per workgroup up to 16 groups (measured at 256 samples: 4 groups 26 us, 8: 15, 16: 10)
-        ngroup = ngroup < 1 ? 1 : (ngroup > 16 ? 16 : ngroup);
-        hipLaunchKernelGGL((k_bwd_mc1<64, 64>), dim3(16 * ngroup), dim3(512), 0, st, h->dm, h->P, h->tp, d_target, h->sel.mc_per, ntile, ngroup);
-        const int nred = (2 * d.D * d.R / 4 + MMG_BLOCK - 1) / MMG_BLOCK;
-        hipLaunchKernelGGL((k_bwd_mc2<64, 100>), dim3(d.B + nred + (with_stats ? 1 : 0)), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, ngroup, nred, with_stats ? 1 : 0);
-        if (launch_check("k_bwd_mc")) return -1;
-    } else {
-        const bool fast = fast_shape(h);
-        Scope sc(h, st, (fast && d.V != 100) ? "k_bwd_conv_wv" : "k_bwd_conv");
-        const bool merge_dc = fast && h->sel.merge_roles;
-        row_map = merge_dc && d.T * d.B <= 2048;         // class role 0 lists the live (step, sample) rows for k_wgrad
-        // k_conversation_fast3 stores softmax rows, not dbar = softmax(y) . desc: trailing workgroups form it (16 rows each)
-        const int n_dbar = (fast && d.use_binary) ? (d.T * d.B + 15) / 16 : 0;
-        if (fast) {      // (a 512-thread variant of this kernel measured slower: 31.8 vs 28.8 us -- it is not issue-bound)
-            const int n_stats = with_stats ? stat_roles(d.T) : 0, n_bas = (with_stats && h->fwd.bas_deferred) ? bas_roles(d) : 0;
-            const int n_class = (with_stats || merge_dc) ? d.D : 0;          // class roles (k_dC's work inside the launch)
-            const auto fn = with_stats ? bwd_conv_fast_fn<true, true>(d.D, d.V) : merge_dc ? bwd_conv_fast_fn<false, true>(d.D, d.V) : bwd_conv_fast_fn<false, false>(d.D, d.V);
-            hipLaunchKernelGGL(fn, dim3(n_stats + d.B + n_class + n_dbar + n_bas), dim3(256), 0, st, h->dm, h->P, h->tp, d_target, n_stats, row_map ? 0 : 1, n_dbar, n_bas);
-        }
-        else
-            if (d.B > 512)
-                hipLaunchKernelGGL(k_bwd_conv<true>, dim3(d.B), dim3(MMG_BLOCK), h->sel.bwd_smem, st, h->dm, h->P, h->tp, d_target);
-            else
-                hipLaunchKernelGGL(k_bwd_conv<false>, dim3(d.B), dim3(MMG_BLOCK), h->sel.bwd_smem, st, h->dm, h->P, h->tp, d_target);
-        if (launch_check("k_bwd_conv")) return -1;
-    }
-    if (conv_done) {
-    } else if (tile_path(h)) {
-        Scope sc(h, st, "k_dC");
-        const int RL = d.R < MMG_BLOCK ? d.R : MMG_BLOCK, CPB = MMG_BLOCK / RL, nsb = dc_slices(d.B);
-        hipLaunchKernelGGL(k_dC_tile, dim3((d.D + CPB - 1) / CPB, nsb), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, nsb, 0);
-        if (nsb > 1) hipLaunchKernelGGL(k_dC_tile, dim3((d.D + CPB - 1) / CPB, 1), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, nsb, 1);
-        if (launch_check("k_dC_tile")) return -1;
-    } else if (!(fast_shape(h) && h->sel.merge_roles) && !mc_bwd(h)) {
-        Scope sc(h, st, "k_dC");
-        hipLaunchKernelGGL(k_dC, dim3(d.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
-        if (launch_check("k_dC")) return -1;
     }
     WgHead hd;
     hd.gemm_tiles = h->jt.gemm_tiles; hd.n_wblocks = h->jt.n_wblocks; hd.special_block = h->jt.special_block; hd.special_job = h->jt.special_job;
@@ -704,11 +580,10 @@ static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_targe
         wo.oa.optim_type = h->cfg.optim_type; wo.oa.only_receiver = 0; wo.oa.lr = h->cfg.learning_rate;
         wo.oa.from_wgrad = 1; wo.oa.bump_step = 1; wo.oa.bump_mb = conv_done ? 1 : 0;
         for (int a = 0; a < 5; ++a) wo.oa.agent_begin[a] = h->pl.agent_begin[a];
-        wo.oa.total = h->pl.total;
-        wo.params = h->params; wo.state = h->opt_state; wo.grads = h->grads; wo.gnll = h->tp.gnll; wo.coefll = h->tp.coefll;
+        wo.oa.total = h->pl.total; wo.params = h->params; wo.state = h->opt_state; wo.grads = h->grads; wo.gnll = h->tp.gnll; wo.coefll = h->tp.coefll;
         wo.counter = h->tp.counter; wo.err_host = h->d_err;
     }
-    return launch_wgrad(h, st, h->d_jt, hd, d_x, d_desc, row_map, h->sel.wgrad_stride, true, with_opt ? &wo : nullptr);
+    return launch_wgrad(h, st, h->d_jt, hd, d_x, d_desc, conv_done || p.row_map, h->sel.wgrad_stride, true, with_opt ? &wo : nullptr);
 }
 
 extern "C" int mmg_backward(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, void* stream) {
@@ -718,11 +593,8 @@ extern "C" int mmg_backward(mmg_handle* h, const float* d_x, const int64_t* d_ta
     // continuous messages: the statistics are this rank's sum of rewards and hit count only, nothing a gradient depends on
     // (model.py:1297-1305) -- the call forms them itself (as a workgroup of the backward launch where the path has one, else as
     // k_stats) and no mmg_loss_stats / statistics all-reduce is needed; they reach the other ranks in the gradient tail
-    bool own_stats = false;
-    if (!h->dm.use_binary) {
-        own_stats = mc_bwd(h) && h->sel.merge_roles;
-        if (!own_stats && mmg_loss_stats(h, stream)) return -1;
-    }
+    const bool own_stats = mc_bwd(h) && h->sel.merge_roles;
+    if (!h->dm.use_binary && !own_stats && mmg_loss_stats(h, stream)) return -1;
     return backward_impl(h, d_x, d_target, d_desc, (hipStream_t)stream, own_stats);
 }
 
@@ -766,15 +638,12 @@ static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
         // the small Adaptive agents: conversation, baselines, statistics and the reverse pass in ONE launch (kernels_game.h), then
         // k_wgrad and k_opt -- three launches per minibatch
         hipStream_t st = (hipStream_t)stream;
-        const Dims& d = h->dm;
+        const Dims& d = h->dm; const LaunchPlan& p = h->sel.plan;
         if (!d_x || !d_desc) return fail("x / desc must not be NULL");
         if ((d_u_z || d_u_s || d_u_w) && !(d_u_z && d_u_s && d_u_w)) return fail("injected uniforms: all three streams or none");
-        ConvArgs ar;
-        memset(&ar, 0, sizeof(ar));
-        ar.x = d_x; ar.target = d_target; ar.desc = d_desc; ar.u_z = d_u_z; ar.u_s = d_u_s; ar.u_w = d_u_w; ar.seed = seed;
-        ar.train = 1; ar.run_all = 0; ar.t_begin = 0; ar.t_end = d.T; ar.phases = 3; ar.sprod_first = 1;
-        ar.nprep = prep_blocks(d, h->sel.prep_cpb, true); ar.prep_cpb = h->sel.prep_cpb; ar.nbase = basehx_tiles(d);
-        GameArgs ga; ga.n_stats = stat_roles(d.T); ga.n_bas = h->sel.game_nbas; ga.bas_ub = h->sel.game_bas_ub;
+        ConvArgs ar = conv_args(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, 0);
+        ar.nprep = p.nprep_hx; ar.prep_cpb = h->sel.prep_cpb; ar.nbase = p.basehx_tiles;
+        GameArgs ga; ga.n_stats = p.n_stats; ga.n_bas = h->sel.game_nbas; ga.bas_ub = h->sel.game_bas_ub;
         h->fwd = ForwardState();                        // (this launch is the forward pass: no baselines left over)
         h->fwd.basehx_ready = true; h->fwd.scores_in_parts = true;
         {
@@ -786,7 +655,7 @@ static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
         if (backward_impl(h, d_x, d_target, d_desc, st, true, h->sel.wgrad_opt_ok, true)) return -1;
         return h->sel.wgrad_opt_ok ? 0 : clip_step_impl(h, st, true, true);
     }
-    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, 2, stream, true)) return -1;
+    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, TAPE_MINIMAL, stream, true)) return -1;
     const bool merged = merge_stats(h);
     if (h->fwd.bas_deferred && !merged) return fail("internal: deferred baselines without the merged backward launch");
     if (!merged && mmg_loss_stats(h, stream)) return -1;
@@ -833,7 +702,7 @@ static int dp_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_target
     hipStream_t st = (hipStream_t)stream;
     mmg_allreduce_fn ar = (mmg_allreduce_fn)h->ar_fn;
     if (reduce && !ar) return fail("mmg_dp_train_step: no collective set (mmg_dp_set_allreduce)");
-    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, full_tape ? 3 : 2, stream)) return -1;
+    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, full_tape ? TAPE_LOG : TAPE_MINIMAL, stream)) return -1;
     if (h->dm.use_binary) {
         if (mmg_loss_stats(h, stream)) return -1;
         if (reduce) {

@@ -1,10 +1,13 @@
 """Per-kernel resource usage of the gfx950 device code (registers, spills, scratch, LDS, occupancy) and instruction counts.
 
   python scripts/isa_stats.py [--kernel SUBSTR] [--count MNEMONIC ...] [-D MACRO ...]
+  python scripts/isa_stats.py --digest          one line per kernel, sorted by symbol: the symbol and a SHA-256 of its assembly
+                                                (equal listings before and after a host-side change = the device code did not move)
 
 Compiles csrc/mmg.hip with `--cuda-device-only -S` (same flags as multimodalgame_amd/build.py) and parses the per-kernel
 trailers the AMDGPU backend writes into the assembly ("; NumVgprs: ...", "; ScratchSize: ...")."""
 import argparse
+import hashlib
 import os
 import re
 import subprocess
@@ -45,6 +48,20 @@ def parse(asm, count=()):
     return kernels
 
 
+def digests(asm):
+    """{kernel symbol: SHA-256 of its assembly text up to .Lfunc_end}.  Block labels and loop comments carry the index of the
+    function in the module (BB<n>_<block>), which moves whenever a host edit changes the order templates are first used in:
+    normalised away."""
+    out = {}
+    parts = re.split(r"^(_Z[\w$.]+):\s*(?:;.*)?$", asm, flags=re.M)
+    for i in range(1, len(parts) - 1, 2):
+        name, body = parts[i], parts[i + 1]
+        if re.search(r"; NumVgprs: (\d+)", body):
+            text = re.sub(r"BB\d+_", "BB_", body.split(".Lfunc_end")[0])
+            out[name] = hashlib.sha256(text.encode()).hexdigest()
+    return out
+
+
 def demangle(names):
     try:
         out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt"] + list(names), capture_output=True, text=True).stdout.split("\n")
@@ -60,8 +77,13 @@ def main():
     ap.add_argument("-D", dest="defines", action="append", default=[])
     ap.add_argument("--asm", default="/tmp/mmg_device.s")
     ap.add_argument("--reuse", action="store_true", help="parse an existing --asm file instead of recompiling")
+    ap.add_argument("--digest", action="store_true", help="print `symbol sha256` per kernel instead of the resource table")
     a = ap.parse_args()
     asm = open(a.asm).read() if a.reuse else device_asm(a.asm, a.defines)
+    if a.digest:
+        for name, digest in sorted(digests(asm).items()):
+            print(name, digest)
+        return
     ks = parse(asm, a.count)
     dm = demangle(list(ks))
     for n, info in sorted(ks.items(), key=lambda kv: dm[kv[0]]):
