@@ -22,6 +22,8 @@
  *   mmg_baseline_forward   <- Baseline.forward              model.py:496-516
  *   mmg_exchange_vjp       <- loss.backward() of ONE agent's graph for any loss built from exchange()'s outputs
  *                             (model.py:1309, 1316, 1322, 1328; graphs split at model.py:807-811, 826-829, 835-843)
+ *   mmg_exchange_vjp_channel <- (no call site: the reference detaches the messages, model.py:807-811, 826-829) backward()
+ *                             through the sender and the receiver as ONE graph, gradients crossing the channel
  *   mmg_sender_vjp         <- backward() through ONE Sender.forward call      model.py:193-238
  *   mmg_receiver_vjp       <- backward() through ONE Receiver.forward call    model.py:333-474
  *   mmg_baseline_vjp       <- backward() through ONE Baseline.forward call    model.py:496-516
@@ -317,6 +319,22 @@ int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, const float
 int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
                      const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
                      void* stream);
+
+/* Vector-Jacobian product of the sender's and the receiver's graphs of the last training exchange as ONE graph: the messages
+ * crossing between the two agents are NOT detached.  This departs from the reference on purpose (model.py:807-811 hands the
+ * receiver z.data, model.py:826-829 hands the sender w.data): it is the differentiable-channel baseline next to REINFORCE.
+ *   continuous messages (use_binary == 0): the receiver reads the sender's logits z_t and the sender's step t + 1 reads the
+ *     receiver's logits w_t with their graph -- the exact gradient;
+ *   binary messages: the straight-through estimator, z_t = pz_t + stopgrad(bits_t - pz_t), w_t = pw_t + stopgrad(bits_t - pw_t):
+ *     the forward values are the sampled bits of the tape, the backward pass treats d z_t / d pz_t and d w_t / d pw_t as 1.
+ * One reverse-time launch runs both agents' steps (kernels_vjp.h: k_vjp_channel); the gradient of the receiver's GRU input flows
+ * into the sender's step t, the gradient of the sender's code input into the receiver's step t - 1 (t = 0: code_bias).
+ * Arguments as mmg_exchange_vjp (same tape, NULL upstream = zero, 1 <= n_steps <= max_exchange; d_x and d_desc must not be
+ * NULL); writes ONLY the receiver's and the sender's slices of the gradient buffer (overwritten, not accumulated).  Constants as
+ * before: the stop bits and masks, softmax(y) inside dbar, data, desc, first_rec and every input of the baselines (their
+ * graphs stay separate: mmg_exchange_vjp).  fp32, deterministic (no float atomics); enqueued on `stream`. */
+int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
+                             const float* d_dz, const float* d_dw, const float* d_dps, void* stream);
 
 /* Vector-Jacobian products of ONE agent-level forward call (mmg_sender_forward / mmg_receiver_forward / mmg_baseline_forward with
  * train = 1): the backward pass of that call alone, for a conversation the caller writes out of module calls.  Every array is

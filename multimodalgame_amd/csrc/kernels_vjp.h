@@ -17,7 +17,9 @@
 // tape (z, h, h_x) are copied to vcz / vch0 / vch1 / vchx; k_wgrad<false> then runs over four per-call tables of B rows.
 //
 // Inputs crossing between agents are constants, as in the reference (model.py:807-811, 826-829, 835-843): the sender's and the
-// receiver's messages, data, desc and softmax(y) (dbar = softmax(y).detach() . desc, model.py:441-452).
+// receiver's messages, data, desc and softmax(y) (dbar = softmax(y).detach() . desc, model.py:441-452).  The one exception is
+// k_vjp_channel (mmg_exchange_vjp_channel, an option the reference does not have): the sender and the receiver as one graph
+// with the gradient crossing the channel through the messages, over the same step functions, tape rows and job tables.
 #pragma once
 #include "device_utils.h"
 #include "kernels_tile.h"
@@ -348,6 +350,69 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen(Dims dm, Params P, Tape t
                 for (int h = 0; h < H; ++h) acc = fmaf(Wc[(size_t)h * W + j], s_dpre[h], acc);
                 tp.vdc0[(size_t)b * W + j] = acc;
             }
+        }
+    }
+    __syncthreads();
+    for (int h = tid; h < H; h += MMG_BLOCK) tp.vdhx[(size_t)b * H + h] = s_dhx[h];
+}
+
+// dynamic LDS floats of k_vjp_channel: the receiver's and the sender's step areas, then the two message-gradient rows
+__host__ __device__ inline int vjp_channel_smem_floats(const Dims& d) {
+    return vjp_rec_smem_floats(d) + vjp_sen_smem_floats(d) + 2 * d.W;
+}
+
+// Sender and receiver as ONE graph (mmg_exchange_vjp_channel): the messages are NOT detached, so the gradient of the receiver's
+// GRU input z_t flows into the sender's step t and the gradient of the sender's code input w_{t-1} into the receiver's step
+// t - 1.  One workgroup per sample, one reverse-time loop running both agents' steps (vjp_rec_step, vjp_sen_step):
+//   s_dw = dw_up[t] + q_{t+1}      -> receiver step t   (q_{t+1} = W_c^T dpre_{t+1}, the cross term of the sender's step t + 1)
+//   s_dz = dz_up[t] + W_ih^T dgi_t -> sender step t
+// Continuous messages: both rows are logit gradients, exact.  Binary: they are d loss / d probabilities and the steps' own
+// p (1 - p) factor applies -- the straight-through estimator z = pz + stopgrad(bits - pz), w = pw + stopgrad(bits - pw).
+// Rows of steps t >= n get zero deltas: both carries start at zero and the cross terms are linear in the upstream gradients.
+// Writes the rows the receiver's and the sender's job tables reduce; the stop bit, softmax(y) inside dbar, data and desc stay
+// constants.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel(Dims dm, Params P, Tape tp, VjpIn in) {
+    extern __shared__ float smem[];
+    const int b = blockIdx.x, B = dm.B, D = dm.D, H = dm.H, W = dm.W, R = dm.R, T = dm.T, tid = threadIdx.x;
+    float* rsm = smem;                                        // vjp_rec_step's area
+    float* ssm = rsm + vjp_rec_smem_floats(dm);               // vjp_sen_step's area
+    float* s_dw = ssm + vjp_sen_smem_floats(dm);
+    float* s_dz = s_dw + W;
+    float* s_car = rsm + 9 * R;                               // (vjp_rec_step's carry slot)
+    float* s_hx = ssm;  float* s_dpre = s_hx + 2 * H;  float* s_dhx = s_dpre + H;
+    const float *Wih = P.p[R_WIH], *Wc = P.p[S_CODE_W], *cb = P.p[S_CODE_BIAS];
+    if (b == 0)
+        for (int j = tid; j < W; j += MMG_BLOCK) { const float s = sigmoidf_(cb[j]); tp.vdsig[j] = s * (1.f - s); }
+    for (int i = tid; i < R; i += MMG_BLOCK) s_car[i] = 0.f;
+    for (int h = tid; h < H; h += MMG_BLOCK) { s_hx[h] = tp.hx[(size_t)b * H + h]; s_dhx[h] = 0.f; }
+    for (int j = tid; j < W; j += MMG_BLOCK)
+        s_dw[j] = (T - 1 < in.n && in.dw) ? in.dw[((size_t)(T - 1) * B + b) * W + j] : 0.f;
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t row = (size_t)t * B + b;
+        const bool live = t < in.n;
+        RecRow io;
+        io.h0 = tp.h + row * R; io.h1 = tp.h + row * R + (size_t)B * R; io.z = tp.z + row * W; io.y = tp.y + row * D;
+        io.pw = tp.pw + row * W; io.ps = tp.ps + row;
+        io.dy = (live && in.dy) ? in.dy + row * D : nullptr;
+        io.dw = s_dw;
+        io.dps = (live && in.dps) ? in.dps + row : nullptr;
+        io.dhw = nullptr;
+        io.row = row;
+        vjp_rec_step(dm, P, tp, rsm, io);
+        __syncthreads();                                      // this row of vdgi complete
+        const float* dgi = tp.vdgi + row * 3 * R;
+        for (int k = tid; k < W; k += MMG_BLOCK) {            // d z_t = W_ih^T dgi_t
+            float acc = 0.f;
+            for (int i = 0; i < 3 * R; ++i) acc = fmaf(Wih[(size_t)i * W + k], dgi[i], acc);
+            s_dz[k] = acc + ((live && in.dz) ? in.dz[row * W + k] : 0.f);
+        }
+        vjp_sen_step(dm, P, tp, ssm, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W, s_dz, row);
+        __syncthreads();                                      // s_dpre complete
+        for (int j = tid; j < W; j += MMG_BLOCK) {            // d w_{t-1} = W_c^T dpre_t (t = 0: the code_bias path)
+            float acc = 0.f;
+            for (int h = 0; h < H; ++h) acc = fmaf(Wc[(size_t)h * W + j], s_dpre[h], acc);
+            if (t == 0) tp.vdc0[(size_t)b * W + j] = acc;
+            else s_dw[j] = acc + ((t - 1 < in.n && in.dw) ? in.dw[(row - B) * W + j] : 0.f);
         }
     }
     __syncthreads();

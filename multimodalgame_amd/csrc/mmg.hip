@@ -900,6 +900,29 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
     return launch_vjp_wgrad(h, st, agent, d_x, d_desc);
 }
 
+// mmg_exchange_vjp_channel: the sender's and the receiver's graphs of the last training exchange as ONE graph, the messages not
+// detached (kernels_vjp.h: k_vjp_channel).  Same tape, same job tables; writes exactly the two agents' slices.
+extern "C" int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
+                                        const float* d_dz, const float* d_dw, const float* d_dps, void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
+    if (!d_x || !d_desc) return fail("x / desc must not be NULL");
+    hipStream_t st = (hipStream_t)stream;
+    VjpIn in;
+    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = nullptr; in.dbr = nullptr; in.n = n_steps;
+    const size_t smem = sizeof(float) * (size_t)vjp_channel_smem_floats(d);
+    if (vjp_lds_ok(smem, "channel", " (too many classes or h_dim too large)") || launch_vjp_cd(h, st, d_desc)) return -1;
+    {
+        Scope sc(h, st, "k_vjp_channel");
+        hipLaunchKernelGGL(k_vjp_channel, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in);
+        if (launch_check("k_vjp_channel")) return -1;
+    }
+    if (launch_vjp_class(h, st, in)) return -1;
+    if (launch_vjp_wgrad(h, st, MMG_AGENT_RECEIVER, d_x, d_desc)) return -1;
+    return launch_vjp_wgrad(h, st, MMG_AGENT_SENDER, d_x, d_desc);
+}
+
 // Can a per-call product run on the MFMA tiles of k_vjp_nn?  tgemm_nn_raw reads Bm rows as float4 (16-byte aligned rows, N a
 // multiple of 4) and k_vjp_nn stages a [16, K] A tile plus the raw accumulators in LDS.
 static bool vjp_nn_fits(const NnProd& p) {

@@ -296,18 +296,33 @@ class Engine(object):
         executed steps -- dy [n, B, D], dz / dw [n, B, W] (probabilities when binary, logits when continuous), dps / dbs / dbr
         [n, B] or [n, B, 1]; None = zero.  The caller checks that the tape is still the forward's (self.generation)."""
         f32 = torch.float32
-        shapes = dict(dy=self.cfg.n_classes, dz=self.cfg.w_dim, dw=self.cfg.w_dim, dps=1, dbs=1, dbr=1)
-        args = {}
-        for k, g in (("dy", dy), ("dz", dz), ("dw", dw), ("dps", dps), ("dbs", dbs), ("dbr", dbr)):
-            if g is not None:
-                g = g.to(self.device, f32).contiguous()
-                if g.numel() != n_steps * self.cfg.batch * shapes[k]:
-                    raise ValueError("%s: %d entries for %d steps x %d samples x %d" % (k, g.numel(), n_steps, self.cfg.batch, shapes[k]))
-            args[k] = g
+        args = self._upstream(n_steps, dy=dy, dz=dz, dw=dw, dps=dps, dbs=dbs, dbr=dbr)
         _lib.check(self.lib.mmg_exchange_vjp(
             self.handle, _lib.AGENTS.index(agent), int(n_steps), self._ptr(x, f32), self._ptr(desc, f32),
             self._ptr(args["dy"]), self._ptr(args["dz"]), self._ptr(args["dw"]), self._ptr(args["dps"]),
             self._ptr(args["dbs"]), self._ptr(args["dbr"]), self._stream()))
+
+    def _upstream(self, n_steps, **named):
+        """Upstream gradients of a tape VJP -> fp32 contiguous device copies, checked to hold n_steps x batch rows; None stays."""
+        width = dict(dy=self.cfg.n_classes, dz=self.cfg.w_dim, dw=self.cfg.w_dim, dps=1, dbs=1, dbr=1)
+        args = {}
+        for k, g in named.items():
+            if g is not None:
+                g = g.to(self.device, torch.float32).contiguous()
+                if g.numel() != n_steps * self.cfg.batch * width[k]:
+                    raise ValueError("%s: %d entries for %d steps x %d samples x %d" % (k, g.numel(), n_steps, self.cfg.batch, width[k]))
+            args[k] = g
+        return args
+
+    def vjp_channel(self, n_steps, x, desc, dy=None, dz=None, dw=None, dps=None):
+        """Backward pass of the sender's and the receiver's graphs of the last training run-all forward as ONE graph, the
+        messages not detached (include/mmg.h: mmg_exchange_vjp_channel): writes self.grads["receiver"] and self.grads["sender"].
+        Upstream gradients as in vjp(); None = zero.  The caller checks that the tape is still the forward's."""
+        f32 = torch.float32
+        args = self._upstream(n_steps, dy=dy, dz=dz, dw=dw, dps=dps)
+        _lib.check(self.lib.mmg_exchange_vjp_channel(
+            self.handle, int(n_steps), self._ptr(x, f32), self._ptr(desc, f32), self._ptr(args["dy"]), self._ptr(args["dz"]),
+            self._ptr(args["dw"]), self._ptr(args["dps"]), self._stream()))
 
     # ------------------------------------------------------------------ per-call vector-Jacobian products
     def _vjp_args(self, named):

@@ -76,6 +76,27 @@ class _BaselineRecVJP(_AgentVJP):
         return _BaselineRecVJP._backward(ctx, grads)
 
 
+class _ChannelVJP(_AgentVJP):
+    """The sender's and the receiver's graphs of a training exchange() as ONE autograd node: the messages crossing between the
+    two agents are not detached (``channel_grad``; the reference detaches them, model.py:807-811, 826-829).  Inputs: a spec as
+    _AgentVJP's and the sender's, then the receiver's parameters; outputs: what _SenderVJP and _ReceiverVJP hand out together
+    (pz | z logits, y, ps, pw | w logits, stacked over the executed steps).  backward runs Engine.vjp_channel ONCE and returns
+    copies of both agents' gradient slices."""
+    KEYS = ("dz", "dy", "dps", "dw")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        ctx.saved_tensors                              # (raises once freed: backward through this node a second time)
+        spec = ctx.spec
+        eng = spec["eng"]
+        if eng.generation != spec["gen"]:
+            raise RuntimeError("the exchange tape this sender-receiver node was recorded on has been overwritten by a later "
+                               "engine call (exchange / train_step / forward): call backward() before the next one")
+        eng.vjp_channel(spec["n"], spec["x"], spec["desc"], **{k: g for k, g in zip(_ChannelVJP.KEYS, grads) if g is not None})
+        return (None,) + tuple(eng.grads[agent][name].clone() for agent, name in spec["names"])
+
+
 class FlatOptimizer(object):
     """Checkpoint-facing stand-in for the reference's four torch.optim objects (model.py:1110-1142):
     the update itself runs inside libmmg (k_gradnorm/k_opt); this class only converts the agent's slice
@@ -191,9 +212,11 @@ class Game(object):
     """Binds the four agent modules to one flat parameter buffer on the GPU and caches one libmmg
     handle per (batch size, number of classes).
 
-    autograd=True: training exchange() calls return outputs that carry autograd graphs (see exchange())."""
+    autograd=True: training exchange() calls return outputs that carry autograd graphs (see exchange()).
+    channel_grad=True (with autograd): the sender and the receiver are ONE graph there, gradients cross the channel."""
 
-    def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False):
+    def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
+                 channel_grad=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -210,6 +233,7 @@ class Game(object):
             "Both sender and receiver should communicate with same dim vectors for now."     # model.py:1756
         self.seed = seed
         self.autograd = bool(autograd)
+        self.channel_grad = bool(channel_grad)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -277,7 +301,14 @@ class Game(object):
         work as in the reference (model.py:1307-1330).  Constants, as in the reference: the sampled bits, the masks, data,
         desc.  ``sender.h_x``, ``receiver.h_z`` and ``receiver.h_w`` stay plain tensors (no gradient flows into them).
         The nodes read the engine's tape: backward() must run before the next exchange / train_step on the same batch shape
-        (a stale tape raises RuntimeError).  Otherwise exchange() returns exactly what it returns without autograd."""
+        (a stale tape raises RuntimeError).  Otherwise exchange() returns exactly what it returns without autograd.
+
+        Differentiable channel (opt-in on top of autograd): with ``exchange_args["channel_grad"] = True`` (or
+        ``Game(..., channel_grad=True)``) the sender and the receiver are ONE node (_ChannelVJP; include/mmg.h:
+        mmg_exchange_vjp_channel): the messages are not detached, so a loss on ``y`` alone trains the sender too.  Continuous
+        messages: the exact gradient through the logits.  Binary: the straight-through estimator, z = pz + stopgrad(bits - pz),
+        w = pw + stopgrad(bits - pw).  Same outputs, same values, same rules; the baselines keep their own nodes, the stop bit
+        stays a constant.  Without autograd being active the option changes nothing."""
         data, target, desc = exchange_args["data"], exchange_args.get("target"), exchange_args["desc"]
         train = exchange_args["train"]
         break_early = exchange_args.get("break_early", False)
@@ -323,7 +354,7 @@ class Game(object):
         self.modules["receiver"].h_z = tp["h"][n]
         self.modules["receiver"].h_w = tp["g"][n - 1]
         if autograd:
-            return self._exchange_graph(eng, data, desc, n, masks)
+            return self._exchange_graph(eng, data, desc, n, masks, bool(exchange_args.get("channel_grad", self.channel_grad)))
         s = (masks, [tp["s"][t].clone() for t in range(n)], [tp["ps"][t].clone() for t in range(n)])
         sen_w = ([tp["z"][t].clone() for t in range(n)], [tp["pz"][t].clone() if binary else None for t in range(n)])
         rec_w = ([tp["w"][t].clone() for t in range(n)], [tp["pw"][t].clone() if binary else None for t in range(n)])
@@ -332,8 +363,9 @@ class Game(object):
         br = [tp["br"][t].clone() for t in range(n)] if train and binary else []
         return s, sen_w, rec_w, y, bs, br
 
-    def _exchange_graph(self, eng, data, desc, n, masks):
-        """exchange()'s return structure with the four agents' autograd nodes (training, run-all tape of this call)."""
+    def _exchange_graph(self, eng, data, desc, n, masks, channel=False):
+        """exchange()'s return structure with the four agents' autograd nodes (training, run-all tape of this call).
+        channel: the sender and the receiver share one node (_ChannelVJP)."""
         tp, binary = eng.tape, self.cfg["use_binary"]
 
         def node(fn, agent, outs):
@@ -342,8 +374,15 @@ class Game(object):
             spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=names, outs=outs)
             return fn.apply(spec, *[p for _, p in mod.named_parameters()])
 
-        sen = node(_SenderVJP, "sender", [tp["pz" if binary else "z"][:n]])[0].unbind(0)
-        y_st, ps_st, w_st = node(_ReceiverVJP, "receiver", [tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
+        if channel:
+            named = [(a, name, p) for a in ("sender", "receiver") for name, p in self.modules[a].named_parameters()]
+            spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=[(a, name) for a, name, _ in named],
+                        outs=[tp["pz" if binary else "z"][:n], tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
+            sen_st, y_st, ps_st, w_st = _ChannelVJP.apply(spec, *[p for _, _, p in named])
+            sen = sen_st.unbind(0)
+        else:
+            sen = node(_SenderVJP, "sender", [tp["pz" if binary else "z"][:n]])[0].unbind(0)
+            y_st, ps_st, w_st = node(_ReceiverVJP, "receiver", [tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
         ps, rw, y = ps_st.unbind(0), w_st.unbind(0), list(y_st.unbind(0))
         s = (masks, [tp["s"][t].clone() for t in range(n)], list(ps))
         if binary:
