@@ -848,17 +848,6 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
         MMG_WG_END();
         return;
     }
-    // rmap != NULL: jobs whose rows are (step, sample) rows reduce over the compacted list of live rows only
-    // (build_row_map); the list is copied to LDS first thing, in the shadow of the job lookup below.
-    constexpr int MAXMAP = 2048;
-    __shared__ unsigned short s_map[MAXMAP];
-    const bool use_map = rmap != nullptr;
-    int nact = 0;
-    if (use_map) {
-        const int tb = dm.T * dm.B;
-        for (int i2 = threadIdx.x; i2 < tb; i2 += MMG_BLOCK) s_map[i2] = (unsigned short)rmap[i2];
-        nact = rcount[0];
-    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (bid == hd.n_wblocks) {
         // spare block: the six logged loss scalars, the semantic step count and the running totals (off every
@@ -911,19 +900,84 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
         }
         return;
     }
-    if (bid < hd.gemm_tiles) {
-      __shared__ int s_arrived;
-      for (int vt = bid; vt < hd.gemm_tiles; vt += (gt_stride > 0 ? gt_stride : hd.gemm_tiles)) {
-        // XCD-aware tile order: workgroup b is dispatched to XCD b % 8, and each XCD has its own 4 MB L2.  Giving
-        // every XCD a CONTIGUOUS range of tiles (= one or two jobs) keeps the operand tapes it re-reads
-        // (16-32 tiles share each of them) inside its L2; with the default order every XCD streams all ~7 MB
-        // of tapes through its L2 and the kernel is bound by L2-miss traffic.  (bijective remap, T1)
+    // XCD-aware tile order: workgroup b is dispatched to XCD b % 8, and each XCD has its own 4 MB L2.  Giving
+    // every XCD a CONTIGUOUS range of tiles (= one or two jobs) keeps the operand tapes it re-reads
+    // (16-32 tiles share each of them) inside its L2; with the default order every XCD streams all ~7 MB
+    // of tapes through its L2 and the kernel is bound by L2-miss traffic.  (bijective remap, T1)
+    auto tile_of = [&](int vt) {
         const int nwg = hd.gemm_tiles, xq = nwg >> 3, xr = nwg & 7;
         const int xcd = vt & 7, slot = vt >> 3;
-        const int tile = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + slot;
-        // job lookup: lane l compares the l-th job's first tile, one ballot (no serial scalar loads)
-        const int j = __popcll(__ballot(jt->g_begin[lane] <= tile)) - 1;
-        const GemmJob& G = jt->g[j];
+        return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + slot;
+    };
+    // ---- prologue: every memory trip the block's first chunk does not depend on is in flight before the first wait.
+    // rmap != NULL: jobs whose rows are (step, sample) rows reduce over the compacted list of live rows only (build_row_map).
+    // Issue order: the job lookup (lane l loads the l-th job's first block), then the list into REGISTERS (unconditional loads,
+    // clamped indices, a compile-time trip count: 3 per thread up to 768 rows -- the shard shape of configs 1-3 -- or 8 up to
+    // 2048), then the live-row count (one more vector load, read back to a scalar in store_list).  Vector loads return in order, so the ballot behind the lookup waits with a
+    // counted vmcnt(3 / 8) and leaves the list in flight; the job record is then copied by value (one group of scalar loads, one
+    // wait), the first operand chunk is issued where it does not need the list, and only then the list registers go to LDS
+    // (store_list) in front of the barrier that completes s_map.  The three variants are ONE uniform branch around lookup + list +
+    // ballot: a join between a load and its wait makes the wait count pessimistic.
+    constexpr int MAXMAP = 2048;
+    __shared__ unsigned short s_map[MAXMAP];
+    const bool use_map = rmap != nullptr;
+    const bool is_gemm = bid < hd.gemm_tiles;
+    const int tb = dm.T * dm.B;
+    const int first_blk = is_gemm ? tile_of(bid) : bid - hd.gemm_tiles;
+    const int* const lk = is_gemm ? jt->g_begin : jt->c_begin;
+    int begin_l, j0, nact = 0, nact_v = 0;
+    int lv[MAXMAP / MMG_BLOCK];
+    auto lookup_and_list = [&](auto nl_tag) {
+        constexpr int NL = decltype(nl_tag)::value;
+        // (the lookup's index passes through the variant's own text too: hoisted above the branch as common code, the load is
+        //  outstanding on paths of the lowered control flow that skip every variant, and the join drains the list for them)
+        int lkl = lane;
+        asm volatile("; job lookup, list variant %1" : "+v"(lkl) : "n"(NL));
+        begin_l = lk[lkl];
+#pragma unroll
+        for (int q = 0; q < NL; ++q) lv[q] = rmap[min((int)threadIdx.x + q * MMG_BLOCK, tb - 1)];
+        // (the live-row count rides behind the list as one more VECTOR load of a wave-uniform address: as a scalar load it shared
+        //  the scalar queue, which only drains whole, with the job record -- a cold trip in front of the record's)
+        if (NL > 0) {
+            int zl = 0;
+            asm volatile("; live-row count: a vector load" : "+v"(zl));
+            nact_v = rcount[zl];
+        }
+        // (the lookup's wait is pinned HERE, inside the variant, where the compiler knows how many loads follow it: it merges the
+        //  three ballots into one behind the join otherwise, and waits there with vmcnt(0).  The text differs per variant.)
+        asm volatile("; job lookup landed, %1 list loads in flight" : "+v"(begin_l) : "n"(NL));
+        j0 = __popcll(__ballot(begin_l <= first_blk)) - 1;
+    };
+    const bool short_list = tb <= 3 * MMG_BLOCK;
+    if (use_map) {
+        if (short_list) lookup_and_list(std::integral_constant<int, 3>{});
+        else lookup_and_list(std::integral_constant<int, MAXMAP / MMG_BLOCK>{});
+    } else lookup_and_list(std::integral_constant<int, 0>{});
+    bool list_pending = use_map;
+    // the list registers to LDS, once per block: called behind the loads that may precede the list's arrival, in front of every
+    // "s_map is complete" barrier
+    auto store_list = [&]() {
+        if (!list_pending) return;
+        list_pending = false;
+        nact = __builtin_amdgcn_readfirstlane(nact_v);
+        // (unconditional: entries beyond T * B receive the clamped load's value and are never read -- every index stays below MAXMAP)
+        if (short_list) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) s_map[(int)threadIdx.x + q * MMG_BLOCK] = (unsigned short)lv[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < MAXMAP / MMG_BLOCK; ++q) s_map[(int)threadIdx.x + q * MMG_BLOCK] = (unsigned short)lv[q];
+        }
+    };
+    if (is_gemm) {
+      __shared__ int s_arrived;
+      for (int vt = bid; vt < hd.gemm_tiles; vt += (gt_stride > 0 ? gt_stride : hd.gemm_tiles)) {
+        const int tile = vt == bid ? first_blk : tile_of(vt);
+        // job lookup: lane l compares the l-th job's first tile, one ballot (no serial scalar loads); the first tile's is the prologue's
+        const int j = vt == bid ? j0 : __popcll(__ballot(begin_l <= tile)) - 1;
+        // the job record BY VALUE: its 88 bytes arrive as one group of scalar loads behind one wait (through a reference the
+        // fields were fetched where the control flow first used them -- about seven dependent scalar trips)
+        const GemmJob G = jt->g[j];
         // many rows, few output tiles (thousands of samples): the rows of a tile are split over nsplit workgroups whose raw
         // partial tiles the last of them to arrive adds in slice order
         const int ns = G.nsplit > 1 ? G.nsplit : 1;
@@ -937,10 +991,14 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
         const bool cmp = use_map && G.compact;
         const int lda = G.lda, ldb = G.ldb, bmod = G.bmod, N = G.N, K = G.K;
         // The live-row list (s_map, nact) is a memory trip to what the previous launch just wrote -- ~2-3 us -- and so is the first
-        // operand chunk.  Round 6: the two trips overlap.  Jobs over plain rows (image_layer, the class jobs) never needed the list;
-        // and the compacted list BEGINS with the B rows of step 0 in order (build_row_map: every sample is live at t = 0), so
-        // with B >= 64 chunk 0 of a live-row job is rows 0..63 -- both kinds issue their first loads BEFORE the barrier that
-        // waits for the list (`early`), the rest of the prefetch ring behind it.  Nothing below may read nact ahead of that barrier.
+        // operand chunk; the list's loads are in flight since the prologue.  Jobs over plain rows (image_layer, the class jobs)
+        // never needed the list; and the compacted list BEGINS with the B rows of step 0 in order (build_row_map: every sample is
+        // live at t = 0), so with B >= 64 chunk 0 of a live-row job is rows 0..63 -- both kinds issue their first loads BEFORE the
+        // list registers are stored and before the barrier that completes s_map, the rest of the prefetch ring behind it.  In the ISA
+        // the virtual-operand kinds hold this order with counted waits (store_list behind vmcnt(4) / (6) / (8)); in the plain
+        // live-row kinds hipcc still waits for the list in front of chunk 0's loads -- it reuses the list loads' address registers
+        // for the chunk's addresses and waits for a load before overwriting those; keeping them costs the fourth workgroup per CU
+        // (DESIGN section 7).  Nothing below may read nact ahead of that barrier.
         const bool ident0 = cmp && dm.B >= 64 && sp == 0;
         int rows = cmp ? 0 : G.rows;                       // (live-row jobs: set behind the barrier)
         const bool veca = ((lda & 3) == 0) && ((((uintptr_t)Abase) & 15) == 0);
@@ -1010,11 +1068,14 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
                 if (CMPJ) { rc_ = s_map[rc_]; c0_ = s_map[c0_]; c1_ = s_map[c1_]; }     // (LDS reads: the global loads stay branch-free)
                 issue(rc_, c0_, c1_, u);
             };
-            // the prefetch ring's first loads: ahead of the list where they do not need it (see `early` above)
+            // the prefetch ring's first loads: ahead of the list's arrival where they do not need it (see above).  store_list sits
+            // INSIDE each arm: behind a join of arms with and without loads its wait would have to assume none (vmcnt(0))
             if (!CMPJ) {
 #pragma unroll
                 for (int u = 0; u < DEPTH - 1; ++u) fetch(cbeg + u, u);
-            } else if (ident0) issue(la, lb0, lb0 + 32, 0);
+                store_list();
+            } else if (ident0) { issue(la, lb0, lb0 + 32, 0); store_list(); }
+            else store_list();
             if (use_map) __syncthreads();                      // s_map is complete
 #ifdef MMG_TIMING
             if (threadIdx.x == 0 && tile < 2000) dbg2[8192 + 4 * tile + 0] = (long long)wall_clock64();
@@ -1062,6 +1123,7 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
             if (virt) run_c(std::true_type{}); else run_c(std::false_type{});
         } else {
             // edge tiles (N or K tail inside the tile, unaligned rows): guarded loads, one chunk at a time
+            store_list();
             if (use_map) __syncthreads();                      // s_map is complete
             if (cmp) set_rows(nact);
             for (int c = cbeg; c < cend; ++c) {
@@ -1178,6 +1240,11 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
                     if (gi2[h2] >= 0) opt_update_one(wo.oa, wo.params, wo.state, gi2[h2], gv2[h2], coef, w[h2], s1[h2], s2[h2], ostep);
             }
         }
+        // (the prefetches beyond a tile's last chunk are never consumed: across the back edge their registers count as outstanding
+        //  at the top of the body, and the first chunk's address arithmetic there then waits for the list.  The fused launch never
+        //  walks tiles -- the host passes no stride with it -- so its block ends here and the drain costs nothing; the tile-walking
+        //  launches keep their stores in flight across tiles instead)
+        if (OPT) __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0) -- the builtin, which the compiler's wait bookkeeping sees; inline text it does not
         __syncthreads();                                   // (the staging buffers / s_acc are the next tile's)
       }
         MMG_WG_END();
@@ -1185,9 +1252,9 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
     }
     // ---- column sums: 16 columns x 16 row groups per block, 4 independent loads in flight per thread
     const int cb = bid - hd.gemm_tiles;
-    const int j = __popcll(__ballot(jt->c_begin[lane] <= cb)) - 1;
-    const ColJob& C = jt->c[j];
+    const ColJob C = jt->c[j0];                            // (by value: one group of scalar loads, see the GEMM blocks)
     const bool ccmp = use_map && C.compact;
+    store_list();
     if (use_map) __syncthreads();                          // s_map is complete
     const int c0 = (cb - C.blk_begin) * 16;
     const int rows = ccmp ? nact : C.rows, ld = C.ld;
