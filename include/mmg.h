@@ -315,7 +315,8 @@ int mmg_baseline_forward(mmg_handle* h, int which, const float* d_x, const float
  *     d_dbs[n,B]    baseline_sen scores bs_t                                         model.py:835
  *     d_dbr[n,B]    baseline_rec scores br_t                                         model.py:842
  * Not differentiated (constants, as in the reference): sampled bits, masks, data, desc, h_x, h_z and softmax(y) inside dbar
- * (model.py:441).  fp32, deterministic (no float atomics); enqueued on `stream`. */
+ * (model.py:441).  The gradients of data and desc are formed on request by mmg_vjp_input_grads, called right after.  fp32,
+ * deterministic (no float atomics); enqueued on `stream`. */
 int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
                      const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
                      void* stream);
@@ -332,7 +333,7 @@ int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const float* d_x, co
  * Arguments as mmg_exchange_vjp (same tape, NULL upstream = zero, 1 <= n_steps <= max_exchange; d_x and d_desc must not be
  * NULL); writes ONLY the receiver's and the sender's slices of the gradient buffer (overwritten, not accumulated).  Constants as
  * before: the stop bits and masks, softmax(y) inside dbar, data, desc, first_rec and every input of the baselines (their
- * graphs stay separate: mmg_exchange_vjp).  fp32, deterministic (no float atomics); enqueued on `stream`. */
+ * graphs stay separate: mmg_exchange_vjp); d data and d desc on request: mmg_vjp_input_grads, called right after.  fp32, deterministic (no float atomics); enqueued on `stream`. */
 int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
                              const float* d_dz, const float* d_dw, const float* d_dps, void* stream);
 
@@ -359,6 +360,24 @@ int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_desc, const
                      const float* d_dps, const float* d_dh_w, const float* d_dh_new, float* d_dz, float* d_dh_prev, void* stream);
 int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
                      const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream);
+
+/* Gradients with respect to the two inputs of the game, the image features data (x) and the class descriptions desc, which every
+ * VJP above treats as constants.  Formed from the deltas that the VJP call IMMEDIATELY BEFORE this one, on the same handle and
+ * stream, left in the workspace -- call order contract: mmg_exchange_vjp(sender) -> d_ddx; mmg_exchange_vjp(receiver) -> d_ddesc;
+ * mmg_exchange_vjp_channel -> both (the deltas then hold the cross terms of the channel); with per_call != 0, mmg_receiver_vjp ->
+ * d_ddesc over the call's B rows, with d_y the y[B,D] handed to that call (and mmg_sender_vjp -> d_ddx, which that call can
+ * also return itself).  Asking for the gradient of an agent whose VJP did not run last reads stale deltas.
+ *   d data[b, :] = (sum_{t < n} d pre_t[b, :]) . image_layer.weight: data enters through image_layer only (model.py:195);
+ *                  baseline_sen reads h_x detached (model.py:835)
+ *   d desc[d, :] = sum_r dCd[d, r] y1.weight[r, R:]                    through the class side of y1 (model.py:432 over build_inp)
+ *                + sum_{t < n, b} softmax(y_t)[b, d] (w_d.weight^T d gpre_t[b, :])   through dbar (model.py:442-452)
+ *   softmax(y) inside dbar stays a constant, as in the reference (model.py:441).  Sums run over the n_steps executed steps (per_call:
+ *   the one call; n_steps is only range-checked); steps >= n_steps contribute exactly zero.
+ *   d_ddx[B,F], d_ddesc[D,V]: NULL = not wanted; otherwise overwritten.  d_y: per_call only (the exchange VJPs read the tape's y).
+ * Touches nothing else: the gradient buffer and every tape array the VJPs write stay bit-identical (its own scratch: vdq).
+ * Errors: a NULL handle, n_steps outside 1..max_exchange, per_call with d_ddesc but without d_y.  fp32 on the matrix cores, a fixed
+ * summation order, no float atomics: bit-identical from run to run; enqueued on `stream`, no host synchronisation. */
+int mmg_vjp_input_grads(mmg_handle* h, int per_call, int n_steps, const float* d_y, float* d_ddx, float* d_ddesc, void* stream);
 
 /* The loss functions of the training block as forward / vector-Jacobian launches over the CALLER'S tensors: handle-free (the
  * arithmetic depends on no mmg_config), on the calling thread's current device, enqueued on `stream`; no host synchronisation, no

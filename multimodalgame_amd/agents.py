@@ -19,8 +19,10 @@ exchange() loop, model.py:725-876, or any variation of it -- trains with ``loss.
     sampled bits are non-differentiable outputs.
   - gradients reach the parameters and every floating input that requires grad: the Sender's x and w (at t == 0 the code
     input is sigmoid(code_bias), model.py:196-200), the Receiver's z and previous state (``receiver.h_z`` is the node's output
-    and the next call's input: backpropagation through time is torch's own graph), all three Baseline inputs.  desc and
-    softmax(y) inside dbar are constants (model.py:441); a desc that requires grad raises NotImplementedError.
+    and the next call's input: backpropagation through time is torch's own graph), all three Baseline inputs.  softmax(y)
+    inside dbar is a constant (model.py:441).  desc is a constant too and a desc that requires grad raises NotImplementedError,
+    unless the Game was built with ``input_grad=True``: then the Receiver's node returns d desc of the call as well (include/mmg.h:
+    mmg_vjp_input_grads) and torch sums it over the calls.
   - a node reads only its own call's saved inputs and outputs and the parameters, never the engine's tape: exchange(), other
     conversations or eval_forward() in between change nothing.  Parameters that changed between forward and backward raise
     RuntimeError (a library-side update: train_step(s), load_state_dicts, ... -- Engine.param_version; an in-place torch edit:
@@ -156,7 +158,8 @@ class _ReceiverCall(_CallVJP):
     (s, s_prob, w logits, y, h_w, h_new) when continuous (s non-differentiable)."""
 
     @staticmethod
-    def forward(ctx, spec, z, h_prev, *params):
+    def forward(ctx, spec, z, h_prev, desc_in, *params):
+        # desc_in: the caller's desc tensor under input_grad (None otherwise): the call reads spec["desc"], its fp32 copy
         eng = spec["eng"]
         ctx.spec = spec
         ctx.set_materialize_grads(False)
@@ -166,7 +169,7 @@ class _ReceiverCall(_CallVJP):
         s, s_prob, w, w_probs, y, h_w = eng.receiver_forward(z.contiguous(), spec["desc"], h, sprod, h_prev is None, spec["t"],
                                                              True, seed=spec["seed"])
         # (desc too: an in-place edit of it before backward() trips torch's version check, as for the other saved inputs)
-        ctx.save_for_backward(z, h_prev, h, y, w_probs, s_prob, spec["desc"], *params)
+        ctx.save_for_backward(z, h_prev, h, y, w_probs, s_prob, spec["desc"], desc_in, *params)
         if w_probs is None:
             ctx.mark_non_differentiable(s)
             return s, s_prob, w, y, h_w, h
@@ -176,7 +179,7 @@ class _ReceiverCall(_CallVJP):
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        z, h_prev, h_new, y, w_probs, s_prob, desc = _CallVJP._check(ctx)[:7]
+        z, h_prev, h_new, y, w_probs, s_prob, desc, desc_in = _CallVJP._check(ctx)[:8]
         if w_probs is None:
             _, dps, dw, dy, dh_w, dh_new = grads
         else:
@@ -184,7 +187,11 @@ class _ReceiverCall(_CallVJP):
         spec = ctx.spec
         dz, dh_prev = spec["eng"].receiver_vjp(z, desc, h_prev, h_new, y, w_probs, s_prob, dy, dw, dps, dh_w, dh_new,
                                                want_dz=ctx.needs_input_grad[1], want_dh_prev=ctx.needs_input_grad[2])
-        return (None, None if dz is None else dz.view_as(z), dh_prev) + _CallVJP._param_grads(ctx)
+        ddesc = None
+        if ctx.needs_input_grad[3]:                                       # d desc of this call, from the deltas the VJP left
+            ddesc = spec["eng"].input_grads(1, want_ddesc=True, per_call=True, y=y)[1]
+            ddesc = ddesc.to(device=desc_in.device, dtype=desc_in.dtype).reshape(desc_in.shape)
+        return (None, None if dz is None else dz.view_as(z), dh_prev, ddesc) + _CallVJP._param_grads(ctx)
 
 
 class _BaselineCall(_CallVJP):
@@ -300,13 +307,15 @@ class Receiver(_Agent):
         game = self._bound_game(z.size(0))
         B = z.size(0)
         if self._graph_on(game):
-            if desc.requires_grad:
-                raise NotImplementedError("gradients with respect to desc are not supported: pass desc.detach() (the reference "
-                                          "hands the receiver desc.data, model.py:803-805)")
+            input_grad = getattr(game, "input_grad", False)
+            if desc.requires_grad and not input_grad:
+                raise NotImplementedError("gradients with respect to desc need the input_grad opt-in (Game(..., input_grad=True)); "
+                                          "without it pass desc.detach() (the reference hands the receiver desc.data, "
+                                          "model.py:803-805)")
             eng = game.engine_for(B)
             spec = self._spec(eng, t=min(self._t, game.max_exchange - 1), seed=game.next_seed(),
                               desc=desc.detach().contiguous())
-            out = _ReceiverCall.apply(spec, z, self.h_z, *self.parameters())
+            out = _ReceiverCall.apply(spec, z, self.h_z, desc if input_grad and desc.requires_grad else None, *self.parameters())
             if self.use_binary:
                 s, s_prob, w, w_probs, y, h_w, h_z = out
             else:

@@ -130,13 +130,14 @@ __device__ __forceinline__ void tgemm_nt_pair(const NtJob& ja, const NtJob& jb, 
     const int tb = (jb.N + 15) >> 4, kb = tile_kparts(tb, nw), nb_ = tb * kb;
     float4 w[4][4];
     int s_tn[4], s_kp[4], s_g0[4], s_n[4];
-    bool s_b[4];
+    bool s_b[4], s_has[4];
 #pragma unroll
     for (int sl = 0; sl < 4; ++sl) {
         const int it = wave + sl * nw;
         const bool isb = it >= na;
         const int li = isb ? it - na : it;
         const bool has = isb ? (li < nb_) : true;
+        s_has[sl] = has;
         const int kparts = isb ? kb : ka, N = isb ? jb.N : ja.N, K = isb ? jb.K : ja.K, ldw = isb ? jb.ldw : ja.ldw;
         const float* Wm = isb ? jb.Wm : ja.Wm;
         const int kgroups = (K + 15) >> 4, per = (kgroups + kparts - 1) / kparts;
@@ -149,7 +150,9 @@ __device__ __forceinline__ void tgemm_nt_pair(const NtJob& ja, const NtJob& jb, 
     }
 #pragma unroll
     for (int sl = 0; sl < 4; ++sl) {
-        if (s_n[sl] == 0) continue;
+        // (an item whose k-part is empty -- K below 16 k-parts, e.g. R = 12 split four ways -- still writes its zeros: raw_sum adds
+        //  every part of the staging area, and a part left unwritten holds another product's values)
+        if (!s_has[sl]) continue;
         const float* A = s_b[sl] ? jb.A : ja.A;
         const int lda = s_b[sl] ? jb.lda : ja.lda, N = s_b[sl] ? jb.N : ja.N;
         float* raw = s_b[sl] ? jb.raw : ja.raw;

@@ -20,6 +20,8 @@
 // receiver's messages, data, desc and softmax(y) (dbar = softmax(y).detach() . desc, model.py:441-452).  The one exception is
 // k_vjp_channel (mmg_exchange_vjp_channel, an option the reference does not have): the sender and the receiver as one graph
 // with the gradient crossing the channel through the messages, over the same step functions, tape rows and job tables.
+// data and desc are constants of every kernel above; mmg_vjp_input_grads forms their gradients afterwards, from the deltas a VJP
+// left in the v* arrays (k_vjp_ddesc, at the end of this file).
 #pragma once
 #include "device_utils.h"
 #include "kernels_tile.h"
@@ -78,7 +80,7 @@ struct RecRow {
 
 // The receiver's step backward (model.py:340-474), shared by the exchange and the per-call VJP.  On entry s_car (LDS, R floats)
 // holds d h_{t+1} from later uses of the state; on exit it holds d h_t.  Writes the row's deltas the weight-gradient jobs reduce
-// (vdgi, vdgh, vdgpre, vdlw, vdls, vdA, vdys) and the recomputed operands (vA, vg, vdbar).
+// (vdgi, vdgh, vdgpre, vdlw, vdls, vdA, vdys) and the recomputed operands (vA, vg, vdbar, the softmax statistics vsm).
 __device__ __forceinline__ void vjp_rec_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const RecRow& io) {
     const int D = dm.D, W = dm.W, R = dm.R, V = dm.V;
     const int tid = threadIdx.x;
@@ -117,7 +119,10 @@ __device__ __forceinline__ void vjp_rec_step(const Dims& dm, const Params& P, co
         s_dbar[v] = acc;
         tp.vdbar[row * V + v] = acc;
     }
-    if (tid == 0) tp.vdys[row] = dys;
+    if (tid == 0) {
+        tp.vdys[row] = dys;
+        tp.vsm[row * 2] = m; tp.vsm[row * 2 + 1] = 1.f / sum;  // the row's softmax statistics (k_vjp_ddesc re-forms softmax(y_t))
+    }
     // GRU gates of the step (model.py:340): r, u, n and W_hn h + b_hn
     for (int i = tid; i < R; i += MMG_BLOCK) {
         float gr = bih[i] + bhh[i], gu = bih[R + i] + bhh[R + i], gin = bih[2 * R + i], ghn = bhh[2 * R + i];
@@ -590,6 +595,108 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_nn(int B, NnProd p0, NnProd p
     for (int e = threadIdx.x; e < MMG_TM * p.N; e += MMG_BLOCK) {
         const int m = e / p.N, n = e - m * p.N;
         if (b0 + m < B) p.C[(size_t)(b0 + m) * p.ldc + n] = raw_sum(raw, ldr, kparts, m, n);
+    }
+}
+
+// The same product for a shape vjp_nn_fits turns down (N or ldb no multiple of 4, the LDS plan beyond 64 KiB): one thread per
+// output element, k in order.  Only mmg_vjp_input_grads needs it -- the per-call kernels form such a product themselves.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_nn_plain(int rows, NnProd p) {
+    const size_t total = (size_t)rows * p.N;
+    for (size_t e = (size_t)blockIdx.x * MMG_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * MMG_BLOCK) {
+        const size_t m = e / p.N;
+        const int n = (int)(e - m * p.N);
+        float acc = 0.f;
+        for (int k = 0; k < p.K; ++k) acc = fmaf(p.A[m * p.lda + k], p.Bm[(size_t)k * p.ldb + n], acc);
+        p.C[m * p.ldc + n] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Input gradients (mmg_vjp_input_grads): the game's two inputs, data and desc, as differentiable inputs of the graphs above.
+//   d data[b, :] = vdhx[b, :] . W_image                     data enters through image_layer only (model.py:195; baseline_sen reads
+//                                                            h_x detached, model.py:835)                                  -> k_vjp_nn
+//   d desc[d, :] = sum_r vdC[d, r] W_y1[r, R:]               through Cd (model.py:432 over build_inp)
+//                + sum_{t < n, b} pi_t[b, d] q_t[b, :]       through dbar = pi_t . desc (model.py:442-452), pi_t = softmax(y_t) a
+//                                                            constant (model.py:441), q_t = vdgpre_t . W_d (vdq, k_vjp_nn)
+// k_vjp_ddesc forms d desc: a [D x rows] . [rows x V] product over the rows = n * B executed (step, sample) rows plus the K = R
+// product of the Cd term, in fp32 on the matrix cores (v_mfma_f32_16x16x4_f32: bit for bit an fmaf chain in k order).
+// One workgroup owns one output tile, 16 classes x MMG_DDESC_VT columns of desc; its four waves split the rows in groups of 16
+// (group g -> wave g & 3) and the k-steps of the Cd term the same way, four accumulator tiles per wave.  Lane (i = l & 15,
+// q = l >> 4) holds A[class i][k = q] and B[k = q][column i] of a k-step of four rows.  The Pi^T operand never exists in memory:
+// a lane forms its element exp(y - m) * inv from the row statistics vjp_rec_step left in vsm -- every element feeds exactly one
+// lane (the wave owns the row, the lane the class), so a round trip through LDS would only add a barrier per group.  Loads are
+// branch-free (indices clamped, the A element zeroed instead) and those of a whole group are in flight together.  The waves'
+// partial tiles meet in LDS and are added in wave order: no atomics, no cross-workgroup traffic, bit-identical from run to run.
+// D, V and rows need not be multiples of anything; rows of steps t >= n are never read, so they contribute exactly zero.
+// ---------------------------------------------------------------------------------------------
+#define MMG_DDESC_VT 64
+
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_ddesc(Dims dm, Params P, Tape tp, const float* __restrict__ y, int rows,
+                                                         float* __restrict__ ddesc) {
+    __shared__ float s_part[MMG_BLOCK / 64][16][MMG_DDESC_VT + 4];
+    const int D = dm.D, V = dm.V, R = dm.R;
+    const int d0 = blockIdx.x * 16, v0 = blockIdx.y * MMG_DDESC_VT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = MMG_BLOCK / 64, i = lane & 15, q = lane >> 4;
+    const bool dok = d0 + i < D;
+    const int dc = min(d0 + i, D - 1);
+    int vc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) vc[j] = min(v0 + 16 * j + i, V - 1);        // (clamped columns: computed, never written)
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // sum over the executed (step, sample) rows of pi[row, d] q[row, v]
+    const float* sm = tp.vsm;
+    const float* dq = tp.vdq;
+    const int ngroups = (rows + 15) >> 4;
+    for (int g = wave; g < ngroups; g += nw) {
+        float yv[4], mx[4], inv[4], b[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int rc = min(g * 16 + u * 4 + q, rows - 1);
+            yv[u] = y[(size_t)rc * D + dc]; mx[u] = sm[(size_t)rc * 2]; inv[u] = sm[(size_t)rc * 2 + 1];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[u][j] = dq[(size_t)rc * V + vc[j]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float a = (dok && g * 16 + u * 4 + q < rows) ? expf(yv[u] - mx[u]) * inv[u] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = mfma16(a, b[u][j], acc[j]);
+        }
+    }
+    // + sum_r vdC[d, r] W_y1[r, R + v]
+    const float* Wy1 = P.p[R_Y1_W];
+    const int cgroups = (R + 15) >> 4;
+    for (int g = wave; g < cgroups; g += nw) {
+        float av[4], b[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int rc = min(g * 16 + u * 4 + q, R - 1);
+            av[u] = tp.vdC[(size_t)dc * R + rc];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[u][j] = Wy1[(size_t)rc * (R + V) + R + vc[j]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float a = (dok && g * 16 + u * 4 + q < R) ? av[u] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = mfma16(a, b[u][j], acc[j]);
+        }
+    }
+    // accumulator tile j: column i, rows 4 q + r in register r
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s_part[wave][q * 4 + r][16 * j + i] = acc[j][r];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 16 * MMG_DDESC_VT; e += MMG_BLOCK) {
+        const int m = e / MMG_DDESC_VT, n = e - m * MMG_DDESC_VT;
+        if (d0 + m < D && v0 + n < V) {
+            float v = s_part[0][m][n];
+            for (int w = 1; w < nw; ++w) v += s_part[w][m][n];
+            ddesc[(size_t)(d0 + m) * V + v0 + n] = v;
+        }
     }
 }
 

@@ -232,6 +232,9 @@ inline Params resolve_params(const ParamLayout& L, float* base) {
     X(vhid_r, float, 0, 3, T, B, K)                                                \
     X(vdbs, float, 0, 2, T, B, 1)                                                  \
     X(vdbr, float, 0, 2, T, B, 1)                                                  \
+    /* ---- input gradients (mmg_vjp_input_grads, kernels_vjp.h: k_vjp_ddesc) ---- */ \
+    X(vsm, float, 0, 3, T, B, 2)         /* softmax(y_t) row statistics left by vjp_rec_step: row max | 1 / sum exp(y - max) */ \
+    X(vdq, float, 0, 3, T, B, V)         /* q_t = dgpre_t . W_d: dL/d dbar_t, formed by mmg_vjp_input_grads */ \
     /* ---- per-call VJPs of the agent modules (mmg_sender_vjp / _receiver_vjp / _baseline_vjp): operand copies of one call ---- */ \
     X(vcz, float, 0, 2, B, W, 1)         /* z (receiver, baseline_rec) | z_r (baseline_sen) of the call     */ \
     X(vch0, float, 0, 2, B, R, 1)        /* receiver: h_prev (zeros for a first call)                      */ \

@@ -947,6 +947,45 @@ static NnProd nn_prod(const float* A, int lda, const float* Bm, int ldb, float* 
     return p;
 }
 
+// One NN product over `rows` rows: the MFMA tiles of k_vjp_nn where the shape fits them, else one thread per output element.
+static int launch_vjp_nn_rows(mmg_handle* h, hipStream_t st, int rows, const NnProd& p) {
+    if (vjp_nn_fits(p)) {
+        Scope sc(h, st, "k_vjp_nn");
+        hipLaunchKernelGGL(k_vjp_nn, dim3(sample_tiles(rows), 1), dim3(MMG_BLOCK), sizeof(float) * (size_t)vjp_nn_smem_floats(p.N, p.K),
+                           st, rows, p, p);
+        return launch_check("k_vjp_nn");
+    }
+    const size_t blocks = ((size_t)rows * p.N + MMG_BLOCK - 1) / MMG_BLOCK;
+    Scope sc(h, st, "k_vjp_nn_plain");
+    hipLaunchKernelGGL(k_vjp_nn_plain, dim3((int)(blocks > 65536 ? 65536 : blocks)), dim3(MMG_BLOCK), 0, st, rows, p);
+    return launch_check("k_vjp_nn_plain");
+}
+
+// mmg_vjp_input_grads: d data and d desc from the deltas the VJP call just before it left in the v* arrays (kernels_vjp.h:
+// k_vjp_ddesc).  Reads the tape and the parameters; writes vdq and the caller's two outputs, nothing else.
+extern "C" int mmg_vjp_input_grads(mmg_handle* h, int per_call, int n_steps, const float* d_y, float* d_ddx, float* d_ddesc,
+                                   void* stream) {
+    if (!h) return fail("NULL handle");
+    const Dims& d = h->dm;
+    if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
+    if (per_call && d_ddesc && !d_y) return fail("y of the call must not be NULL (per_call)");
+    hipStream_t st = (hipStream_t)stream;
+    if (d_ddx) {                                               // d data = dhx . W_image
+        const NnProd px = nn_prod(h->tp.vdhx, d.H, h->P.p[S_IMG_W], d.F, d_ddx, d.F, d.F, d.H);
+        if (launch_vjp_nn_rows(h, st, d.B, px)) return -1;
+    }
+    if (d_ddesc) {
+        const int rows = per_call ? d.B : n_steps * d.B;       // the executed (step, sample) rows | the call's rows
+        const NnProd pq = nn_prod(h->tp.vdgpre, d.R, h->P.p[R_WD_W], d.V, h->tp.vdq, d.V, d.V, d.R);   // q = dgpre . W_d
+        if (launch_vjp_nn_rows(h, st, rows, pq)) return -1;
+        Scope sc(h, st, "k_vjp_ddesc");
+        hipLaunchKernelGGL(k_vjp_ddesc, dim3((d.D + 15) / 16, (d.V + MMG_DDESC_VT - 1) / MMG_DDESC_VT), dim3(MMG_BLOCK), 0, st, d, h->P,
+                           h->tp, per_call ? d_y : (const float*)h->tp.y, rows, d_ddesc);
+        if (launch_check("k_vjp_ddesc")) return -1;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The per-call VJPs of the agent modules' forward() (kernels_vjp.h: k_vjp_sen_call / k_vjp_rec_call / k_vjp_bas_call): the
 // backward pass of ONE mmg_sender_forward / mmg_receiver_forward / mmg_baseline_forward call from the caller's copies of its

@@ -324,6 +324,23 @@ class Engine(object):
             self.handle, int(n_steps), self._ptr(x, f32), self._ptr(desc, f32), self._ptr(args["dy"]), self._ptr(args["dz"]),
             self._ptr(args["dw"]), self._ptr(args["dps"]), self._stream()))
 
+    def input_grads(self, n_steps, want_dx=False, want_ddesc=False, per_call=False, y=None):
+        """d data [B, F] and d desc [D, V] of the VJP that ran LAST on this engine and stream (include/mmg.h:
+        mmg_vjp_input_grads): vjp("sender") leaves what d data needs, vjp("receiver") what d desc needs, vjp_channel both; with
+        per_call, receiver_vjp (y: that call's class logits).  Returns (d data, d desc), None where not wanted.  Writes no
+        gradient slice and no tape array a VJP wrote."""
+        c = self.cfg
+        dx = torch.empty(c.batch, c.feat_dim, device=self.device) if want_dx else None
+        dd = torch.empty(c.n_classes, c.wv_dim, device=self.device) if want_ddesc else None
+        if per_call and y is not None:
+            y = y.detach().to(self.device, torch.float32).contiguous()
+            if y.numel() != c.batch * c.n_classes:
+                raise ValueError("y: %d entries for %d samples x %d" % (y.numel(), c.batch, c.n_classes))
+        if dx is not None or dd is not None:
+            _lib.check(self.lib.mmg_vjp_input_grads(self.handle, int(bool(per_call)), int(n_steps), self._ptr(y if per_call else None),
+                                                    self._ptr(dx), self._ptr(dd), self._stream()))
+        return dx, dd
+
     # ------------------------------------------------------------------ per-call vector-Jacobian products
     def _vjp_args(self, named):
         """(name, tensor or None, floats per sample) -> device pointers of fp32 contiguous copies, checked to hold B rows."""

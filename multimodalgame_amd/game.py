@@ -10,25 +10,41 @@ from . import misc
 from .engine import Engine
 
 
+def _input_grad(g, like):
+    """A gradient the engine formed (fp32, on its device) in the shape, dtype and device of the input it belongs to."""
+    return None if g is None else g.to(device=like.device, dtype=like.dtype).reshape(like.shape)
+
+
 class _AgentVJP(torch.autograd.Function):
     """One agent's graph of a training exchange() as ONE autograd node (the reference's four graphs are disjoint: every input
     crossing between agents is detached, model.py:807-811, 826-829, 835-843).  Inputs: a spec (engine, tape generation, steps,
-    the forward's x / desc, the tape arrays to hand out) and the agent's parameters; outputs: the agent's differentiable outputs
-    stacked over the executed steps, [n, B, .] copies of the tape.  backward runs the agent's HIP VJP (Engine.vjp) and returns
-    copies of its gradient slice."""
+    the forward's x / desc, the tape arrays to hand out), the caller's data and desc tensors under ``input_grad`` (None otherwise,
+    and None for an agent that does not read the input: data belongs to the sender, desc to the receiver) and the agent's
+    parameters; outputs: the agent's differentiable outputs stacked over the executed steps, [n, B, .] copies of the tape.
+    backward runs the agent's HIP VJP (Engine.vjp) and returns copies of its gradient slice -- and, where autograd asks for them,
+    d data / d desc, formed right behind the VJP from the deltas it left (Engine.input_grads)."""
     AGENT = None
     KEYS = ()          # Engine.vjp keyword of each output's gradient
 
     @staticmethod
-    def forward(ctx, spec, *params):
+    def forward(ctx, spec, data, desc, *params):
         ctx.spec = spec
         ctx.set_materialize_grads(False)               # (an unused output: a NULL upstream gradient, i.e. zero)
-        ctx.save_for_backward(*params)                 # a second backward / an in-place update of the parameters raise
+        ctx.save_for_backward(data, desc, *params)     # a second backward / an in-place update of the parameters raise
         return tuple(t.clone() for t in spec["outs"])
+
+    @staticmethod
+    def _input_grads(ctx, saved):
+        """(d data, d desc) of the VJP that has just run, None where autograd does not ask."""
+        want_dx, want_dd = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_dx or want_dd):
+            return None, None
+        dx, dd = ctx.spec["eng"].input_grads(ctx.spec["n"], want_dx, want_dd)
+        return _input_grad(dx, saved[0]), _input_grad(dd, saved[1])
 
     @classmethod
     def _backward(cls, ctx, grads):
-        ctx.saved_tensors                              # (raises once freed: backward through this node a second time)
+        saved = ctx.saved_tensors                      # (raises once freed: backward through this node a second time)
         spec = ctx.spec
         eng = spec["eng"]
         if eng.generation != spec["gen"]:
@@ -37,7 +53,7 @@ class _AgentVJP(torch.autograd.Function):
         eng.vjp(cls.AGENT, spec["n"], spec["x"], spec["desc"],
                 **{k: g for k, g in zip(cls.KEYS, grads) if g is not None})
         views = eng.grads[cls.AGENT]
-        return (None,) + tuple(views[name].clone() for name in spec["names"])
+        return (None,) + cls._input_grads(ctx, saved) + tuple(views[name].clone() for name in spec["names"])
 
 
 class _SenderVJP(_AgentVJP):
@@ -81,20 +97,20 @@ class _ChannelVJP(_AgentVJP):
     two agents are not detached (``channel_grad``; the reference detaches them, model.py:807-811, 826-829).  Inputs: a spec as
     _AgentVJP's and the sender's, then the receiver's parameters; outputs: what _SenderVJP and _ReceiverVJP hand out together
     (pz | z logits, y, ps, pw | w logits, stacked over the executed steps).  backward runs Engine.vjp_channel ONCE and returns
-    copies of both agents' gradient slices."""
+    copies of both agents' gradient slices; under ``input_grad`` d data and d desc too, with the channel's cross terms."""
     KEYS = ("dz", "dy", "dps", "dw")
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        ctx.saved_tensors                              # (raises once freed: backward through this node a second time)
+        saved = ctx.saved_tensors                      # (raises once freed: backward through this node a second time)
         spec = ctx.spec
         eng = spec["eng"]
         if eng.generation != spec["gen"]:
             raise RuntimeError("the exchange tape this sender-receiver node was recorded on has been overwritten by a later "
                                "engine call (exchange / train_step / forward): call backward() before the next one")
         eng.vjp_channel(spec["n"], spec["x"], spec["desc"], **{k: g for k, g in zip(_ChannelVJP.KEYS, grads) if g is not None})
-        return (None,) + tuple(eng.grads[agent][name].clone() for agent, name in spec["names"])
+        return (None,) + _AgentVJP._input_grads(ctx, saved) + tuple(eng.grads[agent][name].clone() for agent, name in spec["names"])
 
 
 class FlatOptimizer(object):
@@ -213,10 +229,11 @@ class Game(object):
     handle per (batch size, number of classes).
 
     autograd=True: training exchange() calls return outputs that carry autograd graphs (see exchange()).
-    channel_grad=True (with autograd): the sender and the receiver are ONE graph there, gradients cross the channel."""
+    channel_grad=True (with autograd): the sender and the receiver are ONE graph there, gradients cross the channel.
+    input_grad=True (with autograd): data and desc are differentiable inputs of exchange() and desc of Receiver.forward()."""
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
-                 channel_grad=False):
+                 channel_grad=False, input_grad=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -234,6 +251,7 @@ class Game(object):
         self.seed = seed
         self.autograd = bool(autograd)
         self.channel_grad = bool(channel_grad)
+        self.input_grad = bool(input_grad)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -308,11 +326,20 @@ class Game(object):
         mmg_exchange_vjp_channel): the messages are not detached, so a loss on ``y`` alone trains the sender too.  Continuous
         messages: the exact gradient through the logits.  Binary: the straight-through estimator, z = pz + stopgrad(bits - pz),
         w = pw + stopgrad(bits - pw).  Same outputs, same values, same rules; the baselines keep their own nodes, the stop bit
-        stays a constant.  Without autograd being active the option changes nothing."""
+        stays a constant.  Without autograd being active the option changes nothing.
+
+        Input gradients (opt-in on top of autograd, combines with channel_grad): with ``exchange_args["input_grad"] = True`` (or
+        ``Game(..., input_grad=True)``) ``exchange_args["data"]`` and ``exchange_args["desc"]`` are tensor inputs of the nodes:
+        where they require grad, backward() also returns d data (from the sender's node) and d desc (from the receiver's; both
+        from the joint node under channel_grad) in their own shape, dtype and device (include/mmg.h: mmg_vjp_input_grads), so
+        that an encoder in front of ``data`` or an embedding table behind ``desc`` trains with the agents.  softmax(y) inside dbar
+        stays a constant (model.py:441); baseline_sen reads h_x detached (model.py:835).  Without the option, or without autograd
+        being active, both stay constants and nothing changes."""
         data, target, desc = exchange_args["data"], exchange_args.get("target"), exchange_args["desc"]
         train = exchange_args["train"]
         break_early = exchange_args.get("break_early", False)
         autograd = bool(exchange_args.get("autograd", self.autograd)) and bool(train) and torch.is_grad_enabled()
+        inputs = (data, desc) if autograd and bool(exchange_args.get("input_grad", self.input_grad)) else (None, None)
         if autograd and self.world > 1:
             raise NotImplementedError("autograd through exchange() runs on one GPU only (data-parallel training: Game.train_step)")
         corrupt_mask = None
@@ -328,8 +355,8 @@ class Game(object):
         B = data.size(0)
         eng = self.engine_for(B, desc.size(0))
         dev = eng.device
-        data = data.to(dev, torch.float32).contiguous().view(B, -1)
-        desc = desc.to(dev, torch.float32).contiguous()
+        data = data.detach().to(dev, torch.float32).contiguous().view(B, -1)
+        desc = desc.detach().to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
         self._call += 1
         # exchange_args["uniforms"] (training): (u_z [T, B, W], u_s [T, B], u_w [T, B, W]) in place of the Philox stream -- the
@@ -354,7 +381,7 @@ class Game(object):
         self.modules["receiver"].h_z = tp["h"][n]
         self.modules["receiver"].h_w = tp["g"][n - 1]
         if autograd:
-            return self._exchange_graph(eng, data, desc, n, masks, bool(exchange_args.get("channel_grad", self.channel_grad)))
+            return self._exchange_graph(eng, data, desc, n, masks, bool(exchange_args.get("channel_grad", self.channel_grad)), inputs)
         s = (masks, [tp["s"][t].clone() for t in range(n)], [tp["ps"][t].clone() for t in range(n)])
         sen_w = ([tp["z"][t].clone() for t in range(n)], [tp["pz"][t].clone() if binary else None for t in range(n)])
         rec_w = ([tp["w"][t].clone() for t in range(n)], [tp["pw"][t].clone() if binary else None for t in range(n)])
@@ -363,26 +390,29 @@ class Game(object):
         br = [tp["br"][t].clone() for t in range(n)] if train and binary else []
         return s, sen_w, rec_w, y, bs, br
 
-    def _exchange_graph(self, eng, data, desc, n, masks, channel=False):
+    def _exchange_graph(self, eng, data, desc, n, masks, channel=False, inputs=(None, None)):
         """exchange()'s return structure with the four agents' autograd nodes (training, run-all tape of this call).
-        channel: the sender and the receiver share one node (_ChannelVJP)."""
+        channel: the sender and the receiver share one node (_ChannelVJP).  inputs: the caller's (data, desc) tensors under
+        input_grad -- tensor inputs of the sender's / the receiver's / the joint node."""
         tp, binary = eng.tape, self.cfg["use_binary"]
+        data_in, desc_in = inputs
 
-        def node(fn, agent, outs):
+        def node(fn, agent, outs, data_in=None, desc_in=None):
             mod = self.modules[agent]
             names = [name for name, _ in mod.named_parameters()]
             spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=names, outs=outs)
-            return fn.apply(spec, *[p for _, p in mod.named_parameters()])
+            return fn.apply(spec, data_in, desc_in, *[p for _, p in mod.named_parameters()])
 
         if channel:
             named = [(a, name, p) for a in ("sender", "receiver") for name, p in self.modules[a].named_parameters()]
             spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=[(a, name) for a, name, _ in named],
                         outs=[tp["pz" if binary else "z"][:n], tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
-            sen_st, y_st, ps_st, w_st = _ChannelVJP.apply(spec, *[p for _, _, p in named])
+            sen_st, y_st, ps_st, w_st = _ChannelVJP.apply(spec, data_in, desc_in, *[p for _, _, p in named])
             sen = sen_st.unbind(0)
         else:
-            sen = node(_SenderVJP, "sender", [tp["pz" if binary else "z"][:n]])[0].unbind(0)
-            y_st, ps_st, w_st = node(_ReceiverVJP, "receiver", [tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
+            sen = node(_SenderVJP, "sender", [tp["pz" if binary else "z"][:n]], data_in=data_in)[0].unbind(0)
+            y_st, ps_st, w_st = node(_ReceiverVJP, "receiver", [tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]],
+                                     desc_in=desc_in)
         ps, rw, y = ps_st.unbind(0), w_st.unbind(0), list(y_st.unbind(0))
         s = (masks, [tp["s"][t].clone() for t in range(n)], list(ps))
         if binary:
