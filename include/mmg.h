@@ -172,6 +172,30 @@ int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64_t* d_targe
  * Returns 0, or negative for n != w_dim or an entry other than 0 / 1 (the mask set before stays). */
 int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, int n);
 
+/* Random message flips, the noisy channel of -flipout_sen / -flipout_rec / -flipout_dev (model.py:233-234, 467-468, 554-568).
+ * has_sen / has_rec: the sender's / the receiver's message flips with probability p_sen / p_rec in [0, 1]; both zero clears the
+ * setting.  Binary messages only (use_binary == 0: accepted, nothing happens -- the reference does not flip continuous messages).
+ * While it is set, every later forward entry (mmg_exchange_forward, mmg_train_step[s], mmg_dp_train_step[s], mmg_eval_steps,
+ * mmg_sender_forward, mmg_receiver_forward) replaces a message bit, right after it was sampled (training) or rounded
+ * (evaluation), by |bit - m| with m = 1 iff a uniform draw lies below the probability (a float32 compare: p = 0 never flips,
+ * p = 1 always).  Training conversations always flip; evaluation conversations only with flipout_dev != 0.  The flipped bit is
+ * what everything downstream reads: the other agent, both baselines, the tape arrays "z" / "w" / "zr", the log-likelihood
+ * sums "lp_z" / "lp_w" (model.py:908-910 scores the returned bits), the backward pass and mmg_eval_steps' Hamming counts;
+ * "pz" / "pw" and the entropy terms stay functions of the logits.  A mask of mmg_set_message_corruption is applied after the flip.
+ * Draws: philox_uniform(key, e, c1, stream) at the element index of the Bernoulli draws, e = (t * B_global + batch_offset + b) * W
+ * + j, so a data-parallel shard draws what the single-GPU batch draws.
+ *   training:   streams 3 (sender) / 4 (receiver), key = the call's seed, c1 = the minibatch counter of the Bernoulli draws --
+ *               also when d_u_z / d_u_s / d_u_w are injected;
+ *   evaluation: streams 5 / 6, key = eval_seed, c1 = the number of evaluation conversations enqueued on this handle since this
+ *               call (counted on the host; the device-side minibatch counter stays untouched).  The agent-level entries draw
+ *               with the count of the conversation the last mmg_sender_forward(t = 0, train = 0) began.
+ * Kernels: a flipping handle runs the register-resident k_conversation_fast3 chain (configs 1-3's agents; mmg_train_step then
+ * launches k_conversation_fast3 + k_bwd_conv_fast + k_wgrad instead of the one-launch k_game_fast) or the generic per-sample
+ * kernels (every other shape: the many-class, sample-tile and wide-receiver kernels do not flip).  The call re-runs the kernel
+ * selection and does no other GPU work; clearing restores the original selection.
+ * Returns 0, or negative for a probability outside [0, 1] or NaN (the setting before stays). */
+int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec, float p_rec, int flipout_dev, uint64_t eval_seed);
+
 /* Dev evaluation inside the library (eval_dev's loop body, model.py:620-691): n consecutive evaluation conversations, each
  * followed on the same stream by ONE reduction launch (k_eval_reduce) that leaves what the reference computes per dev batch
  * on the host -- as integers, so the results do not depend on any summation order and are bit-reproducible.

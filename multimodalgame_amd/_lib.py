@@ -49,7 +49,7 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_log_snapshot_count", "mmg_log_snapshot", "mmg_set_message_corruption", "mmg_exchange_vjp",
            "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps",
            "mmg_loss_save_doubles", "mmg_loss_binary_forward", "mmg_loss_binary_vjp", "mmg_loss_bas_forward", "mmg_loss_bas_vjp",
-           "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads"]
+           "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads", "mmg_set_message_flipout"]
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
 EVAL_ACC_HEAD = 4
@@ -85,6 +85,7 @@ def load():
     lib.mmg_eval_acc_count.restype = i64; lib.mmg_eval_acc_count.argtypes = [cfgp]
     lib.mmg_eval_steps.restype = i32; lib.mmg_eval_steps.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp]
     lib.mmg_set_message_corruption.restype = i32; lib.mmg_set_message_corruption.argtypes = [vp, vp, i32]
+    lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
     lib.mmg_exchange_vjp.restype = i32; lib.mmg_exchange_vjp.argtypes = [vp, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_exchange_vjp_channel.restype = i32; lib.mmg_exchange_vjp_channel.argtypes = [vp, i32, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_vjp_input_grads.restype = i32; lib.mmg_vjp_input_grads.argtypes = [vp, i32, i32, fp, fp, fp, vp]

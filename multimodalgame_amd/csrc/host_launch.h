@@ -43,7 +43,8 @@ struct LaunchPlan {
     bool mc3p_wins = false;                     // the pair kernel needs fewer rounds (at the call: lean)
     bool merge_prep = false, fwd_basehx = false;         // k_prep's blocks / the basehx tiles as roles of the conversation launch (basehx at the call: train && !all rows)
     decltype(&k_conversation_fast3<256, 32, 64, 100, false>) fast_fn = nullptr;
-    decltype(&k_conversation<256>) conv_fn = nullptr;
+    decltype(&k_conversation<256>) conv_fn = nullptr, agent_fn = nullptr;   // whole conversation / the agent-level entries' step window (k_conversation<256>)
+    int fast_smem = 0;                          // dynamic LDS of fast_fn
     const char *conv_name = "k_conversation", *bwd_name = "k_bwd_conv";
     bool bas_defer_ok = false, bas_pending_ok = false;   // roles of the backward launch (fused step) / of k_bas_stats (phased step)
     BasKernel bas_kernel = BAS_ALL2;
@@ -73,6 +74,7 @@ struct Selection {
     int game_nbas = 0;           // ... its baseline roles (a multiple of 2 * ceil(K / 64), sized by the co-residency budget)
     int wgrad_stride = 0;        // > 0: k_wgrad's GEMM tiles are walked by this many resident workgroups (more tiles than slots); 0: one workgroup per tile
     bool wgrad_opt_ok = false;   // the clip + optimizer step can run inside k_wgrad's launch (k_wgrad<true>: every block co-resident, no row splits); MMG_NO_WGRAD_OPT=1: off
+    bool flip = false;           // message flips are set on a binary handle (mmg_set_message_flipout): k_conversation_fast3<FLIP> / k_conversation<FLIP> serve it, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
     bool merge_roles = false;    // MMG_NO_MERGE=1 keeps k_stats / k_dC / basehx as separate launches / in-kernel work
     // sample-tile MFMA path (kernels_tile.h): every shape the register-resident kernels do not cover
@@ -146,6 +148,12 @@ struct mmg_handle {
     // while it is set, the training entries refuse to run
     bool corrupt_on = false;
     uint32_t corrupt[MMG_BLOCK / 32] = {};
+    // mmg_set_message_flipout: random flips of the message bits (model.py:554-568).  Host state; flip_args copies it into the launch
+    // arguments of every forward entry.  flip_evals: evaluation conversations enqueued since the setter call (their Philox counter)
+    bool flip_sen = false, flip_rec = false, flip_dev = false;
+    float flip_p_sen = 0.f, flip_p_rec = 0.f;
+    uint64_t flip_eval_seed = 0;
+    uint32_t flip_evals = 0;
     WgHead vjp_hd[8] = {};       // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
     ~mmg_handle() {
         for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }

@@ -114,7 +114,16 @@ static void plan_launches(mmg_handle* h) {
     const bool wide = fam == FAM_FAST && d.V != 100;
     p.fast_fn = wide ? (p.merge_prep ? k_conversation_fast3<256, 32, 64, 0, true> : k_conversation_fast3<256, 32, 64, 0, false>)
                      : (p.merge_prep ? k_conversation_fast3<256, 32, 64, 100, true> : k_conversation_fast3<256, 32, 64, 100, false>);
+    p.fast_smem = fast3_lds_bytes();
     p.conv_fn = s.conv_threads == 512 ? k_conversation<512> : k_conversation<256>;
+    p.agent_fn = k_conversation<256>;
+    if (s.flip) {                                // message flips: the FLIP instantiations (select_paths has cleared every other conversation kernel)
+        p.fast_fn = wide ? (p.merge_prep ? k_conversation_fast3<256, 32, 64, 0, true, true> : k_conversation_fast3<256, 32, 64, 0, false, true>)
+                         : (p.merge_prep ? k_conversation_fast3<256, 32, 64, 100, true, true> : k_conversation_fast3<256, 32, 64, 100, false, true>);
+        p.fast_smem = fast3_flip_lds_bytes();
+        p.conv_fn = s.conv_threads == 512 ? k_conversation<512, true> : k_conversation<256, true>;
+        p.agent_fn = k_conversation<256, true>;
+    }
     p.conv_name = wide ? "k_conversation_wv" : "k_conversation";
     p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
     // ---- baselines (training minibatch that did not run all rows) ----
@@ -206,12 +215,14 @@ static int select_paths(mmg_handle* h) {
     const mmg_config& cfg = h->cfg; const Dims& d = h->dm; const bool no_roles = h->no_roles;
     h->sel = Selection();
     Selection& s = h->sel;
+    // message flips on binary messages (continuous ones are not flipped: the setting is kept and nothing happens)
+    s.flip = (h->flip_sen || h->flip_rec) && d.use_binary;
     s.use_fast = !getenv("MMG_NO_FAST"); s.merge_roles = !getenv("MMG_NO_MERGE") && !no_roles;
     s.sw_merge_prep = !getenv("MMG_NO_MERGE_PREP") && !no_roles;
     s.sw_merge_bas = s.merge_roles;
     s.persist_ll = !getenv("MMG_NO_PERSIST_LL") && persist_ll_shape(cfg.batch, cfg.h_dim, cfg.w_dim, cfg.rec_hidden, cfg.wv_dim, cfg.n_classes, cfg.max_exchange);
     s.sw_rsample = !getenv("MMG_NO_RSAMPLE"); s.sw_rmsg = !getenv("MMG_NO_RMSG"); s.sw_fused_s = !getenv("MMG_NO_FUSED_S");
-    s.mc_ok = s.use_fast && mc_shape(d.H, d.W, d.R, d.V, d.D, d.T) && !getenv("MMG_NO_MC") && !no_roles;
+    s.mc_ok = s.use_fast && mc_shape(d.H, d.W, d.R, d.V, d.D, d.T) && !getenv("MMG_NO_MC") && !no_roles && !s.flip;
     s.mc_per = (((d.D + 15) / 16) + 3) & ~3;
     s.mc_xcd = 1;                                   // a tile's 16 workgroups on one XCD (measured at config 5, 256 samples: 192 us per minibatch against 201); cleared below on a device without room for it
     int n_cu = 0;
@@ -269,7 +280,8 @@ static int select_paths(mmg_handle* h) {
         s.rc_fwd = aligned && s.tile_ext && s.tile_smem > 160 * 1024 && rc_shape(d.B, d.H, d.W, d.R, d.V, d.D) && !getenv("MMG_NO_RC");
         // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
         //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
-        s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !getenv("MMG_NO_TILE");
+        // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
+        s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !getenv("MMG_NO_TILE") && !s.flip;
         s.tile_force = getenv("MMG_TILE") != nullptr;
         // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
         // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -353,10 +365,14 @@ static int select_paths(mmg_handle* h) {
     }
     raise_lds(fast3_lds_bytes(), k_conversation_fast3<256, 32, 64, 100, false>, k_conversation_fast3<256, 32, 64, 100, true>);
     if (fast_wide_v(d.V)) raise_lds(fast3_lds_bytes(), k_conversation_fast3<256, 32, 64, 0, false>, k_conversation_fast3<256, 32, 64, 0, true>);
+    if (s.flip) {
+        raise_lds(fast3_flip_lds_bytes(), k_conversation_fast3<256, 32, 64, 100, false, true>, k_conversation_fast3<256, 32, 64, 100, true, true>);
+        if (fast_wide_v(d.V)) raise_lds(fast3_flip_lds_bytes(), k_conversation_fast3<256, 32, 64, 0, false, true>, k_conversation_fast3<256, 32, 64, 0, true, true>);
+    }
     {
         const bool shape = s.use_fast && s.merge_roles && s.sw_merge_prep && s.sw_merge_bas && d.H == 256 && d.W == 32 && d.R == 64 && d.V == 100 &&
                            d.D <= 32 && d.T <= 15 && d.B <= 64 && d.use_binary && !d.fixed && (d.K + 63) / 64 <= 8 && d.K <= 512 &&
-                           !(s.tile_ok && s.tile_force) && s.prep_cpb == 1 && s.prep_smem <= game_lds_bytes() && !getenv("MMG_NO_GAME") && !no_roles;
+                           !(s.tile_ok && s.tile_force) && s.prep_cpb == 1 && s.prep_smem <= game_lds_bytes() && !getenv("MMG_NO_GAME") && !no_roles && !s.flip;
         if (shape && e == hipSuccess) {
             const void* fn = (const void*)game_fast_fn(d.D);
             raise_lds(game_lds_bytes(), fn);
@@ -375,6 +391,7 @@ static int select_paths(mmg_handle* h) {
         }
     }
     if (s.conv_smem > 48 * 1024) raise_lds(s.conv_smem, k_conversation<256>, k_conversation<512>);
+    if (s.conv_smem > 48 * 1024 && s.flip) raise_lds(s.conv_smem, k_conversation<256, true>, k_conversation<512, true>);
     if (s.bwd_smem > 48 * 1024) raise_lds(s.bwd_smem, k_bwd_conv<false>, k_bwd_conv<true>);
     if (e != hipSuccess) return fail("device init failed: %s", hipGetErrorString(e));
     s.family = select_family(s, d);

@@ -93,10 +93,15 @@ struct Fast3Lds {
     static constexpr int total = park + 12 * 256 * 4;
 };
 __host__ __device__ inline int fast3_lds_bytes() { return Fast3Lds::total * 4; }
+// FLIP instantiations: 2 TMAX words behind the plan -- the flip masks of the whole conversation, one 32-bit word per step (W = 32),
+// the sender's message at [t], the receiver's at [TMAX + t]
+__host__ __device__ inline int fast3_flip_lds_bytes() { return (Fast3Lds::total + 2 * Fast3Lds::TMAX) * 4; }
 
 // MERGED: the launch carries k_prep's blocks as leading roles (ar.nprep of them); a compile-time switch -- a runtime branch
 // around the prologue's loads makes hipcc drain them at the join
-template <int H, int W, int R, int V, bool MERGED>
+// FLIP: the instantiations of a handle with message flips (mmg_set_message_flipout; kernels_fwd.h: flip_msg states the rule) --
+// the prologue draws the masks of the whole conversation beside the Bernoulli draws, P2 and P7 apply them
+template <int H, int W, int R, int V, bool MERGED, bool FLIP = false>
 __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P, Tape tp, ConvArgs ar) {
     constexpr int NT = 256, TMAX = Fast3Lds::TMAX;
     static_assert(H == 256 && W == 32 && R == 64 && (V == 0 || (V % 4 == 0 && V <= 128)), "lane maps of k_conversation_fast3; V: a compile-time width, or 0 = the run's width (dm.V)");
@@ -143,6 +148,7 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
     float* const s_us = lds + L::small; float* const s_ps = s_us + 16; float* const s_sb = s_us + 32; float* const s_mask = s_us + 48;
     float* const s_misc = s_us + 65; float* const s_sig = s_us + 80;
     float4* const s_park = reinterpret_cast<float4*>(lds + L::park);
+    [[maybe_unused]] uint32_t* const s_flip = reinterpret_cast<uint32_t*>(lds + L::total);     // (FLIP only: fast3_flip_lds_bytes)
 
     const int b = (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int B = dm.B, T = dm.T, Dr = dm.D;
@@ -259,6 +265,23 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
         }
         if (tid < T) s_us[tid] = philox_uniform(ar.seed, (uint32_t)(tid * dm.Bg + gb), mb_counter, 1u);
     }
+    if constexpr (FLIP) {
+        // flip masks of the whole conversation (training and, under flipout_dev, evaluation: ar.flip_on says which streams), also
+        // while the weight loads are in flight: a wave covers two steps of 32 bits, its ballot holds their two mask words.  Wave-
+        // uniform trip count (whole waves up to T * W); steps beyond T land inside the TMAX words and are never read.
+        const bool fev = (ar.flip_on & 4) != 0;
+        const uint32_t c1 = fev ? ar.flip_c1 : mb_counter, sz = fev ? 5u : 3u;
+        const float fpz = (ar.flip_on & 1) ? ar.flip_pz : 0.f, fpw = (ar.flip_on & 2) ? ar.flip_pw : 0.f;
+        if (ar.flip_on) {
+            for (int i = tid; i < ((T * W + 63) & ~63); i += NT) {
+                const int t = i / W, j = i - t * W;
+                const uint32_t e = (uint32_t)((t * dm.Bg + gb) * W + j);
+                const unsigned long long mz = __ballot(philox_uniform(ar.flip_key, e, c1, sz) < fpz);
+                const unsigned long long mw = __ballot(philox_uniform(ar.flip_key, e, c1, sz + 1u) < fpw);
+                if (j == 0) { s_flip[t] = (uint32_t)(mz >> (lane & 32)); s_flip[TMAX + t] = (uint32_t)(mw >> (lane & 32)); }
+            }
+        } else if (tid < 2 * TMAX) s_flip[tid] = 0u;
+    }
 #pragma unroll
     for (int i = 0; i < 12; ++i) s_park[i * NT + tid] = whh_tmp[i];
     if (merged) {
@@ -313,10 +336,16 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
         // ===== P2 sender logits + sample
         {
             const float uz = s_uz[t * W + m2];
+            uint32_t fzw = 0u;
+            if constexpr (FLIP) fzw = s_flip[t];
             const float lz = dpp_group_sum<8>(dot4p<8>(wb, s_a + t * H + k2 * 4, 32)) + bb;
             const float ps = fsigmoid(lz);
             const float pp = binary ? ps : 0.f;
-            const float zz = corrupt_msg(ar, m2, binary ? (train ? ((uz < ps) ? 1.f : 0.f) : rintf(ps)) : lz);
+            float zz;
+            if constexpr (FLIP)      // |bit - m| (model.py:233-234), then the evaluation mask (model.py:813-820)
+                zz = corrupt_msg(ar, m2, binary ? fabsf((train ? ((uz < ps) ? 1.f : 0.f) : rintf(ps)) - (float)((fzw >> m2) & 1u)) : lz);
+            else
+                zz = corrupt_msg(ar, m2, binary ? (train ? ((uz < ps) ? 1.f : 0.f) : rintf(ps)) : lz);
             if (k2 == 0) { s_z[t * W + m2] = zz; s_pz[t * W + m2] = pp; }
         }
         __syncthreads(); MMG_STAMP(8 + 10 * t + 1);
@@ -404,12 +433,16 @@ __global__ __launch_bounds__(256, 1) void k_conversation_fast3(Dims dm, Params P
         // ===== P7 receiver message
         {
             const float uw = s_uw[t * W + m2];
+            uint32_t fww = 0u;
+            if constexpr (FLIP) fww = s_flip[TMAX + t];
             float4 pk[4], hq[4];
             park_load(pk, hq, s_park, 2, tid, hn + q3 * 16);
             const float lw = dpp_group_sum<8>(dot4p<2>(ww, s_g + t * R + k2 * 8, 4)) + bw;
             const float ps = fsigmoid(lw);
             const float pp = binary ? ps : 0.f;
-            const float wv = binary ? (train ? ((uw < ps) ? 1.f : 0.f) : rintf(ps)) : lw;
+            float wv;
+            if constexpr (FLIP) wv = binary ? fabsf((train ? ((uw < ps) ? 1.f : 0.f) : rintf(ps)) - (float)((fww >> m2) & 1u)) : lw;   // model.py:467-468
+            else wv = binary ? (train ? ((uw < ps) ? 1.f : 0.f) : rintf(ps)) : lw;
             ghn = dpp_group_sum<4>(park_fma(pk, hq)) + b_hn;
             if (k2 == 0) { s_w[(t + 1) * W + m2] = wv; s_pw[t * W + m2] = pp; }
         }

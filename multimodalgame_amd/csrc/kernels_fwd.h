@@ -377,6 +377,13 @@ struct ConvArgs {
     // m = bit j of corrupt[j / 32]; by value, so a wave-uniform kernel argument (0: nothing applied)
     int corrupt_on;
     uint32_t corrupt[MMG_BLOCK / 32];
+    // mmg_set_message_flipout: random bit flips of the messages (model.py:233-234, 467-468, 554-568), binary messages only.  By value,
+    // filled per call by the host (0: nothing applied): bit 0 the sender's message flips, bit 1 the receiver's, bit 2 the draws are an
+    // EVALUATION conversation's (streams 5 / 6, counter flip_c1 counted on the host; else streams 3 / 4 and the minibatch counter)
+    int flip_on;
+    float flip_pz, flip_pw;    // flip probabilities of the sender's / the receiver's message bits
+    uint32_t flip_c1;          // evaluation: conversations enqueued on the handle since the setter call
+    uint64_t flip_key;         // Philox key of the flip draws: the call's seed (training) / the setter's eval_seed
 };
 
 // the reference's corruption of message entry j, literally |z - m_j| in fp32 (model.py:818): exact XOR for z in {0, 1}, and in
@@ -388,6 +395,18 @@ __device__ __forceinline__ float corrupt_msg(const ConvArgs& ar, int j, float z)
     if (!ar.corrupt_on) return z;
     const uint32_t w = ar.corrupt[(j >> 5) & (MMG_BLOCK / 32 - 1)];      // (j < W <= MMG_BLOCK; the mask keeps the load inside)
     return fabsf(z - (float)((w >> (j & 31)) & 1u));
+}
+
+// flipout (model.py:554-568) of message entry e = (t * B_global + b_global) * W + j: |z - m|, m = 1 iff a uniform draw of the flip
+// stream lies below the flip probability (a float32 compare: p = 0 never flips, p = 1 always).  Call it right behind the sample /
+// the rounding, BEFORE the log-likelihood term, the tape and anything another consumer reads; corrupt_msg comes after it
+// (exchange() applies its mask to what the sender returned).  rec: the receiver's message (bit 1, streams 4 / 6), else the
+// sender's (bit 0, streams 3 / 5).  mb: the minibatch counter of the kernel's Bernoulli draws.
+__device__ __forceinline__ float flip_msg(const ConvArgs& ar, bool rec, uint32_t e, uint32_t mb, float z) {
+    if (!(ar.flip_on & (rec ? 2 : 1))) return z;
+    const bool ev = (ar.flip_on & 4) != 0;
+    const float u = philox_uniform(ar.flip_key, e, ev ? ar.flip_c1 : mb, (ev ? 5u : 3u) + (rec ? 1u : 0u));
+    return fabsf(z - ((u < (rec ? ar.flip_pw : ar.flip_pz)) ? 1.f : 0.f));
 }
 
 struct ConvSmem {
@@ -409,7 +428,9 @@ __global__ __launch_bounds__(64) void k_xcc_probe(uint32_t* __restrict__ out) {
     if (threadIdx.x == 0) out[blockIdx.x] = xcc_id();
 }
 
-template <int NT>
+// FLIP: the instantiations a handle with message flips runs (flip_msg at both message sites); a compile-time switch, so that
+// the kernels of every other handle stay what they were
+template <int NT, bool FLIP = false>
 __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp, ConvArgs ar) {
     constexpr int GU = NT == 512 ? 8 : 4;               // row passes per load batch of gemv_rows
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -501,6 +522,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                         } else {
                             zz = rintf(p);                         // model.py:229 (torch.round = half-to-even)
                         }
+                        if (FLIP) zz = flip_msg(ar, false, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, zz);   // model.py:233-234
                         tp.pz[row * W + n] = p;
                         const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
                         lpv = zz * l1 + (1.f - zz) * l0;           // model.py:908-910
@@ -674,6 +696,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                     } else {
                         wv = rintf(p);                             // model.py:462
                     }
+                    if (FLIP) wv = flip_msg(ar, true, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, wv);       // model.py:467-468
                     tp.pw[row * W + n] = p;
                     const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
                     lpv = wv * l1 + (1.f - wv) * l0;

@@ -293,6 +293,17 @@ static ConvArgs conv_args(const mmg_handle* h, const float* d_x, const int64_t* 
     return ar;
 }
 
+// Message flips of this call (mmg_set_message_flipout), by value: training conversations always, evaluation ones under flipout_dev.
+// new_conv: the call enqueues a whole evaluation conversation (it takes the next evaluation count); the agent-level entries draw
+// with the count of the conversation the last mmg_sender_forward(t = 0) began.
+static void flip_args(mmg_handle* h, ConvArgs& ar, uint64_t seed, int train, bool new_conv) {
+    if (!h->sel.flip || (!train && !h->flip_dev)) return;
+    ar.flip_on = (h->flip_sen ? 1 : 0) | (h->flip_rec ? 2 : 0) | (train ? 0 : 4);
+    ar.flip_pz = h->flip_p_sen; ar.flip_pw = h->flip_p_rec;
+    ar.flip_key = train ? seed : h->flip_eval_seed;
+    if (!train) ar.flip_c1 = new_conv ? h->flip_evals++ : (h->flip_evals ? h->flip_evals - 1u : 0u);
+}
+
 // FAM_TILE: one of the plan's seven outcomes (host_select.h: plan_launches).  The outcome is known BEFORE a timing scope opens.
 static int launch_conv_tile(mmg_handle* h, hipStream_t st, ConvArgs ar) {
     const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
@@ -377,7 +388,7 @@ static int launch_conv_sample(mmg_handle* h, hipStream_t st, ConvArgs ar, bool b
     Scope sc(h, st, p.conv_name);
     if (s.family == FAM_FAST) {
         ar.nprep = p.merge_prep ? p.nprep_hx : 0; ar.prep_cpb = s.prep_cpb; ar.nbase = base_ready ? p.basehx_tiles : 0;
-        hipLaunchKernelGGL(p.fast_fn, dim3(d.B + ar.nbase + (p.merge_prep ? ar.nprep + 1 : 0)), dim3(256), fast3_lds_bytes(), st, h->dm, h->P, h->tp, ar);
+        hipLaunchKernelGGL(p.fast_fn, dim3(d.B + ar.nbase + (p.merge_prep ? ar.nprep + 1 : 0)), dim3(256), p.fast_smem, st, h->dm, h->P, h->tp, ar);
     } else
         hipLaunchKernelGGL(p.conv_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar);
     return launch_check("k_conversation");
@@ -419,6 +430,7 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
     ar.y_last_only = (mode == TAPE_MINIMAL && d.fixed) ? 1 : 0;
     ar.lean = (mode == TAPE_MINIMAL && !d.use_binary) ? 1 : 0;
     if (h->corrupt_on) { ar.corrupt_on = 1; memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt)); }
+    flip_args(h, ar, seed, train, true);
     h->fwd = ForwardState();
     const bool base_ready = p.fwd_basehx && bas && !all_rows;
     switch (s.family) {
@@ -486,6 +498,34 @@ extern "C" int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, in
     }
     memcpy(h->corrupt, words, sizeof(words));
     h->corrupt_on = true;
+    return 0;
+}
+
+// Random message flips (include/mmg.h): host state; re-runs the selection, since a flipping handle is served by k_conversation_fast3 /
+// k_conversation only (host_select.h).  The job table goes to the device again only where the family changed it.
+extern "C" int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec, float p_rec, int flipout_dev, uint64_t eval_seed) {
+    if (!h) return fail("NULL handle");
+    if (has_sen && !(p_sen >= 0.f && p_sen <= 1.f)) return fail("mmg_set_message_flipout: p_sen = %g is not a probability in [0, 1]", (double)p_sen);
+    if (has_rec && !(p_rec >= 0.f && p_rec <= 1.f)) return fail("mmg_set_message_flipout: p_rec = %g is not a probability in [0, 1]", (double)p_rec);
+    const bool o_sen = h->flip_sen, o_rec = h->flip_rec, o_dev = h->flip_dev; const float o_ps = h->flip_p_sen, o_pr = h->flip_p_rec;
+    const uint64_t o_seed = h->flip_eval_seed; const uint32_t o_evals = h->flip_evals;
+    auto set = [&](bool sen, float ps, bool rec, float pr, bool dev, uint64_t sd, uint32_t ev) {
+        h->flip_sen = sen; h->flip_p_sen = sen ? ps : 0.f; h->flip_rec = rec; h->flip_p_rec = rec ? pr : 0.f;
+        h->flip_dev = dev && (sen || rec); h->flip_eval_seed = sd; h->flip_evals = ev;
+    };
+    set(has_sen != 0, p_sen, has_rec != 0, p_rec, flipout_dev != 0, eval_seed, 0u);
+    if (((h->flip_sen || h->flip_rec) && h->dm.use_binary) == h->sel.flip) return 0;        // same routing: nothing to select
+    const JobTable old = h->jt;
+    if (select_paths(h)) {
+        const std::string why = g_err;
+        set(o_sen, o_ps, o_rec, o_pr, o_dev, o_seed, o_evals);
+        select_paths(h);
+        return fail("mmg_set_message_flipout: %s", why.c_str());
+    }
+    if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
+        HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
+        HIP_OK(hipMemcpy(h->d_jt, &h->jt, sizeof(JobTable), hipMemcpyHostToDevice));
+    }
     return 0;
 }
 
@@ -795,7 +835,9 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
     memset(&ar, 0, sizeof(ar));
     ar.x = d_x; ar.u_z = d_u_z ? d_u_z - (size_t)t * d.B * d.W : nullptr; ar.seed = seed; ar.train = train; ar.run_all = 1;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 1; ar.w_in = d_w;
-    hipLaunchKernelGGL(k_conversation<256>, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
+    flip_args(h, ar, seed, train, false);
+    if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
+    hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(sender)")) return -1;
     const size_t off = (size_t)t * d.B * d.W;
     HIP_OK(hipMemcpyAsync(d_message, h->tp.z + off, sizeof(float) * d.B * d.W, hipMemcpyDeviceToDevice, st));
@@ -822,7 +864,8 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
     ar.desc = d_desc; ar.seed = seed; ar.train = train; ar.run_all = 1;
     ar.u_s = d_u_s ? d_u_s - offB : nullptr; ar.u_w = d_u_w ? d_u_w - offW : nullptr;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 2; ar.h_state = d_h_z; ar.sprod_state = d_s_prob_prod; ar.sprod_first = first;
-    hipLaunchKernelGGL(k_conversation<256>, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
+    flip_args(h, ar, seed, train, false);
+    hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(receiver)")) return -1;
     if (d_s) HIP_OK(hipMemcpyAsync(d_s, h->tp.s + offB, sizeof(float) * d.B, hipMemcpyDeviceToDevice, st));
     if (d_s_prob) HIP_OK(hipMemcpyAsync(d_s_prob, h->tp.ps + offB, sizeof(float) * d.B, hipMemcpyDeviceToDevice, st));

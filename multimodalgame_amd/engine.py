@@ -154,6 +154,18 @@ class Engine(object):
             cached = self._corrupt_buf = (key, (C.c_uint8 * a.size)(*[int(v) for v in a.tolist()]))
         _lib.check(self.lib.mmg_set_message_corruption(self.handle, cached[1], len(cached[1])))
 
+    def set_message_flipout(self, p_sen=None, p_rec=None, dev=False, eval_seed=0):
+        """Random flips of the message bits, the reference's -flipout_sen / -flipout_rec / -flipout_dev (model.py:554-568;
+        include/mmg.h: mmg_set_message_flipout).  p_sen / p_rec: flip probability of every bit of the sender's / the receiver's
+        message, None = that message is not flipped; both None clears the setting.  dev: evaluation conversations flip too (their
+        draws are keyed by eval_seed and a count of the evaluation conversations since this call).  Holds for every later
+        forward entry of this engine (forward, train_step(s), dp_train_step(s), eval_steps, sender_forward, receiver_forward);
+        binary messages only.  Host only: the library re-selects its kernels, no GPU work."""
+        _lib.check(self.lib.mmg_set_message_flipout(
+            self.handle, int(p_sen is not None), float(p_sen if p_sen is not None else 0.0), int(p_rec is not None),
+            float(p_rec if p_rec is not None else 0.0), int(bool(dev)), C.c_uint64(int(eval_seed) & 0xFFFFFFFFFFFFFFFF)))
+        self.flipout = None if p_sen is None and p_rec is None else (p_sen, p_rec, bool(dev))
+
     def loss_stats(self):
         _lib.check(self.lib.mmg_loss_stats(self.handle, self._stream()))
 

@@ -253,8 +253,8 @@ UNSUPPORTED = (
     # (flag, predicate on its value and the flags object, reference lines that read it)
     ("desc_attn", lambda v, fl: bool(v), "model.py:344-409 (description attention)"),
     ("sender_mix", lambda v, fl: v not in (None, "sum"), "model.py:201-214 (prod / mou mixing of h_x and h_w)"),
-    ("flipout_sen", lambda v, fl: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message)"),
-    ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message)"),
+    ("flipout_sen", lambda v, fl: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message; the library option: Game(..., flipout_sen=P))"),
+    ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message; the library option: Game(..., flipout_rec=P))"),
     ("ignore_receiver", lambda v, fl: bool(v), "model.py:217-218 (sender ignores the receiver's message)"),
     ("ignore_code", lambda v, fl: bool(v), "model.py:219-221 (sender ignores its code input)"),
     ("visual_attn", lambda v, fl: bool(v), "model.py:114-191 (visual attention over layer4_2)"),

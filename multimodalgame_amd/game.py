@@ -230,10 +230,14 @@ class Game(object):
 
     autograd=True: training exchange() calls return outputs that carry autograd graphs (see exchange()).
     channel_grad=True (with autograd): the sender and the receiver are ONE graph there, gradients cross the channel.
-    input_grad=True (with autograd): data and desc are differentiable inputs of exchange() and desc of Receiver.forward()."""
+    input_grad=True (with autograd): data and desc are differentiable inputs of exchange() and desc of Receiver.forward().
+    flipout_sen / flipout_rec (a probability, None: off) and flipout_dev: the reference's noisy channel (model.py:233-234, 467-468,
+    554-568) -- every bit of the sender's / the receiver's message is inverted with that probability right after it is sampled,
+    in training conversations always, in evaluation ones under flipout_dev; everything downstream reads the flipped bits
+    (Engine.set_message_flipout).  These keyword arguments are separate from `flags`, whose -flipout_* switches stay refused."""
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
-                 channel_grad=False, input_grad=False):
+                 channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -252,6 +256,12 @@ class Game(object):
         self.autograd = bool(autograd)
         self.channel_grad = bool(channel_grad)
         self.input_grad = bool(input_grad)
+        for name, p in (("flipout_sen", flipout_sen), ("flipout_rec", flipout_rec)):
+            if p is not None and not 0.0 <= float(p) <= 1.0:             # (NaN fails both compares)
+                raise ValueError("%s = %r is not a probability in [0, 1]" % (name, p))
+        self.flipout = None if flipout_sen is None and flipout_rec is None else (flipout_sen, flipout_rec, bool(flipout_dev))
+        if self.flipout and self.channel_grad:
+            raise NotImplementedError("channel_grad with message flips: the straight-through surrogate under a flip is not defined")
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -296,6 +306,8 @@ class Game(object):
         if key not in self.engines:
             eng = Engine(device=self.device, share=self.engine, batch=batch, n_classes=n_classes,
                          global_batch=global_batch, batch_offset=batch_offset, **self.cfg)
+            if self.flipout:
+                eng.set_message_flipout(self.flipout[0], self.flipout[1], dev=self.flipout[2], eval_seed=self.seed)
             if self.engine is None:
                 self.engine = eng
                 self._adopt(eng)
@@ -340,6 +352,8 @@ class Game(object):
         break_early = exchange_args.get("break_early", False)
         autograd = bool(exchange_args.get("autograd", self.autograd)) and bool(train) and torch.is_grad_enabled()
         inputs = (data, desc) if autograd and bool(exchange_args.get("input_grad", self.input_grad)) else (None, None)
+        if autograd and self.flipout and bool(exchange_args.get("channel_grad", self.channel_grad)):
+            raise NotImplementedError("channel_grad with message flips: the straight-through surrogate under a flip is not defined")
         if autograd and self.world > 1:
             raise NotImplementedError("autograd through exchange() runs on one GPU only (data-parallel training: Game.train_step)")
         corrupt_mask = None
