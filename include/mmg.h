@@ -301,6 +301,23 @@ int mmg_dp_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target,
 int mmg_clear_error(mmg_handle* h, void* stream);
 int mmg_degraded(const mmg_handle* h);
 
+/* What the kernel selection decided (host only, additive).  The selection is a pure function of the config, the MMG_* / CU-mask
+ * environment switches, two handle flags and the "caps": MMG_PLAN_CAPS int32 values the device reports -- the CU count (after
+ * cu_budget) and, per role kernel, the workgroups of it one CU holds (0: the query failed, -1: not asked for this shape):
+ * k_conv_split | k_conv_persist (the variant the shape uses) | k_rc_bwd | k_rc_persist | k_conversation_mc | _mc3 | _mc3p |
+ * k_game_fast | k_wgrad with the optimizer inside | k_wgrad.
+ *   mmg_plan_text: the selection of this handle as text: five lines of decisions (family and k_wgrad's plan; capabilities, LDS
+ *                  sizes and budgets; the sample tiles' forward; many-class / register-resident forward and baselines; backward),
+ *                  then one line with the caps it probed, in MMG_CAP_* order.
+ *   mmg_plan_for:  the same text for a config and caller-supplied caps (n_caps == MMG_PLAN_CAPS), under the environment of the
+ *                  call: no handle, no buffers, no GPU.  flags: bit 0 = no in-launch waits (what MMG_NO_ROLES=1 or a recovery
+ *                  selects), bit 1 = message flips are set.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
+ * Both return 0, or negative (out too small: about 2 KB are needed; a config the library refuses). */
+enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP_RC_PERSIST, MMG_CAP_MC, MMG_CAP_MC3, MMG_CAP_MC3P,
+       MMG_CAP_GAME, MMG_CAP_WGRAD_OPT, MMG_CAP_WGRAD, MMG_PLAN_CAPS };
+int mmg_plan_text(const mmg_handle* h, char* out, int out_bytes);
+int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_caps, int flags, char* out, int out_bytes);
+
 /* Agent-level entry points (one exchange step), mirroring the reference modules.  Forward only: their backward pass is
  * mmg_sender_vjp / mmg_receiver_vjp / mmg_baseline_vjp below, from the caller's copies of the call's inputs and outputs.
  *   sender:   x[B,F], w[B,W] (ignored when t==0), t -> message[B,W], probs[B,W] (NULL if continuous),

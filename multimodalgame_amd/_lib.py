@@ -49,7 +49,12 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_log_snapshot_count", "mmg_log_snapshot", "mmg_set_message_corruption", "mmg_exchange_vjp",
            "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps",
            "mmg_loss_save_doubles", "mmg_loss_binary_forward", "mmg_loss_binary_vjp", "mmg_loss_bas_forward", "mmg_loss_bas_vjp",
-           "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads", "mmg_set_message_flipout"]
+           "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads", "mmg_set_message_flipout",
+           "mmg_plan_text", "mmg_plan_for"]
+
+# the caps of mmg_plan_for / the last line of mmg_plan_text (include/mmg.h: MMG_CAP_*): the CU count, then one occupancy per role kernel
+PLAN_CAPS = ("n_cu", "split", "persist", "rc_bwd", "rc_persist", "mc", "mc3", "mc3p", "game", "wgrad_opt", "wgrad")
+PLAN_NO_ROLES, PLAN_FLIPS = 1, 2        # flags of mmg_plan_for
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
 EVAL_ACC_HEAD = 4
@@ -109,6 +114,8 @@ def load():
     lib.mmg_dp_train_steps.restype = i32; lib.mmg_dp_train_steps.argtypes = [vp, fp, vp, i64, fp, u64, i32, vp]
     lib.mmg_clear_error.restype = i32; lib.mmg_clear_error.argtypes = [vp, vp]
     lib.mmg_degraded.restype = i32; lib.mmg_degraded.argtypes = [vp]
+    lib.mmg_plan_text.restype = i32; lib.mmg_plan_text.argtypes = [vp, C.c_char_p, i32]
+    lib.mmg_plan_for.restype = i32; lib.mmg_plan_for.argtypes = [cfgp, C.POINTER(C.c_int32), i32, i32, C.c_char_p, i32]
     lib.mmg_log_snapshot_count.restype = i64; lib.mmg_log_snapshot_count.argtypes = [cfgp, i32, i32]
     lib.mmg_log_snapshot.restype = i32; lib.mmg_log_snapshot.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.mmg_sender_forward.restype = i32
@@ -172,3 +179,18 @@ def tape_table(cfg):
     check(0 if lib.mmg_tape_table(C.byref(cfg), arr, n) == n else -1)
     return [dict(name=e.name.decode(), dtype=e.dtype, dims=[int(e.dims[i]) for i in range(e.ndim)], offset=e.offset)
             for e in arr]
+
+
+def plan_for(cfg, caps, flags=0):
+    """The kernel selection of `cfg` on a device with these caps (PLAN_CAPS order), as mmg_plan_text prints it.  Host only."""
+    buf = C.create_string_buffer(4096)
+    arr = (C.c_int32 * len(caps))(*caps)
+    check(load().mmg_plan_for(C.byref(cfg), arr, len(caps), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+def plan_caps(text):
+    """The caps a plan text ends with, in PLAN_CAPS order."""
+    words = text.strip().splitlines()[-1].split()
+    assert words[:2] == ["mmg_create:", "caps"] and tuple(words[2::2]) == PLAN_CAPS, text
+    return [int(v) for v in words[3::2]]

@@ -1,5 +1,5 @@
-// host_launch.h -- host side of mmg.hip: the handle with its Selection and LaunchPlan, the timing scope of a launch and the launch helpers that more
-// than one entry point uses.  Included by mmg.hip only (after the kernels and fail() / HIP_OK).
+// host_launch.h -- host side of mmg.hip: the handle with its Selection (the device caps it was decided from included) and LaunchPlan, the timing
+// scope of a launch and the launch helpers that more than one entry point uses.  Included by mmg.hip only (after the kernels and fail() / HIP_OK).
 #pragma once
 
 struct KernelTimer { std::string name; hipEvent_t t0, t1; };
@@ -64,7 +64,9 @@ struct LaunchPlan {
 };
 
 // What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes, the co-residency budgets, the
-// family and the launch plan.  Constant until the next selection (mmg_create; error_gate after a timed-out dependency).
+// family and the launch plan.  Filled in three steps -- shape_pass (pure: everything up to the candidates that wait for a budget, and `ask`),
+// probe_device (`caps`), decide (pure: the rest) -- and printed by plan_text.  Constant until the next selection (mmg_create; error_gate after a
+// timed-out dependency; mmg_set_message_flipout when the routing changes).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
     bool sw_merge_bas = false;   // (= merge_roles) the baselines' forward pass rides in the backward / statistics launch; off: its own launch
@@ -105,6 +107,11 @@ struct Selection {
     // minus a margin): the role launches (k_conv_persist / k_conv_split / k_conversation_mc) spin on each other, so a launch
     // may never hold more roles than this
     int resident_budget = 0, split_budget = 0, n_cu = 0;
+    // the selection's device inputs (host_select.h): which occupancies the shape needs, what the device answered (indexed by MMG_CAP_*; 0: query
+    // failed, -1: not asked), and k_wgrad<true>'s workgroups per CU where the in-launch optimizer was a candidate (else 0)
+    bool ask[MMG_PLAN_CAPS] = {};
+    int32_t caps[MMG_PLAN_CAPS] = {};
+    int wgrad_resident = 0;
     Family family = FAM_GENERIC;
     LaunchPlan plan;
 };

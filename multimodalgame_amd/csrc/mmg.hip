@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -170,31 +171,33 @@ extern "C" int mmg_tape_table(const mmg_config* cfg, mmg_tape_entry* out, int ma
     return L.n;
 }
 
-extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int64_t workspace_bytes,
-                                  float* d_params, float* d_grads, float* d_opt_state) {
-    if (validate(cfg)) return nullptr;
-    if (!d_workspace || !d_params || !d_grads || !d_opt_state) { fail("NULL device buffer"); return nullptr; }
+// A handle with its layouts and the addresses inside the caller's buffers (no GPU call)
+static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, float* grads, float* opt_state) {
     mmg_handle* h = new mmg_handle();
-    h->cfg = *cfg;
+    h->cfg = cfg;
     if (h->cfg.global_batch <= 0) h->cfg.global_batch = h->cfg.batch;
     h->dm = make_dims(h->cfg);
     h->pl = param_layout(h->cfg);
     h->tl = tape_layout(h->cfg);
-    if (workspace_bytes < h->tl.total) { fail("workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)h->tl.total); delete h; return nullptr; }
-    h->ws = d_workspace; h->params = d_params; h->grads = d_grads; h->opt_state = d_opt_state;
-    h->P = resolve_params(h->pl, d_params);
-    h->G = resolve_params(h->pl, d_grads);
-    h->tp = resolve_tape(h->tl, d_workspace);
+    h->ws = ws; h->params = params; h->grads = grads; h->opt_state = opt_state;
+    h->P = resolve_params(h->pl, params);
+    h->G = resolve_params(h->pl, grads);
+    h->tp = resolve_tape(h->tl, ws);
     h->d_jt = reinterpret_cast<JobTable*>(h->tp.tables);
+    return h;
+}
+
+extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int64_t workspace_bytes,
+                                  float* d_params, float* d_grads, float* d_opt_state) {
+    if (validate(cfg)) return nullptr;
+    if (!d_workspace || !d_params || !d_grads || !d_opt_state) { fail("NULL device buffer"); return nullptr; }
+    mmg_handle* h = new_handle(*cfg, d_workspace, d_params, d_grads, d_opt_state);
+    if (workspace_bytes < h->tl.total) { fail("workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)h->tl.total); delete h; return nullptr; }
     if (hipHostMalloc((void**)&h->h_err, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) {
         *h->h_err = 0u;
         if (hipHostGetDevicePointer((void**)&h->d_err, h->h_err, 0) != hipSuccess) h->d_err = nullptr;
     } else h->h_err = nullptr;
-    h->no_roles = getenv("MMG_NO_ROLES") != nullptr;
-    // a process whose compute units are masked (HSA_CU_MASK / ROC_GLOBAL_CU_MASK) still sees the whole chip in
-    // hipGetDeviceProperties: the occupancy budgets below would promise co-residency the dispatcher cannot deliver
-    if (getenv("HSA_CU_MASK") || getenv("ROC_GLOBAL_CU_MASK")) h->no_roles = true;
-    if (select_paths(h)) { delete h; return nullptr; }
+    if (select_paths(h)) { delete h; return nullptr; }       // (also sets h->no_roles for MMG_NO_ROLES=1 / a CU mask in the environment)
     {
         // does this device place workgroup i of a launch on XCD i % 8 (8 distinct XCDs)?  The XCD-aware launches only PREFER that
         // placement; the many-class conversation may additionally keep its hand-off pairs inside the XCD's L2 when it holds.
@@ -229,6 +232,30 @@ extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int6
 }
 
 extern "C" void mmg_destroy(mmg_handle* h) { delete h; }      // (~mmg_handle releases the events and the pinned error word)
+
+extern "C" int mmg_plan_text(const mmg_handle* h, char* out, int out_bytes) {
+    if (!h) return fail("NULL handle");
+    return plan_text(h, out, out_bytes);
+}
+
+// The pure passes of select_paths on a handle that owns nothing: the job table is built from addresses only, so the buffers
+// are stand-in addresses that nothing dereferences.
+extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_caps, int flags, char* out, int out_bytes) {
+    if (validate(cfg)) return -1;
+    if (!caps || n_caps != MMG_PLAN_CAPS) return fail("mmg_plan_for: %d caps expected (MMG_CAP_*)", MMG_PLAN_CAPS);
+    if (caps[MMG_CAP_N_CU] <= 0) return fail("mmg_plan_for: caps[MMG_CAP_N_CU] must be positive");
+    float* const base = reinterpret_cast<float*>(uintptr_t(1) << 40);
+    const std::unique_ptr<mmg_handle> owner(new_handle(*cfg, base, base, base, base));
+    mmg_handle* h = owner.get();
+    h->d_err = reinterpret_cast<uint32_t*>(base);           // (as a created handle has one; h_err stays NULL: nothing to release)
+    h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0;
+    const Switches w = read_switches();
+    if (shape_pass(h, w)) return -1;
+    memcpy(h->sel.caps, caps, sizeof(h->sel.caps));
+    if (cfg->cu_budget > 0 && cfg->cu_budget < caps[MMG_CAP_N_CU]) h->sel.caps[MMG_CAP_N_CU] = cfg->cu_budget;
+    if (decide(h, w)) return -1;
+    return plan_text(h, out, out_bytes);
+}
 
 extern "C" int mmg_set_profiling(mmg_handle* h, int enabled) {
     if (!h) return fail("NULL handle");

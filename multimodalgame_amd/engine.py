@@ -263,6 +263,12 @@ class Engine(object):
         """Clear a recorded in-launch dependency error (drains the stream; the selected kernels stay)."""
         _lib.check(self.lib.mmg_clear_error(self.handle, self._stream()))
 
+    def plan_text(self):
+        """What the kernel selection of this handle decided, and the device caps it decided from (include/mmg.h: mmg_plan_text)."""
+        buf = C.create_string_buffer(4096)
+        _lib.check(self.lib.mmg_plan_text(self.handle, buf, len(buf)))
+        return buf.value.decode()
+
     def degraded(self):
         """0: role launches in use; 1: launches without in-launch waits since mmg_create; 2: ... since a recovery."""
         return int(self.lib.mmg_degraded(self.handle))

@@ -51,8 +51,8 @@ GEMM tiles without it; the bias columns run as K = 1 GEMMs when wgrad_nsplit > 1
   C4 / C4 at R = 256     tile / wide-receiver paths: code_bias from u0 (k_dhx), thousands of output tiles
   C1 D = 200, B = 40     many-class binary (k_conversation_mc, generic backward): dC / Py2 over 200 class rows, code_bias
                          from dc0
-Walked tiles (wgrad_stride > 0, occupancy-dependent; recorded once with an -DMMG_DEBUG_CREATE build, 256 CUs): config 3
-at B = 512 (856 workgroups walk 1 336 tiles) and C4 (672 walk 3 848); see WGRAD_STRIDE below."""
+Walked tiles (wgrad_stride > 0, occupancy-dependent; 256 CUs): config 3 at B = 512 (856 workgroups walk 1 336 tiles) and
+C4 (672 walk 3 848); see WGRAD_STRIDE below, checked against the engine's own plan text."""
 import numpy as np
 import pytest
 import torch
@@ -65,11 +65,16 @@ pytestmark = pytest.mark.gpu
 TAPE_NAMES = ("dgi", "dgh", "z", "h", "dA", "hstar", "dC", "descc", "Py2", "dysum", "dgpre", "dbar", "dlw", "g", "dls", "dhx",
               "dpre", "c", "dsig", "u0", "dc0", "dlz", "a", "dbr", "hid_r", "dbs", "hid_s", "hx", "zr", "tstar")
 
-# mmg_create's choice of walked GEMM tiles per shape on a 256-CU MI355X, recorded once with an -DMMG_DEBUG_CREATE build (not
-# shipped): "mmg_create: wgrad_stride <s> (gemm tiles <n>)" -- g2, C1 at B = 10 / 50 / 256 and D = 200: 0 (760 tiles);
-# config 3 at B = 512: 856 (1 336); C5 shard: 0 (504); C5 at B = 2 048: 0 (984); C4: 672 (3 848); C4 at R = 256: 0 (5 120,
-# more than 6 tiles per slot).  A shape not listed walks no tiles.
+# mmg_create's choice of walked GEMM tiles per shape on a 256-CU MI355X, the "wgrad_stride <s> (gemm tiles <n>)" of
+# Engine.plan_text() -- g2, C1 at B = 10 / 50 / 256 and D = 200: 0 (760 tiles); config 3 at B = 512: 856 (1 336); C5 shard:
+# 0 (504); C5 at B = 2 048: 0 (984); C4: 672 (3 848); C4 at R = 256: 0 (5 120, more than 6 tiles per slot).  A shape not
+# listed walks no tiles.  _case asserts the value against the engine it runs.
 WGRAD_STRIDE = {"c3-b512-fused": 856, "c3-b512-runall": 856, "c4-R64": 672}
+
+
+def _plan_field(eng, name):
+    words = eng.plan_text().split()
+    return int(words[words.index(name) + 1])
 
 REPORT = {}         # shape label -> worst |got - ref| / bound over its jobs (printed by the test)
 
@@ -213,6 +218,7 @@ def _variant(d, names):
 def _case(label, meta, modes, variant, expect_names=None, twin=False, name=None, over=None):
     """Runs the minibatches `modes` on one engine; every one through (a) (b) (c).  twin: (d) on the first minibatch."""
     eng = common.make_engine(meta, **(over or {}))
+    assert _plan_field(eng, "wgrad_stride") == WGRAD_STRIDE.get(label, 0), (label, eng.plan_text())
     d = wgrad_ref.dims_of(eng.cfg)
     table = eng.param_entries
     jobs = wgrad_ref.build_jobs(d, table, variant)
