@@ -196,6 +196,33 @@ int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, int n);
  * Returns 0, or negative for a probability outside [0, 1] or NaN (the setting before stays). */
 int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec, float p_rec, int flipout_dev, uint64_t eval_seed);
 
+/* The sender's communication ablations, -sender_mix prod / -ignore_code / -ignore_receiver (model.py:217-218, 208-210, 470-472).
+ * With h_x = image_layer(x) and h_w = code_layer(c_t), c_0 = sigmoid(code_bias), c_t = w_{t-1}:
+ *   mix = MMG_MIX_SUM   a_t = tanh(h_x + h_w)   (the default)
+ *   mix = MMG_MIX_PROD  a_t = tanh(h_x * h_w), at t = 0 too; backward: dpre = (W_b^T dlz)(1 - a_t^2), d h_x = dpre * h_w, d h_w = dpre * h_x
+ *   ignore_code         a_t = tanh(h_x) with either mix (prod + ignore_code == sum + ignore_code); code_layer.weight, code_layer.bias and
+ *                       code_bias get exact ZERO gradients.  (The reference leaves their .grad None and its optimizers skip them; here
+ *                       the update sees zeros: the parameters stay bit-identical, RMSprop's square average of the three tensors decays.)
+ *   ignore_receiver     binary messages only (use_binary == 0: accepted, nothing happens).  The receiver's message is replaced by zeros
+ *                       AFTER it was sampled (training) or rounded (evaluation); the uniform draw is still consumed, so no Philox stream
+ *                       and no injected uniform shifts.  Everything downstream reads the zeros: the sender's code input of t > 0 (h_w =
+ *                       code_layer.bias), baseline_sen's z_r, the tape arrays "w" / "zr", "lp_w" (= sum_j log(1 - pw_j + 1e-8)), the
+ *                       REINFORCE seed of the receiver's message stream (q = 0) and mmg_eval_steps' Hamming counts; "pw" and "ne_w" stay
+ *                       functions of the logits.
+ * All three at their defaults clears the setting.  While it is set it holds for every forward entry (mmg_exchange_forward,
+ * mmg_train_step[s], mmg_dp_train_step[s], mmg_eval_steps, mmg_sender_forward, mmg_receiver_forward), for the backward pass and for
+ * mmg_exchange_vjp / mmg_sender_vjp; mmg_exchange_vjp_channel refuses such a handle.  No tensor changes shape: parameter buffer,
+ * checkpoints and mmg_config stay as they are.
+ * Kernels: a variant handle runs the generic per-sample family -- k_conversation -> baselines and statistics launches -> k_bwd_conv ->
+ * k_wgrad -- in instantiations of their own (the backward one recomputes h_w of a step from the tape's code input); the register-resident,
+ * many-class, sample-tile and wide-receiver kernels do not form the variants.  The call re-runs the kernel selection and does no other
+ * GPU work; clearing restores the original selection.  A handle has message flips or a sender variant, not both (this bounds the
+ * kernel instantiations): whichever setter comes second returns negative.
+ * Returns 0, or negative: any other mix (-sender_mix mou needs a [W, 4H] binary layer and, with -ignore_code, one more parameter --
+ * another parameter layout), or flips are set; the setting before stays. */
+enum { MMG_MIX_SUM = 0, MMG_MIX_PROD = 1 };
+int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_receiver);
+
 /* Dev evaluation inside the library (eval_dev's loop body, model.py:620-691): n consecutive evaluation conversations, each
  * followed on the same stream by ONE reduction launch (k_eval_reduce) that leaves what the reference computes per dev batch
  * on the host -- as integers, so the results do not depend on any summation order and are bit-reproducible.
@@ -311,7 +338,7 @@ int mmg_degraded(const mmg_handle* h);
  *                  then one line with the caps it probed, in MMG_CAP_* order.
  *   mmg_plan_for:  the same text for a config and caller-supplied caps (n_caps == MMG_PLAN_CAPS), under the environment of the
  *                  call: no handle, no buffers, no GPU.  flags: bit 0 = no in-launch waits (what MMG_NO_ROLES=1 or a recovery
- *                  selects), bit 1 = message flips are set.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
+ *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
  * Both return 0, or negative (out too small: about 2 KB are needed; a config the library refuses). */
 enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP_RC_PERSIST, MMG_CAP_MC, MMG_CAP_MC3, MMG_CAP_MC3P,
        MMG_CAP_GAME, MMG_CAP_WGRAD_OPT, MMG_CAP_WGRAD, MMG_PLAN_CAPS };

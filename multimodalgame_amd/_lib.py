@@ -50,11 +50,12 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_sender_vjp", "mmg_receiver_vjp", "mmg_baseline_vjp", "mmg_eval_acc_count", "mmg_eval_steps",
            "mmg_loss_save_doubles", "mmg_loss_binary_forward", "mmg_loss_binary_vjp", "mmg_loss_bas_forward", "mmg_loss_bas_vjp",
            "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads", "mmg_set_message_flipout",
-           "mmg_plan_text", "mmg_plan_for"]
+           "mmg_plan_text", "mmg_plan_for", "mmg_set_sender_variant"]
 
 # the caps of mmg_plan_for / the last line of mmg_plan_text (include/mmg.h: MMG_CAP_*): the CU count, then one occupancy per role kernel
 PLAN_CAPS = ("n_cu", "split", "persist", "rc_bwd", "rc_persist", "mc", "mc3", "mc3p", "game", "wgrad_opt", "wgrad")
-PLAN_NO_ROLES, PLAN_FLIPS = 1, 2        # flags of mmg_plan_for
+PLAN_NO_ROLES, PLAN_FLIPS, PLAN_VARIANT = 1, 2, 4        # flags of mmg_plan_for
+MIX = {"sum": 0, "prod": 1}             # mmg_set_sender_variant's mix (include/mmg.h: MMG_MIX_SUM, MMG_MIX_PROD)
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
 EVAL_ACC_HEAD = 4
@@ -91,6 +92,7 @@ def load():
     lib.mmg_eval_steps.restype = i32; lib.mmg_eval_steps.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp]
     lib.mmg_set_message_corruption.restype = i32; lib.mmg_set_message_corruption.argtypes = [vp, vp, i32]
     lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
+    lib.mmg_set_sender_variant.restype = i32; lib.mmg_set_sender_variant.argtypes = [vp, i32, i32, i32]
     lib.mmg_exchange_vjp.restype = i32; lib.mmg_exchange_vjp.argtypes = [vp, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_exchange_vjp_channel.restype = i32; lib.mmg_exchange_vjp_channel.argtypes = [vp, i32, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_vjp_input_grads.restype = i32; lib.mmg_vjp_input_grads.argtypes = [vp, i32, i32, fp, fp, fp, vp]

@@ -66,7 +66,7 @@ struct LaunchPlan {
 // What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes, the co-residency budgets, the
 // family and the launch plan.  Filled in three steps -- shape_pass (pure: everything up to the candidates that wait for a budget, and `ask`),
 // probe_device (`caps`), decide (pure: the rest) -- and printed by plan_text.  Constant until the next selection (mmg_create; error_gate after a
-// timed-out dependency; mmg_set_message_flipout when the routing changes).
+// timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant when the routing changes).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
     bool sw_merge_bas = false;   // (= merge_roles) the baselines' forward pass rides in the backward / statistics launch; off: its own launch
@@ -77,6 +77,8 @@ struct Selection {
     int wgrad_stride = 0;        // > 0: k_wgrad's GEMM tiles are walked by this many resident workgroups (more tiles than slots); 0: one workgroup per tile
     bool wgrad_opt_ok = false;   // the clip + optimizer step can run inside k_wgrad's launch (k_wgrad<true>: every block co-resident, no row splits); MMG_NO_WGRAD_OPT=1: off
     bool flip = false;           // message flips are set on a binary handle (mmg_set_message_flipout): k_conversation_fast3<FLIP> / k_conversation<FLIP> serve it, nothing else
+    int variant = 0;             // the sender variant in effect (mmg_set_sender_variant; SV_* bits, SV_IGNORE_REC on a binary handle only): != 0: the generic
+                                 // per-sample family with k_conversation<NT, false, VAR> / k_bwd_conv<MANY, VAR> serves the handle, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
     bool merge_roles = false;    // MMG_NO_MERGE=1 keeps k_stats / k_dC / basehx as separate launches / in-kernel work
     // sample-tile MFMA path (kernels_tile.h): every shape the register-resident kernels do not cover
@@ -161,6 +163,9 @@ struct mmg_handle {
     float flip_p_sen = 0.f, flip_p_rec = 0.f;
     uint64_t flip_eval_seed = 0;
     uint32_t flip_evals = 0;
+    // mmg_set_sender_variant: SV_* bits as the caller set them (layout.h).  Host state; what is in effect on this handle is sel.variant, which the
+    // forward entries copy into ConvArgs::sender_var and the backward / sender-VJP launches pass as sv
+    int sender_var = 0;
     WgHead vjp_hd[8] = {};       // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
     ~mmg_handle() {
         for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }

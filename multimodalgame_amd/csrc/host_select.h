@@ -126,6 +126,10 @@ static void plan_launches(mmg_handle* h) {
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, true> : k_conversation<256, true>;
         p.agent_fn = k_conversation<256, true>;
     }
+    if (s.variant) {                             // a sender variant: the VAR instantiations (shape_pass has cleared every other conversation kernel)
+        p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, true> : k_conversation<256, false, true>;
+        p.agent_fn = k_conversation<256, false, true>;
+    }
     p.conv_name = wide ? "k_conversation_wv" : "k_conversation";
     p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
     // ---- baselines (training minibatch that did not run all rows) ----
@@ -187,12 +191,15 @@ static void plan_launches(mmg_handle* h) {
             p.bwd_fast_fn = merge_dc ? bwd_conv_fast_fn<false, true>(d.D, d.V) : bwd_conv_fast_fn<false, false>(d.D, d.V);
         }
         p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true> : k_bwd_conv<false>;
+        // (a sender variant: the reverse step of tanh(h_x) / tanh(h_x * h_w); ignore_receiver alone needs none -- the tape holds the zeros)
+        if (s.variant & SV_IGNORE_CODE) p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true, SV_IGNORE_CODE> : k_bwd_conv<false, SV_IGNORE_CODE>;
+        else if (s.variant & SV_PROD) p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true, SV_PROD> : k_bwd_conv<false, SV_PROD>;
         p.dc = merge_dc ? DC_NONE : DC_PLAIN;
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout changes the
+// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout / mmg_set_sender_variant change the
 // routing, and again when the library falls back to launches WITHOUT in-launch waits (h->no_roles: after a timed-out dependency, for a CU
 // budget / CU mask that cannot hold the role launches, or MMG_NO_ROLES=1).  Four steps, in this order:
 //   read_switches   the environment, once per selection -- never on the per-minibatch path, and nowhere else in the library
@@ -221,14 +228,19 @@ static Switches read_switches() {
     return w;
 }
 
-// Pure.  Everything Dims, the switches and the handle's flags (no_roles; flips: message flips are set; err_word: the pinned error word exists)
+// Pure.  Everything Dims, the switches and the handle's flags (no_roles; flips: message flips are set; variant: the SV_* bits of
+// mmg_set_sender_variant; err_word: the pinned error word exists)
 // settle alone.  A capability that also needs a co-residency budget (tile_split, tile_persist, mc_ok) leaves here as a CANDIDATE: its
 // preconditions hold and s.ask names the occupancy it waits for; decide() confirms or clears it.
-static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, bool err_word, Selection& s) {
+static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool err_word, Selection& s) {
     s = Selection();
     // message flips on binary messages (continuous ones are not flipped: the setting is kept and nothing happens)
     s.flip = flips && d.use_binary;
-    s.use_fast = !w[SW_NO_FAST]; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
+    // a sender variant (ignore_receiver on binary messages only, like the flips): the generic per-sample kernels form it -- the register-resident
+    // family with the one-launch step, the many-class kernels, the sample tiles and the wide receiver do not, so all of them are cleared here
+    s.variant = variant & (d.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
+    if (s.variant && s.flip) return fail("message flips and a sender variant on one handle");
+    s.use_fast = !w[SW_NO_FAST] && !s.variant; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
     s.sw_merge_prep = !w[SW_NO_MERGE_PREP] && !no_roles;
     s.sw_merge_bas = s.merge_roles;
     s.persist_ll = !w[SW_NO_PERSIST_LL] && persist_ll_shape(cfg.batch, cfg.h_dim, cfg.w_dim, cfg.rec_hidden, cfg.wv_dim, cfg.n_classes, cfg.max_exchange);
@@ -240,7 +252,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     s.conv_threads = (d.B <= 256 && ((int64_t)d.H * d.W >= 65536 || (int64_t)d.D * (d.R + d.V) >= 65536)) ? 512 : 256;
     s.conv_smem = conv_smem_floats(d, s.conv_threads) * 4;
     s.conv_smem_agent = conv_smem_floats(d, MMG_BLOCK) * 4;
-    s.bwd_smem = bwd_smem_floats(d) * 4;
+    s.bwd_smem = bwd_smem_floats(d, (s.variant & (SV_PROD | SV_IGNORE_CODE)) == SV_PROD) * 4;
     s.prep_smem = ((d.V > d.W ? d.V : d.W) + 16) * 4;
     // hundreds of classes: 8 per class block of k_prep (weight rows in registers across them); few classes: one per block (latency)
     s.prep_cpb = (d.D >= 256 && d.R <= 64 && d.V <= 128 && !(d.V & 3) && 2 * d.R <= MMG_BLOCK) ? 2 : 1;
@@ -267,7 +279,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
     //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
     // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
-    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip;
+    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant;
     s.tile_force = w[SW_TILE];
     // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
     // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -367,7 +379,10 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     occupancy(MMG_CAP_GAME, game_fast_fn(d.D), 256, game_lds_bytes());
     if (s.conv_smem > 48 * 1024) raise_lds(s.conv_smem, k_conversation<256>, k_conversation<512>);
     if (s.conv_smem > 48 * 1024 && s.flip) raise_lds(s.conv_smem, k_conversation<256, true>, k_conversation<512, true>);
+    if (s.conv_smem > 48 * 1024 && s.variant) raise_lds(s.conv_smem, k_conversation<256, false, true>, k_conversation<512, false, true>);
     if (s.bwd_smem > 48 * 1024) raise_lds(s.bwd_smem, k_bwd_conv<false>, k_bwd_conv<true>);
+    if (s.bwd_smem > 48 * 1024 && (s.variant & SV_IGNORE_CODE)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_IGNORE_CODE>, k_bwd_conv<true, SV_IGNORE_CODE>);
+    else if (s.bwd_smem > 48 * 1024 && (s.variant & SV_PROD)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_PROD>, k_bwd_conv<true, SV_PROD>);
     if (e != hipSuccess) return fail("device init failed: %s", hipGetErrorString(e));
     occupancy(MMG_CAP_WGRAD_OPT, k_wgrad<true>, MMG_BLOCK, 0);
     occupancy(MMG_CAP_WGRAD, k_wgrad<false>, MMG_BLOCK, 0);
@@ -458,7 +473,7 @@ static int decide(mmg_handle* h, const Switches& w) {
 
 static int shape_pass(mmg_handle* h, const Switches& w) {
     h->no_roles = h->no_roles || w.roles_off();
-    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->d_err != nullptr, h->sel);
+    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel);
 }
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();

@@ -345,14 +345,24 @@ __device__ __forceinline__ float bit_seed(float q, float p, float wh, float ce) 
     return dLdp * p * (1.f - p);
 }
 
-__host__ __device__ inline int bwd_smem_floats(const Dims& d) {
+// prod: k_bwd_conv<MANY, SV_PROD>'s extra row (the recomputed h_w of a step) behind everything else
+__host__ __device__ inline int bwd_smem_floats(const Dims& d, bool prod = false) {
     auto p4 = [](int n) { return (n + 3) & ~3; };
-    return 7 * d.T + 3 * p4(d.H) + 3 * p4(d.W) + 6 * p4(d.R) + 2 * p4(3 * d.R) + p4(d.D) + 4 * MMG_BLOCK + 32;
+    return 7 * d.T + 3 * p4(d.H) + 3 * p4(d.W) + 6 * p4(d.R) + 2 * p4(3 * d.R) + p4(d.D) + 4 * MMG_BLOCK + 32 + (prod ? p4(d.H) : 0);
 }
 
 // MANY: thousands of samples -- occupancy matters more than load depth (<= 128 VGPRs, 4 workgroups per CU).
-template <bool MANY>
-__global__ __launch_bounds__(MMG_BLOCK, MANY ? 4 : 1) void k_bwd_conv(Dims dm, Params P, Tape tp, const int64_t* __restrict__ target) {
+// VAR: the instantiations a handle with a sender variant runs (mmg_set_sender_variant): SV_PROD or SV_IGNORE_CODE (layout.h; both set = the
+// latter), 0 for every other handle -- compile-time, so that the kernels of every other handle stay what they were, symbol and arguments
+// included.  With a = tanh(h_x * h_w) the step's two factors get different gradients:
+//   dpre = (W_b^T dlz)(1 - a^2),  d h_x = dpre * h_w,  d h_w = dpre * h_x
+// and the tapes keep their meanings for k_wgrad's jobs: tp.dpre = d h_w (code_layer), tp.dhx = sum_t d h_x (image_layer), tp.dc0 =
+// W_c^T d h_w at t = 0 (code_bias).  h_w of the step is RECOMPUTED (W_c c_t + b_c from tp.c, tp.hw0 at t = 0): a [T, B, H] tape array would
+// be paid for by every handle.  SV_IGNORE_CODE: d h_w = 0 exactly, d h_x = dpre.  SV_IGNORE_REC needs nothing here -- tp.w holds the zeros --:
+// a handle with that bit alone runs k_bwd_conv<MANY>.
+// (MANY && VAR: 3 workgroups per CU, 168 VGPRs -- at 4 the recomputation spills, and k_bwd_conv<true> itself carries 48 bytes of scratch.)
+template <bool MANY, int VAR = 0>
+__global__ __launch_bounds__(MMG_BLOCK, MANY ? (VAR ? 3 : 4) : 1) void k_bwd_conv(Dims dm, Params P, Tape tp, const int64_t* __restrict__ target) {
     constexpr int TU = MANY ? 2 : 8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -369,6 +379,8 @@ __global__ __launch_bounds__(MMG_BLOCK, MANY ? 4 : 1) void k_bwd_conv(Dims dm, P
     float* s_dy = p; p += p4(D);
     float* s_red = p; p += 4 * MMG_BLOCK;
     float* s_misc = p;
+    float* s_hw = s_misc + 32;                                    // SV_PROD only (bwd_smem_floats(d, true)): h_w of the step, recomputed
+    constexpr bool prod = VAR == SV_PROD, no_code = (VAR & SV_IGNORE_CODE) != 0;
 
     loss_coefficients(dm, tp.stats, lc, nullptr, nullptr);        // logged losses: spare block of k_wgrad
 
@@ -486,13 +498,24 @@ __global__ __launch_bounds__(MMG_BLOCK, MANY ? 4 : 1) void k_bwd_conv(Dims dm, P
             for (int j = tid; j < W; j += nt) {
                 const float v = bit_seed(tp.z[row * W + j], tp.pz[row * W + j], wh, ce_z[t]);
                 s_dlz[j] = v; tp.dlz[row * W + j] = v;
+                if (VAR && prod && t > 0) s_dc0[j] = tp.c[row * W + j];        // the step's code input (s_dc0 is free until t = 0)
             }
             __syncthreads();
+            // VAR: h_w = W_c c_t + b_c again (t = 0: tp.hw0), beside the product below -- no barrier of its own: gemv_t ends with one
+            if (VAR && prod && t > 0) gemv_rows<(MANY ? 2 : 4)>(P.p[S_CODE_W], W, H, W, s_dc0, [&](int n, float acc) { s_hw[n] = acc; });
             gemv_t<TU>(P.p[S_BIN_W], H, W, H, s_dlz, s_da, s_red, false);          // da = W_b^T dlz
             for (int i = tid; i < H; i += nt) {
                 const float a = tp.a[row * H + i];
                 const float v = s_da[i] * (1.f - a * a);
-                s_dpre[i] = v; tp.dpre[row * H + i] = v; s_dhx[i] += v;
+                if (VAR && prod) {                                             // a = tanh(h_x * h_w), model.py:217-218
+                    const float hw = (t == 0) ? tp.hw0[i] : s_hw[i] + P.p[S_CODE_B][i];
+                    const float dhw = v * tp.hx[(size_t)b * H + i];
+                    s_dpre[i] = dhw; tp.dpre[row * H + i] = dhw; s_dhx[i] += v * hw;
+                } else if (VAR && no_code) {                                   // a = tanh(h_x), model.py:208-210: nothing reaches code_layer / code_bias
+                    s_dpre[i] = 0.f; tp.dpre[row * H + i] = 0.f; s_dhx[i] += v;
+                } else {
+                    s_dpre[i] = v; tp.dpre[row * H + i] = v; s_dhx[i] += v;
+                }
             }
             __syncthreads();
             if (t == 0) {                                                      // code_bias path (model.py:199)

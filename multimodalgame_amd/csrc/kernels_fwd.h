@@ -359,6 +359,7 @@ struct ConvArgs {
     int run_all;               // 1: every sample runs all steps
     int t_begin, t_end;        // step window (whole conversation: 0, T)
     int phases;                // bit 0 sender, bit 1 receiver
+    int sender_var;            // mmg_set_sender_variant: SV_* bits, read by the VAR instantiations only (0: the plain sender); sits in what was padding
     // agent-level I/O (NULL in the fused path: state lives in the tape)
     const float* w_in;         // sender input code for t_begin > 0   [B,W]
     float* h_state;            // receiver GRU state in/out           [B,R]
@@ -429,8 +430,9 @@ __global__ __launch_bounds__(64) void k_xcc_probe(uint32_t* __restrict__ out) {
 }
 
 // FLIP: the instantiations a handle with message flips runs (flip_msg at both message sites); a compile-time switch, so that
-// the kernels of every other handle stay what they were
-template <int NT, bool FLIP = false>
+// the kernels of every other handle stay what they were.  VAR: likewise for a handle with a sender variant (ar.sender_var: SV_* bits); a
+// handle has flips or a variant, never both, so FLIP && VAR is not instantiated
+template <int NT, bool FLIP = false, bool VAR = false>
 __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp, ConvArgs ar) {
     constexpr int GU = NT == 512 ? 8 : 4;               // row passes per load batch of gemv_rows
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -492,7 +494,8 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                 tp.c[row * W + j] = (t == 0) ? sigmoidf_(P.p[S_CODE_BIAS][j]) : cv;
             }
             __syncthreads();
-            if (t > 0) {
+            const bool no_code = VAR && (ar.sender_var & SV_IGNORE_CODE);     // model.py:208-210: h_w is not used (the reference computes and drops it)
+            if (t > 0 && !no_code) {
                 // (epilogues only park the sums in LDS: a bias / uniform load inside them would be one dependent
                 //  global round trip per row pass, executed by a single lane of each group)
                 gemv_rows<GU>(P.p[S_CODE_W], W, H, W, s.c, [&](int n, float acc) { s.a[n] = acc; });
@@ -500,8 +503,14 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
             }
             const float* bc = P.p[S_CODE_B];
             for (int i = tid; i < H; i += nt) {
-                const float hw = (t == 0) ? tp.hw0[i] : s.a[i] + bc[i];
-                const float av = tanhf(s.hx[i] + hw);              // model.py:216
+                float av;
+                if (VAR && no_code) {
+                    av = tanhf(s.hx[i]);                           // model.py:208-210
+                } else {
+                    const float hw = (t == 0) ? tp.hw0[i] : s.a[i] + bc[i];
+                    av = (VAR && (ar.sender_var & SV_PROD)) ? tanhf(s.hx[i] * hw)      // model.py:217-218
+                                                            : tanhf(s.hx[i] + hw);     // model.py:216
+                }
                 s.a[i] = av;
                 tp.a[row * H + i] = av;
             }
@@ -697,6 +706,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                         wv = rintf(p);                             // model.py:462
                     }
                     if (FLIP) wv = flip_msg(ar, true, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, wv);       // model.py:467-468
+                    if (VAR && (ar.sender_var & SV_IGNORE_REC)) wv = 0.f;                                          // model.py:470-472 (the draw above is still consumed)
                     tp.pw[row * W + n] = p;
                     const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
                     lpv = wv * l1 + (1.f - wv) * l0;

@@ -37,6 +37,7 @@ struct VjpIn {
     const float* dbs;    // [n, B]      d loss / d bs_t
     const float* dbr;    // [n, B]      d loss / d br_t
     int n;               // executed steps: upstream gradients exist for t < n only
+    int sv;              // k_vjp_sen: the handle's sender variant (SV_* bits, layout.h; 0: the plain sender); sits in what was padding
 };
 
 __device__ __forceinline__ float vjp_block_reduce(float v, float* s_red, bool is_max) {
@@ -297,8 +298,13 @@ __host__ __device__ inline int vjp_sen_smem_floats(const Dims& d) { return 4 * d
 // The sender's step backward (model.py:195-238), shared by the exchange and the per-call VJP.  s_hx (LDS) holds h_x of the sample;
 // c: the code input w_{t-1} (NULL: sigmoid(code_bias), t = 0), pz: the message probabilities (binary), dz: d probs | d logits
 // (NULL = zero).  Adds d pre of the step to s_dhx and leaves it in s_dpre.
+// VAR (a handle with a sender variant; sv: SV_* bits, wave-uniform): with a = tanh(h_x * h_w) (SV_PROD, model.py:217-218) the step adds
+// d h_x = dpre * h_w to s_dhx and leaves d h_w = dpre * h_x in s_dpre / vdpre -- the operand of code_layer's jobs and of W_c^T .
+// (code_bias, d w) --; with a = tanh(h_x) (SV_IGNORE_CODE, model.py:208-210) d h_x = dpre and d h_w = 0 exactly.  A compile-time
+// switch: the callers without a variant (k_vjp_channel among them) keep the code they had.
+template <bool VAR = false>
 __device__ __forceinline__ void vjp_sen_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const float* c,
-                                             const float* pz, const float* dz, size_t row) {
+                                             const float* pz, const float* dz, size_t row, int sv = 0) {
     const int H = dm.H, W = dm.W, tid = threadIdx.x;
     float* s_hx = smem;  float* s_a = s_hx + H;  float* s_dpre = s_a + H;  float* s_dhx = s_dpre + H;
     float* s_c = s_dhx + H;  float* s_dlz = s_c + W;
@@ -320,16 +326,26 @@ __device__ __forceinline__ void vjp_sen_step(const Dims& dm, const Params& P, co
     __syncthreads();
     for (int h = tid; h < H; h += MMG_BLOCK) {
         float pre = s_hx[h] + bc[h];
-        for (int j = 0; j < W; ++j) pre = fmaf(Wc[(size_t)h * W + j], s_c[j], pre);
+        float fx = 1.f, fw = 1.f;                             // VAR: d h_x = dpre * fx, d h_w = dpre * fw
+        if (VAR && (sv & SV_IGNORE_CODE)) {
+            pre = s_hx[h]; fw = 0.f;
+        } else if (VAR && (sv & SV_PROD)) {
+            float hw = bc[h];
+            for (int j = 0; j < W; ++j) hw = fmaf(Wc[(size_t)h * W + j], s_c[j], hw);
+            pre = s_hx[h] * hw; fx = hw; fw = s_hx[h];
+        } else {
+            for (int j = 0; j < W; ++j) pre = fmaf(Wc[(size_t)h * W + j], s_c[j], pre);
+        }
         const float a = tanhf(pre);
         s_a[h] = a;
         tp.va[row * H + h] = a;
         float da = 0.f;
         for (int j = 0; j < W; ++j) da = fmaf(Wb[(size_t)j * H + h], s_dlz[j], da);
         const float dp = da * (1.f - a * a);
-        s_dpre[h] = dp;
-        tp.vdpre[row * H + h] = dp;
-        s_dhx[h] += dp;
+        const float dw = VAR ? dp * fw : dp;
+        s_dpre[h] = dw;
+        tp.vdpre[row * H + h] = dw;
+        s_dhx[h] += VAR ? dp * fx : dp;
     }
 }
 
@@ -346,8 +362,10 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen(Dims dm, Params P, Tape t
     for (int t = 0; t < T; ++t) {
         const size_t row = (size_t)t * B + b;
         const bool live = t < in.n;
-        vjp_sen_step(dm, P, tp, smem, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W,
-                     (live && in.dz) ? in.dz + row * W : nullptr, row);    // (the receiver's previous message)
+        const float* c = t == 0 ? nullptr : tp.w + (row - B) * W;                 // (the receiver's previous message)
+        const float* dz = (live && in.dz) ? in.dz + row * W : nullptr;
+        if (in.sv) vjp_sen_step<true>(dm, P, tp, smem, c, tp.pz + row * W, dz, row, in.sv);
+        else vjp_sen_step(dm, P, tp, smem, c, tp.pz + row * W, dz, row);
         if (t == 0) {
             __syncthreads();
             for (int j = tid; j < W; j += MMG_BLOCK) {
@@ -430,6 +448,7 @@ struct SenCall {
     float *dx, *dw;
     int t;
     int q_tiles, dx_tiles;     // W_c^T dpre / d x are formed by k_vjp_nn (MFMA) after this kernel, from vdpre / vdhx
+    int sv;                    // the handle's sender variant (SV_* bits, layout.h; 0: the plain sender); sits in what was padding
 };
 
 // Sender, one call: one workgroup per sample.  vjp_sen_step on row b, then W_c^T dpre -> the code_bias path (t = 0) or d w (t > 0),
@@ -443,8 +462,10 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_sen_call(Dims dm, Params P, T
     if (b == 0)
         for (int j = tid; j < W; j += MMG_BLOCK) { const float s = sigmoidf_(cb[j]); tp.vdsig[j] = s * (1.f - s); }
     for (int h = tid; h < H; h += MMG_BLOCK) { s_hx[h] = c.h_x[(size_t)b * H + h]; s_dhx[h] = 0.f; }
-    vjp_sen_step(dm, P, tp, smem, c.t == 0 ? nullptr : c.w + (size_t)b * W, c.probs ? c.probs + (size_t)b * W : nullptr,
-                 c.dout ? c.dout + (size_t)b * W : nullptr, b);
+    if (c.sv) vjp_sen_step<true>(dm, P, tp, smem, c.t == 0 ? nullptr : c.w + (size_t)b * W, c.probs ? c.probs + (size_t)b * W : nullptr,
+                                 c.dout ? c.dout + (size_t)b * W : nullptr, b, c.sv);
+    else vjp_sen_step(dm, P, tp, smem, c.t == 0 ? nullptr : c.w + (size_t)b * W, c.probs ? c.probs + (size_t)b * W : nullptr,
+                      c.dout ? c.dout + (size_t)b * W : nullptr, b);
     __syncthreads();
     for (int j = tid; j < W; j += MMG_BLOCK) {
         if (c.q_tiles) {                                      // (k_vjp_nn writes vdc0 at t = 0 and d w after)

@@ -389,4 +389,12 @@ inline Dims make_dims(const mmg_config& c) {
     return d;
 }
 
+// mmg_set_sender_variant, the reference's communication ablations.  Bits of ConvArgs::sender_var and of the sv argument of k_bwd_conv and
+// the sender VJPs; only the VAR instantiations of those kernels read them.
+//   SV_PROD         a_t = tanh(h_x * h_w) instead of tanh(h_x + h_w), at t = 0 too   (model.py:217-218)
+//   SV_IGNORE_CODE  a_t = tanh(h_x): h_w is not used, with either mix               (model.py:208-210)
+//   SV_IGNORE_REC   the receiver's binary message is replaced by zeros AFTER the sample / the rounding (model.py:470-472): the tape, the
+//                   sender's next code input, baseline_sen's z_r, lp_w and the REINFORCE seed read the zeros; pw and ne_w stay
+enum { SV_PROD = 1, SV_IGNORE_CODE = 2, SV_IGNORE_REC = 4 };
+
 }  // namespace mmg

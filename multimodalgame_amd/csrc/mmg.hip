@@ -248,7 +248,7 @@ extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_ca
     const std::unique_ptr<mmg_handle> owner(new_handle(*cfg, base, base, base, base));
     mmg_handle* h = owner.get();
     h->d_err = reinterpret_cast<uint32_t*>(base);           // (as a created handle has one; h_err stays NULL: nothing to release)
-    h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0;
+    h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0; h->sender_var = (flags & 4) ? SV_PROD : 0;
     const Switches w = read_switches();
     if (shape_pass(h, w)) return -1;
     memcpy(h->sel.caps, caps, sizeof(h->sel.caps));
@@ -458,6 +458,7 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
     ar.lean = (mode == TAPE_MINIMAL && !d.use_binary) ? 1 : 0;
     if (h->corrupt_on) { ar.corrupt_on = 1; memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt)); }
     flip_args(h, ar, seed, train, true);
+    ar.sender_var = s.variant;
     h->fwd = ForwardState();
     const bool base_ready = p.fwd_basehx && bas && !all_rows;
     switch (s.family) {
@@ -540,6 +541,8 @@ extern "C" int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, 
         h->flip_sen = sen; h->flip_p_sen = sen ? ps : 0.f; h->flip_rec = rec; h->flip_p_rec = rec ? pr : 0.f;
         h->flip_dev = dev && (sen || rec); h->flip_eval_seed = sd; h->flip_evals = ev;
     };
+    if ((has_sen || has_rec) && h->sender_var)
+        return fail("mmg_set_message_flipout: the handle has a sender variant (mmg_set_sender_variant); flips and a variant do not combine");
     set(has_sen != 0, p_sen, has_rec != 0, p_rec, flipout_dev != 0, eval_seed, 0u);
     if (((h->flip_sen || h->flip_rec) && h->dm.use_binary) == h->sel.flip) return 0;        // same routing: nothing to select
     const JobTable old = h->jt;
@@ -548,6 +551,33 @@ extern "C" int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, 
         set(o_sen, o_ps, o_rec, o_pr, o_dev, o_seed, o_evals);
         select_paths(h);
         return fail("mmg_set_message_flipout: %s", why.c_str());
+    }
+    if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
+        HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
+        HIP_OK(hipMemcpy(h->d_jt, &h->jt, sizeof(JobTable), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// The sender's communication ablations (include/mmg.h): host state; re-runs the selection, since a variant handle is served by the generic
+// per-sample family only (host_select.h).  The job table goes to the device again only where the family changed it.
+extern "C" int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_receiver) {
+    if (!h) return fail("NULL handle");
+    if (mix != MMG_MIX_SUM && mix != MMG_MIX_PROD)
+        return fail("mmg_set_sender_variant: mix = %d is not MMG_MIX_SUM or MMG_MIX_PROD (-sender_mix mou needs a 4H binary layer, another parameter layout)", mix);
+    const int want = (mix == MMG_MIX_PROD ? SV_PROD : 0) | (ignore_code ? SV_IGNORE_CODE : 0) | (ignore_receiver ? SV_IGNORE_REC : 0);
+    if (want && (h->flip_sen || h->flip_rec))
+        return fail("mmg_set_sender_variant: the handle has message flips (mmg_set_message_flipout); flips and a variant do not combine");
+    const int old_var = h->sender_var;
+    h->sender_var = want;
+    const int eff = want & (h->dm.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
+    if (eff == h->sel.variant) return 0;                 // same routing and the same kernels: nothing to select
+    const JobTable old = h->jt;
+    if (select_paths(h)) {
+        const std::string why = g_err;
+        h->sender_var = old_var;
+        select_paths(h);
+        return fail("mmg_set_sender_variant: %s", why.c_str());
     }
     if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
         HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
@@ -863,6 +893,7 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
     ar.x = d_x; ar.u_z = d_u_z ? d_u_z - (size_t)t * d.B * d.W : nullptr; ar.seed = seed; ar.train = train; ar.run_all = 1;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 1; ar.w_in = d_w;
     flip_args(h, ar, seed, train, false);
+    ar.sender_var = h->sel.variant;
     if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
     hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(sender)")) return -1;
@@ -892,6 +923,7 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
     ar.u_s = d_u_s ? d_u_s - offB : nullptr; ar.u_w = d_u_w ? d_u_w - offW : nullptr;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 2; ar.h_state = d_h_z; ar.sprod_state = d_s_prob_prod; ar.sprod_first = first;
     flip_args(h, ar, seed, train, false);
+    ar.sender_var = h->sel.variant;
     hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(receiver)")) return -1;
     if (d_s) HIP_OK(hipMemcpyAsync(d_s, h->tp.s + offB, sizeof(float) * d.B, hipMemcpyDeviceToDevice, st));
@@ -942,7 +974,7 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
     if (agent >= MMG_AGENT_BASELINE_REC && !d.use_binary) return fail("baseline scores exist in binary training only (model.py:834-843)");
     hipStream_t st = (hipStream_t)stream;
     VjpIn in;
-    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = d_dbs; in.dbr = d_dbr; in.n = n_steps;
+    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = d_dbs; in.dbr = d_dbr; in.n = n_steps; in.sv = h->sel.variant;
     if (agent == MMG_AGENT_RECEIVER) {
         if (!d_desc) return fail("desc must not be NULL");
         const size_t smem = sizeof(float) * (size_t)vjp_rec_smem_floats(d);
@@ -978,9 +1010,10 @@ extern "C" int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float*
     const Dims& d = h->dm;
     if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
     if (!d_x || !d_desc) return fail("x / desc must not be NULL");
+    if (h->sel.variant) return fail("mmg_exchange_vjp_channel: not available on a handle with a sender variant (mmg_set_sender_variant)");
     hipStream_t st = (hipStream_t)stream;
     VjpIn in;
-    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = nullptr; in.dbr = nullptr; in.n = n_steps;
+    in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = nullptr; in.dbr = nullptr; in.n = n_steps; in.sv = 0;
     const size_t smem = sizeof(float) * (size_t)vjp_channel_smem_floats(d);
     if (vjp_lds_ok(smem, "channel", " (too many classes or h_dim too large)") || launch_vjp_cd(h, st, d_desc)) return -1;
     {
@@ -1074,7 +1107,7 @@ extern "C" int mmg_sender_vjp(mmg_handle* h, const float* d_x, const float* d_w,
     hipStream_t st = (hipStream_t)stream;
     SenCall c;
     c.w = d_w; c.h_x = d_h_x; c.probs = d.use_binary ? d_probs : nullptr; c.dout = d_dout; c.dh_x = d_dh_x;
-    c.dx = d_dx; c.dw = d_dw; c.t = t;
+    c.dx = d_dx; c.dw = d_dw; c.t = t; c.sv = h->sel.variant;
     // W_c^T dpre (-> vdc0 at t = 0, d w after) and d x = W_img^T d h_x on the MFMA tiles where the shape allows
     NnProd pr[2];
     int np = 0;

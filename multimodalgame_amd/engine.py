@@ -166,6 +166,22 @@ class Engine(object):
             float(p_rec if p_rec is not None else 0.0), int(bool(dev)), C.c_uint64(int(eval_seed) & 0xFFFFFFFFFFFFFFFF)))
         self.flipout = None if p_sen is None and p_rec is None else (p_sen, p_rec, bool(dev))
 
+    def set_sender_variant(self, mix="sum", ignore_code=False, ignore_receiver=False):
+        """The sender's communication ablations, the reference's -sender_mix prod / -ignore_code / -ignore_receiver
+        (model.py:217-218, 208-210, 470-472; include/mmg.h: mmg_set_sender_variant).  mix: "sum" -- tanh(h_x + h_w) -- or "prod" --
+        tanh(h_x * h_w); ignore_code: tanh(h_x), and code_layer / code_bias get exact zero gradients; ignore_receiver (binary
+        messages only): the receiver's message is replaced by zeros after it was sampled or rounded.  All defaults clears the
+        setting.  Holds for every later forward entry of this engine, its backward pass and the sender's VJPs.  Host only: the
+        library re-selects its kernels (a variant runs the generic per-sample family), no GPU work.  Not together with message
+        flips."""
+        if mix == "mou":
+            raise NotImplementedError("sender_mix = 'mou' needs a 4H binary layer: another parameter layout")
+        if mix not in ("sum", "prod"):
+            raise ValueError("mix = %r: 'sum' or 'prod' expected" % (mix,))
+        _lib.check(self.lib.mmg_set_sender_variant(self.handle, _lib.MIX[mix], int(bool(ignore_code)), int(bool(ignore_receiver))))
+        variant = (mix, bool(ignore_code), bool(ignore_receiver))
+        self.sender_variant = None if variant == ("sum", False, False) else variant
+
     def loss_stats(self):
         _lib.check(self.lib.mmg_loss_stats(self.handle, self._stream()))
 

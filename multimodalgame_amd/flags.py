@@ -252,11 +252,11 @@ def default_flags(argv=None):
 UNSUPPORTED = (
     # (flag, predicate on its value and the flags object, reference lines that read it)
     ("desc_attn", lambda v, fl: bool(v), "model.py:344-409 (description attention)"),
-    ("sender_mix", lambda v, fl: v not in (None, "sum"), "model.py:201-214 (prod / mou mixing of h_x and h_w)"),
+    ("sender_mix", lambda v, fl: v not in (None, "sum"), "model.py:201-221 (prod / mou mixing of h_x and h_w; the library option for prod: Game(..., sender_mix=\"prod\"); mou needs a 4H binary layer)"),
     ("flipout_sen", lambda v, fl: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message; the library option: Game(..., flipout_sen=P))"),
     ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message; the library option: Game(..., flipout_rec=P))"),
-    ("ignore_receiver", lambda v, fl: bool(v), "model.py:217-218 (sender ignores the receiver's message)"),
-    ("ignore_code", lambda v, fl: bool(v), "model.py:219-221 (sender ignores its code input)"),
+    ("ignore_receiver", lambda v, fl: bool(v), "model.py:470-472 (the receiver's message is replaced by zeros; the library option: Game(..., ignore_receiver=True))"),
+    ("ignore_code", lambda v, fl: bool(v), "model.py:208-210 (sender ignores its code input; the library option: Game(..., ignore_code=True))"),
     ("visual_attn", lambda v, fl: bool(v), "model.py:114-191 (visual attention over layer4_2)"),
     # -bit_flip WITH a region corrupts every dev evaluation's messages (model.py:637-638, 813-820); without one the reference
     # crashes at its first dev evaluation (build_mask(None, ...), misc.py:390)

@@ -234,10 +234,16 @@ class Game(object):
     flipout_sen / flipout_rec (a probability, None: off) and flipout_dev: the reference's noisy channel (model.py:233-234, 467-468,
     554-568) -- every bit of the sender's / the receiver's message is inverted with that probability right after it is sampled,
     in training conversations always, in evaluation ones under flipout_dev; everything downstream reads the flipped bits
-    (Engine.set_message_flipout).  These keyword arguments are separate from `flags`, whose -flipout_* switches stay refused."""
+    (Engine.set_message_flipout).  These keyword arguments are separate from `flags`, whose -flipout_* switches stay refused.
+    sender_mix ("sum" | "prod"), ignore_code, ignore_receiver: the reference's communication ablations (model.py:217-218, 208-210,
+    470-472) -- the sender's hidden layer is tanh(h_x * h_w) / tanh(h_x) instead of tanh(h_x + h_w), and the receiver's binary
+    message is replaced by zeros after it was sampled or rounded (Engine.set_sender_variant).  They hold for every entry of every
+    engine the game creates, on every rank; plain autograd works with them, channel_grad, input_grad and message flips do not.
+    Separate from `flags` as well: -sender_mix, -ignore_code and -ignore_receiver stay refused there."""
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
-                 channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False):
+                 channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False,
+                 sender_mix="sum", ignore_code=False, ignore_receiver=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -262,6 +268,17 @@ class Game(object):
         self.flipout = None if flipout_sen is None and flipout_rec is None else (flipout_sen, flipout_rec, bool(flipout_dev))
         if self.flipout and self.channel_grad:
             raise NotImplementedError("channel_grad with message flips: the straight-through surrogate under a flip is not defined")
+        if sender_mix == "mou":
+            raise NotImplementedError("sender_mix = 'mou' needs a 4H binary layer (binary_layer [W, 4H], and code_bias_mou under "
+                                      "ignore_code): another parameter layout; 'sum' and 'prod' are available")
+        if sender_mix not in ("sum", "prod"):
+            raise ValueError("sender_mix = %r: 'sum' or 'prod' expected" % (sender_mix,))
+        variant = (sender_mix, bool(ignore_code), bool(ignore_receiver))
+        self.sender_variant = None if variant == ("sum", False, False) else variant
+        if self.sender_variant and self.flipout:
+            raise NotImplementedError("a sender variant (sender_mix / ignore_code / ignore_receiver) with message flips: a handle "
+                                      "has one or the other")
+        self._refuse_variant_graph(self.channel_grad, self.input_grad)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -282,6 +299,12 @@ class Game(object):
 
     def next_seed(self):
         return self.seed
+
+    def _refuse_variant_graph(self, channel_grad, input_grad):
+        """The joint sender-receiver node and the input gradients do not form the sender variants."""
+        if self.sender_variant and (channel_grad or input_grad):
+            raise NotImplementedError("%s with a sender variant (sender_mix / ignore_code / ignore_receiver) is not available: "
+                                      "plain autograd is" % ("channel_grad" if channel_grad else "input_grad"))
 
     def set_parallel(self, rank, world, group=None):
         """Data-parallel training (dist.DataParallel): train_step() then takes THIS rank's rows of the global minibatch --
@@ -308,6 +331,8 @@ class Game(object):
                          global_batch=global_batch, batch_offset=batch_offset, **self.cfg)
             if self.flipout:
                 eng.set_message_flipout(self.flipout[0], self.flipout[1], dev=self.flipout[2], eval_seed=self.seed)
+            if self.sender_variant:
+                eng.set_sender_variant(*self.sender_variant)
             if self.engine is None:
                 self.engine = eng
                 self._adopt(eng)
@@ -354,6 +379,9 @@ class Game(object):
         inputs = (data, desc) if autograd and bool(exchange_args.get("input_grad", self.input_grad)) else (None, None)
         if autograd and self.flipout and bool(exchange_args.get("channel_grad", self.channel_grad)):
             raise NotImplementedError("channel_grad with message flips: the straight-through surrogate under a flip is not defined")
+        if autograd:
+            self._refuse_variant_graph(bool(exchange_args.get("channel_grad", self.channel_grad)),
+                                       bool(exchange_args.get("input_grad", self.input_grad)))
         if autograd and self.world > 1:
             raise NotImplementedError("autograd through exchange() runs on one GPU only (data-parallel training: Game.train_step)")
         corrupt_mask = None
