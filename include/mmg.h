@@ -18,7 +18,7 @@
  *   mmg_dp_train_step[s]   <- the same block on one rank of a data-parallel job (statistics + gradient
  *                             all-reduce; couplings model.py:912-915, 947-961, 1310)
  *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (non-attention, sender_mix=sum)
- *   mmg_receiver_forward   <- Receiver.forward              model.py:303-477 (non-desc_attn)
+ *   mmg_receiver_forward   <- Receiver.forward              model.py:303-477 (the desc_attn branch on a handle of mmg_attn_create)
  *   mmg_baseline_forward   <- Baseline.forward              model.py:496-516
  *   mmg_exchange_vjp       <- loss.backward() of ONE agent's graph for any loss built from exchange()'s outputs
  *                             (model.py:1309, 1316, 1322, 1328; graphs split at model.py:807-811, 826-829, 835-843)
@@ -222,6 +222,43 @@ int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec
  * another parameter layout), or flips are set; the setting before stays. */
 enum { MMG_MIX_SUM = 0, MMG_MIX_PROD = 1 };
 int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_receiver);
+
+/* Description attention, the reference's -desc_attn (model.py:267-271, 344-410, 444-445): the receiver's class description is no
+ * fixed bag-of-words mean but, per sample and step, an attention over the WORDS of each description with the GRU state as the query.
+ * With set [n_words, V] = the word vectors of all classes concatenated (a word without a vector is a row of zeros and is still
+ * attended over), lens[D] > 0 the words per class, A = attn_dim and h = h_z after the GRU update:
+ *   score[b, j] = d_attn(tanh(d_d(set[j]) + d_h(h[b])));   alpha = softmax of score inside each class's segment
+ *   wdesc[b, d] = sum_{j in d} alpha[b, j] set[j];         y[b, d] = y2(relu(y1([wdesc[b, d] || h[b]])))   -- the description FIRST:
+ *                 y1.weight[:, :V] multiplies the description and y1.weight[:, V:] the state, the opposite of the plain receiver
+ *   dbar[b]     = sum_d softmax(y)[b, d].detach() wdesc[b, d]: alpha keeps its graph there, so the receiver's message stream trains
+ *                 d_d / d_h / d_attn and h at every step before the output step, the class logits at the output step
+ * desc [D, V] is still an argument of every entry and is NOT read by an attention receiver.
+ * The twins below take (cfg, attn_dim, n_words); with attn_dim == 0 each returns exactly what its plain twin returns.  attn_dim > 0:
+ *   - six more receiver tensors under the reference's state_dict names, BEHIND its fifteen and inside its contiguous range (clip norm,
+ *     optimizer state and checkpoints cover them like the others; the other agents' tensors move up): d_d.weight [A, V], d_d.bias [A],
+ *     d_h.weight [A, R], d_h.bias [A], d_attn.weight [1, A], d_attn.bias [1].  d_attn.bias shifts every score of a softmax segment
+ *     alike: its gradient is EXACTLY zero here (the reference's autograd leaves rounding noise there, which RMSprop turns into steps
+ *     of the size of the learning rate) -- it stays bit-identical under every optimizer;
+ *   - more workspace arrays behind the plain ones, among them "alpha" [T, B, n_words];
+ *   - supported: attn_dim 1..128, n_classes <= n_words <= 2048, n_classes <= 128, batch <= 512, one GPU (global_batch == batch);
+ *     anything else is an error.
+ * mmg_set_desc_set uploads the set (d_set: DEVICE memory, copied into the workspace) and the segment table (lens: HOST memory, D
+ * entries, each > 0, summing to n_words == the handle's); a blocking call, required before the first conversation, repeatable.  The
+ * per-word tables (set . d_d.weight^T + d_d.bias, set . y1.weight[:, :V]^T, set . w_d.weight^T) are rebuilt from the current
+ * parameters by every forward entry, like the per-class tables of the plain receiver.
+ * Kernels: the generic per-sample family in instantiations of its own -- k_attn_prep -> k_conversation_attn -> baselines and
+ * statistics launches -> k_bwd_conv_attn -> k_attn_dE, k_attn_dDD -> k_wgrad -- for training, evaluation and the agent-level entry
+ * alike; no entry runs the plain receiver on such a handle.  Not offered, each an error: mmg_set_message_flipout /
+ * mmg_set_sender_variant with anything set, mmg_dp_train_step[s], mmg_exchange_vjp[_channel], mmg_vjp_input_grads and the per-call
+ * VJPs. */
+int64_t mmg_attn_param_count(const mmg_config* cfg, int attn_dim, int n_words);
+int64_t mmg_attn_grad_floats(const mmg_config* cfg, int attn_dim, int n_words);
+int     mmg_attn_param_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_param_entry* out, int max_entries);
+int64_t mmg_attn_workspace_bytes(const mmg_config* cfg, int attn_dim, int n_words);
+int     mmg_attn_tape_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_tape_entry* out, int max_entries);
+mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int n_words, void* d_workspace, int64_t workspace_bytes,
+                            float* d_params, float* d_grads, float* d_opt_state);
+int     mmg_set_desc_set(mmg_handle* h, const float* d_set, const int32_t* lens, int n_words);
 
 /* Dev evaluation inside the library (eval_dev's loop body, model.py:620-691): n consecutive evaluation conversations, each
  * followed on the same stream by ONE reduction launch (k_eval_reduce) that leaves what the reference computes per dev batch

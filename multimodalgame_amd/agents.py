@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from . import flags as _flags
 
 
@@ -262,10 +263,12 @@ class Sender(_Agent):
 
 
 class Receiver(_Agent):
-    """model.py:241-477 (non-desc_attn)."""
+    """model.py:241-477.  desc_attn=True (the reference's -desc_attn / -desc_attn_dim, model.py:267-271, 344-410): the receiver
+    attends over the words of every description -- forward() then needs desc_set [n_words, desc_dim] and desc_set_lens, and the
+    module owns d_d, d_h and d_attn beside the reference's other layers, under the reference's state_dict names."""
     agent_name = "receiver"
 
-    def __init__(self, z_dim, desc_dim, hid_dim, out_dim, w_dim, s_dim, use_binary):
+    def __init__(self, z_dim, desc_dim, hid_dim, out_dim, w_dim, s_dim, use_binary, desc_attn=False, desc_attn_dim=64):
         super().__init__()
         if out_dim != 1 or s_dim != 1:
             raise NotImplementedError("rec_out_dim and rec_s_dim must be 1 (the reference's only working setting)")
@@ -278,6 +281,14 @@ class Receiver(_Agent):
         self.y1 = nn.Linear(hid_dim + desc_dim, hid_dim)
         self.y2 = nn.Linear(hid_dim, out_dim)
         self.s = nn.Linear(hid_dim, s_dim)
+        self.desc_attn = bool(desc_attn)
+        self.attn_dim = int(desc_attn_dim) if self.desc_attn else 0
+        if self.desc_attn:                                                # model.py:267-271
+            if not 1 <= self.attn_dim <= _lib.ATTN_MAX_DIM:
+                raise NotImplementedError("desc_attn_dim must be 1..%d (got %d)" % (_lib.ATTN_MAX_DIM, self.attn_dim))
+            self.d_d = nn.Linear(desc_dim, self.attn_dim)
+            self.d_h = nn.Linear(hid_dim, self.attn_dim)
+            self.d_attn = nn.Linear(self.attn_dim, 1)
         self.reset_parameters()
         self.reset_state()
 
@@ -306,6 +317,11 @@ class Receiver(_Agent):
     def forward(self, z, desc, desc_set=None, desc_set_lens=None):
         game = self._bound_game(z.size(0))
         B = z.size(0)
+        if self.desc_attn:
+            if getattr(game, "autograd", False) and self.training and torch.is_grad_enabled():
+                raise NotImplementedError("autograd through Receiver.forward with desc_attn is not available (the per-call VJPs do "
+                                          "not form the attention); Game.train_step trains an attention receiver")
+            game.set_desc_set(desc_set, desc_set_lens)                    # (an unchanged pair is not uploaded again)
         if self._graph_on(game):
             input_grad = getattr(game, "input_grad", False)
             if desc.requires_grad and not input_grad:

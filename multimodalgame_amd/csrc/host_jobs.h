@@ -27,6 +27,14 @@ struct JobBuilder {
         tiles += ((N + 15) / 16) * g.tiles_k * g.nsplit;
         return g;
     }
+    // a job whose rows are NOT (step, sample) rows whatever their count (the words of a description set): never compact, never split
+    GemmJob& gemm_fixed(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int rows, int N, int Kk) {
+        const int keep = split_rows;
+        split_rows = -1;
+        GemmJob& g = gemm(A, lda, Bm, ldb, 0, SRC_STATIC, C, ldc, rows, N, Kk);
+        split_rows = keep;
+        return g;
+    }
     // dW = (dbeta * w2 * relu'(hid))^T . input  with the first factor formed on the fly
     void gemm_virt(const float* dbeta, const float* hid, const float* w2, const float* Bm, int ldb, int bmod,
                    float* C, int ldc, int rows, int N, int Kk) {
@@ -84,9 +92,25 @@ static int build_jobs(mmg_handle* h, CodeBiasJob code_bias, bool small_split) {
     jb.gemm(tp.dgh, 3 * R, tp.h, R, 0, SRC_STATIC, G.p[R_WHH], R, TB, 3 * R, R);          // rnn.weight_hh (h before the step)
     jb.bias(tp.dgi, 3 * R, TB, 3 * R, G.p[R_BIH]);
     jb.bias(tp.dgh, 3 * R, TB, 3 * R, G.p[R_BHH]);
+    if (h->attn_dim) {
+        // description attention (model.py:409-410 puts the description FIRST): y1.weight[:, :V] = dE^T . set, y1.weight[:, V:] = dA^T . h*;
+        // the three extra layers: d_d from dDD over the words, d_h and d_attn.weight from the (step, sample) tapes of k_bwd_conv_attn.
+        // d_attn.bias has NO job: a shift inside a softmax segment -- its gradient is exactly zero, the buffer keeps mmg_attn_create's zero
+        const AttnTape& atp = h->at.tp; const AttnParams& AG = h->AG;
+        const int A = h->attn_dim, NW = h->n_words;
+        jb.gemm_fixed(atp.attn_dE, R, atp.attn_set, V, G.p[R_Y1_W], R + V, NW, R, V);
+        jb.gemm(tp.dA, R, tp.hstar, R, 0, SRC_STATIC, G.p[R_Y1_W] + V, R + V, B, R, R);
+        jb.gemm_fixed(atp.attn_dDD, A, atp.attn_set, V, AG.p[A_DD_W], V, NW, A, V);
+        jb.col(atp.attn_dDD, A, NW, A, AG.p[A_DD_B], nullptr).compact = 0;
+        jb.gemm(atp.attn_ddh, A, tp.h + (size_t)B * R, R, 0, SRC_STATIC, AG.p[A_DH_W], R, TB, A, R);   // d_h (h after the step)
+        jb.bias(atp.attn_ddh, A, TB, A, AG.p[A_DH_B]);
+        jb.bias(atp.attn_dv, A, TB, A, AG.p[A_DA_W]);
+    } else {
     jb.gemm(tp.dA, R, tp.hstar, R, 0, SRC_STATIC, G.p[R_Y1_W], R + V, B, R, R);           // y1.weight[:, :R]
     jb.gemm(tp.dC, R, tp.descc, V, 0, SRC_STATIC, G.p[R_Y1_W] + R, R + V, D, R, V);      // y1.weight[:, R:]
-    jb.col(tp.dC, R, D, R, G.p[R_Y1_B], nullptr);
+    }
+    if (h->attn_dim) jb.col(tp.dA, R, B, R, G.p[R_Y1_B], nullptr).compact = 0;             // y1.bias = sum_b dA (sum_d first, where it cancels: bwd_conv_body.h)
+    else jb.col(tp.dC, R, D, R, G.p[R_Y1_B], nullptr);
     jb.col(tp.Py2, R, D, R, G.p[R_Y2_W], nullptr);
     jb.col(tp.dysum, 1, B, 1, G.p[R_Y2_B], nullptr);
     if (bin) {

@@ -44,6 +44,7 @@ struct LaunchPlan {
     bool merge_prep = false, fwd_basehx = false;         // k_prep's blocks / the basehx tiles as roles of the conversation launch (basehx at the call: train && !all rows)
     decltype(&k_conversation_fast3<256, 32, 64, 100, false>) fast_fn = nullptr;
     decltype(&k_conversation<256>) conv_fn = nullptr, agent_fn = nullptr;   // whole conversation / the agent-level entries' step window (k_conversation<256>)
+    decltype(&k_conversation_attn<256>) conv_attn_fn = nullptr, agent_attn_fn = nullptr;   // ... of an attention handle (the receiver's entries; the sender's run agent_fn)
     int fast_smem = 0;                          // dynamic LDS of fast_fn
     const char *conv_name = "k_conversation", *bwd_name = "k_bwd_conv";
     bool bas_defer_ok = false, bas_pending_ok = false;   // roles of the backward launch (fused step) / of k_bas_stats (phased step)
@@ -77,6 +78,7 @@ struct Selection {
     int wgrad_stride = 0;        // > 0: k_wgrad's GEMM tiles are walked by this many resident workgroups (more tiles than slots); 0: one workgroup per tile
     bool wgrad_opt_ok = false;   // the clip + optimizer step can run inside k_wgrad's launch (k_wgrad<true>: every block co-resident, no row splits); MMG_NO_WGRAD_OPT=1: off
     bool flip = false;           // message flips are set on a binary handle (mmg_set_message_flipout): k_conversation_fast3<FLIP> / k_conversation<FLIP> serve it, nothing else
+    bool attn = false;           // an attention handle (mmg_attn_create): the generic per-sample family with k_conversation_attn / k_bwd_conv_attn serves it, nothing else
     int variant = 0;             // the sender variant in effect (mmg_set_sender_variant; SV_* bits, SV_IGNORE_REC on a binary handle only): != 0: the generic
                                  // per-sample family with k_conversation<NT, false, VAR> / k_bwd_conv<MANY, VAR> serves the handle, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
@@ -166,6 +168,13 @@ struct mmg_handle {
     // mmg_set_sender_variant: SV_* bits as the caller set them (layout.h).  Host state; what is in effect on this handle is sel.variant, which the
     // forward entries copy into ConvArgs::sender_var and the backward / sender-VJP launches pass as sv
     int sender_var = 0;
+    // mmg_attn_create: desc_attn_dim (0: a plain handle) and the words of the description set; `at` is what the ATTN instantiations get
+    // on top of the plain kernels' arguments (the six tensors inside the flat buffer, the attention arrays behind the plain tape), AG
+    // the six gradient tensors; set_ready: mmg_set_desc_set has uploaded a set
+    int attn_dim = 0, n_words = 0;
+    AttnArgs at = {};
+    AttnParams AG = {};
+    bool set_ready = false;
     WgHead vjp_hd[8] = {};       // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
     ~mmg_handle() {
         for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }

@@ -126,6 +126,10 @@ static void plan_launches(mmg_handle* h) {
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, true> : k_conversation<256, true>;
         p.agent_fn = k_conversation<256, true>;
     }
+    if (s.attn) {                                // description attention: the ATTN instantiations (shape_pass has cleared every other family)
+        p.conv_attn_fn = s.conv_threads == 512 ? k_conversation_attn<512> : k_conversation_attn<256>;
+        p.agent_attn_fn = k_conversation_attn<256>;
+    }
     if (s.variant) {                             // a sender variant: the VAR instantiations (shape_pass has cleared every other conversation kernel)
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, true> : k_conversation<256, false, true>;
         p.agent_fn = k_conversation<256, false, true>;
@@ -194,7 +198,7 @@ static void plan_launches(mmg_handle* h) {
         // (a sender variant: the reverse step of tanh(h_x) / tanh(h_x * h_w); ignore_receiver alone needs none -- the tape holds the zeros)
         if (s.variant & SV_IGNORE_CODE) p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true, SV_IGNORE_CODE> : k_bwd_conv<false, SV_IGNORE_CODE>;
         else if (s.variant & SV_PROD) p.bwd_conv_fn = d.B > 512 ? k_bwd_conv<true, SV_PROD> : k_bwd_conv<false, SV_PROD>;
-        p.dc = merge_dc ? DC_NONE : DC_PLAIN;
+        p.dc = (merge_dc || s.attn) ? DC_NONE : DC_PLAIN;     // (attention: k_attn_dE forms Py2 beside dE, y1.bias comes from dA)
     }
 }
 
@@ -232,15 +236,19 @@ static Switches read_switches() {
 // mmg_set_sender_variant; err_word: the pinned error word exists)
 // settle alone.  A capability that also needs a co-residency budget (tile_split, tile_persist, mc_ok) leaves here as a CANDIDATE: its
 // preconditions hold and s.ask names the occupancy it waits for; decide() confirms or clears it.
-static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool err_word, Selection& s) {
+static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool err_word, Selection& s,
+                      int attn_dim = 0, int n_words = 0) {
     s = Selection();
+    // description attention: the generic per-sample family in its ATTN instantiations; every other family is cleared below (use_fast, tile_ok)
+    s.attn = attn_dim > 0;
+    if (s.attn && (flips || variant)) return fail("desc_attn with message flips or a sender variant");
     // message flips on binary messages (continuous ones are not flipped: the setting is kept and nothing happens)
     s.flip = flips && d.use_binary;
     // a sender variant (ignore_receiver on binary messages only, like the flips): the generic per-sample kernels form it -- the register-resident
     // family with the one-launch step, the many-class kernels, the sample tiles and the wide receiver do not, so all of them are cleared here
     s.variant = variant & (d.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
     if (s.variant && s.flip) return fail("message flips and a sender variant on one handle");
-    s.use_fast = !w[SW_NO_FAST] && !s.variant; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
+    s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.attn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
     s.sw_merge_prep = !w[SW_NO_MERGE_PREP] && !no_roles;
     s.sw_merge_bas = s.merge_roles;
     s.persist_ll = !w[SW_NO_PERSIST_LL] && persist_ll_shape(cfg.batch, cfg.h_dim, cfg.w_dim, cfg.rec_hidden, cfg.wv_dim, cfg.n_classes, cfg.max_exchange);
@@ -253,6 +261,11 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     s.conv_smem = conv_smem_floats(d, s.conv_threads) * 4;
     s.conv_smem_agent = conv_smem_floats(d, MMG_BLOCK) * 4;
     s.bwd_smem = bwd_smem_floats(d, (s.variant & (SV_PROD | SV_IGNORE_CODE)) == SV_PROD) * 4;
+    if (s.attn) {
+        s.conv_smem = conv_attn_smem_floats(d, s.conv_threads, attn_dim, n_words) * 4;
+        s.conv_smem_agent = conv_attn_smem_floats(d, MMG_BLOCK, attn_dim, n_words) * 4;
+        s.bwd_smem = bwd_attn_smem_floats(d, attn_dim, n_words) * 4;
+    }
     s.prep_smem = ((d.V > d.W ? d.V : d.W) + 16) * 4;
     // hundreds of classes: 8 per class block of k_prep (weight rows in registers across them); few classes: one per block (latency)
     s.prep_cpb = (d.D >= 256 && d.R <= 64 && d.V <= 128 && !(d.V & 3) && 2 * d.R <= MMG_BLOCK) ? 2 : 1;
@@ -279,7 +292,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
     //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
     // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
-    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant;
+    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.attn;
     s.tile_force = w[SW_TILE];
     // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
     // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -380,6 +393,8 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     if (s.conv_smem > 48 * 1024) raise_lds(s.conv_smem, k_conversation<256>, k_conversation<512>);
     if (s.conv_smem > 48 * 1024 && s.flip) raise_lds(s.conv_smem, k_conversation<256, true>, k_conversation<512, true>);
     if (s.conv_smem > 48 * 1024 && s.variant) raise_lds(s.conv_smem, k_conversation<256, false, true>, k_conversation<512, false, true>);
+    if (s.conv_smem > 48 * 1024 && s.attn) raise_lds(s.conv_smem, k_conversation_attn<256>, k_conversation_attn<512>);
+    if (s.bwd_smem > 48 * 1024 && s.attn) raise_lds(s.bwd_smem, k_bwd_conv_attn);
     if (s.bwd_smem > 48 * 1024) raise_lds(s.bwd_smem, k_bwd_conv<false>, k_bwd_conv<true>);
     if (s.bwd_smem > 48 * 1024 && (s.variant & SV_IGNORE_CODE)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_IGNORE_CODE>, k_bwd_conv<true, SV_IGNORE_CODE>);
     else if (s.bwd_smem > 48 * 1024 && (s.variant & SV_PROD)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_PROD>, k_bwd_conv<true, SV_PROD>);
@@ -473,7 +488,7 @@ static int decide(mmg_handle* h, const Switches& w) {
 
 static int shape_pass(mmg_handle* h, const Switches& w) {
     h->no_roles = h->no_roles || w.roles_off();
-    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel);
+    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words);
 }
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();

@@ -361,180 +361,78 @@ __host__ __device__ inline int bwd_smem_floats(const Dims& d, bool prod = false)
 // be paid for by every handle.  SV_IGNORE_CODE: d h_w = 0 exactly, d h_x = dpre.  SV_IGNORE_REC needs nothing here -- tp.w holds the zeros --:
 // a handle with that bit alone runs k_bwd_conv<MANY>.
 // (MANY && VAR: 3 workgroups per CU, 168 VGPRs -- at 4 the recomputation spills, and k_bwd_conv<true> itself carries 48 bytes of scratch.)
-template <bool MANY, int VAR = 0>
-__global__ __launch_bounds__(MMG_BLOCK, MANY ? (VAR ? 3 : 4) : 1) void k_bwd_conv(Dims dm, Params P, Tape tp, const int64_t* __restrict__ target) {
-    constexpr int TU = MANY ? 2 : 8;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int B = dm.B, H = dm.H, W = dm.W, R = dm.R, V = dm.V, D = dm.D, T = dm.T;
+#define MMG_BWD_ATTN 0
+#include "bwd_conv_body.h"
+#undef MMG_BWD_ATTN
+
+__host__ __device__ inline int bwd_attn_smem_floats(const Dims& d, int A, int NW) {
     auto p4 = [](int n) { return (n + 3) & ~3; };
-    float* p = smem;
-    LossCoef lc; lc.cw = p; p += 3 * T; lc.ce = p; p += 3 * T; lc.cb = p; p += T;
-    p = smem + ((7 * T + 3) & ~3);
-    float* s_dhx = p; p += p4(H);   float* s_da = p; p += p4(H);   float* s_dpre = p; p += p4(H);
-    float* s_dlz = p; p += p4(W);   float* s_dlw = p; p += p4(W);  float* s_dc0 = p; p += p4(W);
-    float* s_dh = p; p += p4(R);    float* s_dhn = p; p += p4(R);  float* s_dg = p; p += p4(R);
-    float* s_A = p; p += p4(R);     float* s_dA = p; p += p4(R);   float* s_hs = p; p += p4(R);
-    float* s_dgi = p; p += p4(3 * R); float* s_dgh = p; p += p4(3 * R);
-    float* s_dy = p; p += p4(D);
-    float* s_red = p; p += 4 * MMG_BLOCK;
-    float* s_misc = p;
-    float* s_hw = s_misc + 32;                                    // SV_PROD only (bwd_smem_floats(d, true)): h_w of the step, recomputed
-    constexpr bool prod = VAR == SV_PROD, no_code = (VAR & SV_IGNORE_CODE) != 0;
+    return bwd_smem_floats(d) + 2 * p4(NW) + 2 * p4(A) + p4(d.D);
+}
 
-    loss_coefficients(dm, tp.stats, lc, nullptr, nullptr);        // logged losses: spare block of k_wgrad
+#define MMG_BWD_ATTN 1
+#include "bwd_conv_body.h"
+#undef MMG_BWD_ATTN
 
-    const bool binary = dm.use_binary != 0;
-    const int tstar = tp.tstar[b];
-    const float L = tp.logs[b];
-    const float* cw_s = lc.cw, *cw_r = lc.cw + T, *cw_z = lc.cw + 2 * T;
-    const float* ce_s = lc.ce, *ce_r = lc.ce + T, *ce_z = lc.ce + 2 * T;
+// ---------------------------------------------------------------------------------------------
+// The two reductions of an attention handle that are no GEMM over (step, sample) rows.  Fixed order, no float atomics.
+// k_attn_dE: grid = D.  With pre[b, d, :] recomputed from alpha at t*(b) and E, dpre[b, d, r] = dy[b, d] w_y2[r] 1[pre > 0]:
+//   dE[j, r] = sum_b alpha*[b, j] dpre[b, class j, r]  (-> y1.weight[:, :V] = dE^T . set)
+//   Py2[d, r] = sum_b dy[b, d] relu(pre[b, d, r]) (-> y2.weight): the plain tape's array and job.  (y1.bias = sum_b dA, from k_bwd_conv_attn.)
+// A thread owns unit r = tid % RL for the words j0 + g + k groups (g = tid / RL, k < 8) of a chunk of 8 * groups words of the class's
+// segment, sums over the samples in order and keeps its 8 sums in registers; a longer segment takes one pass over the samples per chunk.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MMG_BLOCK) void k_attn_dE(Dims dm, Params P, Tape tp, AttnArgs at) {
+    const int d = blockIdx.x, tid = threadIdx.x, R = dm.R, B = dm.B, D = dm.D, NW = at.NW;
+    const int RL = R < MMG_BLOCK ? R : MMG_BLOCK, groups = MMG_BLOCK / RL, g = tid / RL, r = tid - g * RL;
+    const int j0 = at.tp.attn_seg[d], j1 = at.tp.attn_seg[d + 1];
+    if (g >= groups) return;
+    const float* E = at.tp.attn_E;
+    const float w2 = P.p[R_Y2_W][r], b1 = P.p[R_Y1_B][r];
+    for (int c0 = j0; c0 < j1; c0 += 8 * groups) {
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float py = 0.f;
+        for (int b = 0; b < B; ++b) {
+            const float* al = at.tp.alpha + ((size_t)tp.tstar[b] * B + b) * NW;
+            float pre = tp.Astar[(size_t)b * R + r] + b1;
+#pragma unroll 8
+            for (int j = j0; j < j1; ++j) pre = fmaf(al[j], E[(size_t)j * R + r], pre);     // (loads of 8 words in flight; the sum keeps its order)
+            const float dyv = tp.dy[(size_t)b * D + d];
+            const float dp = pre > 0.f ? dyv * w2 : 0.f;
+            py = fmaf(dyv, fmaxf(pre, 0.f), py);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const int j = c0 + g + k * groups; acc[k] = fmaf(j < j1 ? al[j] : 0.f, dp, acc[k]); }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int j = c0 + g + k * groups; if (j < j1) at.tp.attn_dE[(size_t)j * R + r] = acc[k]; }
+        if (c0 == j0 && g == 0) tp.Py2[(size_t)d * R + r] = py;
+    }
+}
 
-    for (int i = tid; i < R; i += nt) s_dh[i] = 0.f;
-    for (int i = tid; i < H; i += nt) s_dhx[i] = 0.f;
+// k_attn_dDD: grid = NW.  dDD[j, a] = sum over the live rows of dscore[row, j] v[a] (1 - tanh^2(DD[j, a] + dh[row, a])): tanh depends on row,
+// word and unit, so this is no GEMM.  The workgroup of word j holds S = MMG_BLOCK / A row slices per unit: slice s walks the rows s, s + S, ...
+// in order, and the slices' sums are added in slice order.
+__global__ __launch_bounds__(MMG_BLOCK) void k_attn_dDD(Dims dm, Tape tp, AttnArgs at) {
+    __shared__ float s_part[MMG_BLOCK];
+    const int tid = threadIdx.x, A = at.A, NW = at.NW, B = dm.B, TB = dm.T * dm.B, j = blockIdx.x;
+    const int S = MMG_BLOCK / A, s = tid / A, a = tid - s * A;
+    if (s < S) {
+        const float dd = at.tp.attn_DD[(size_t)j * A + a];
+        float acc = 0.f;
+        for (int row = s; row < TB; row += S) {
+            const int t = row / B, b = row - t * B;
+            if (t > tp.tstar[b]) continue;
+            const float ds = at.tp.dscore[(size_t)row * NW + j];
+            if (ds != 0.f) { const float th = tanhf(dd + at.tp.attn_dh[(size_t)row * A + a]); acc = fmaf(ds, 1.f - th * th, acc); }
+        }
+        s_part[tid] = acc;
+    }
     __syncthreads();
-
-    // ---------------- zero the gradient tapes of steps this sample never took ----------------
-    for (int t = tstar + 1; t < T; ++t) {
-        const size_t row = (size_t)t * B + b;
-        for (int i = tid; i < W; i += nt) { tp.dlz[row * W + i] = 0.f; tp.dlw[row * W + i] = 0.f; }
-        for (int i = tid; i < H; i += nt) tp.dpre[row * H + i] = 0.f;
-        for (int i = tid; i < R; i += nt) tp.dgpre[row * R + i] = 0.f;
-        for (int i = tid; i < 3 * R; i += nt) { tp.dgi[row * 3 * R + i] = 0.f; tp.dgh[row * 3 * R + i] = 0.f; }
-        if (tid == 0) { tp.dls[row] = 0.f; tp.dbs[row] = 0.f; tp.dbr[row] = 0.f; }
+    if (tid < A) {
+        float v = 0.f;
+        for (int q = 0; q < S; ++q) v += s_part[q * A + tid];
+        at.tp.attn_dDD[(size_t)j * A + tid] = v * at.P.p[A_DA_W][tid];
     }
-
-    // ---------------- reverse time ----------------
-    for (int t = tstar; t >= 0; --t) {
-        const size_t row = (size_t)t * B + b;
-        const float* hn = tp.h + ((size_t)(t + 1) * B + b) * R;    // h after step t
-        const float* hp = tp.h + ((size_t)t * B + b) * R;          // h before step t
-
-        // ---- receiver message head (stream 1: active while m_{t+1} == 1) ----
-        const bool act_next = binary && (t < tstar);
-        if (act_next) {
-            const float wh = (L - tp.br[row]) * cw_r[t];
-            for (int j = tid; j < W; j += nt) {
-                const float v = bit_seed(tp.w[row * W + j], tp.pw[row * W + j], wh, ce_r[t]);
-                s_dlw[j] = v; tp.dlw[row * W + j] = v;
-            }
-            __syncthreads();
-            gemv_t<TU>(P.p[R_W_W], R, W, R, s_dlw, s_dg, s_red, false);            // dg = W_w^T dlw
-            for (int i = tid; i < R; i += nt) {
-                const float g = tp.g[row * R + i];
-                const float v = s_dg[i] * (1.f - g * g);
-                s_dg[i] = v; tp.dgpre[row * R + i] = v;
-            }
-            __syncthreads();
-            gemv_t<TU>(P.p[R_WH_W], R, R, R, s_dg, s_dh, s_red, true);             // dh += W_h^T dgpre
-        } else {
-            for (int j = tid; j < W; j += nt) tp.dlw[row * W + j] = 0.f;
-            for (int i = tid; i < R; i += nt) tp.dgpre[row * R + i] = 0.f;
-        }
-        // ---- stop head (stream 0, Adaptive only) ----
-        if (binary && !dm.fixed) {
-            const float wh = (L - tp.br[row]) * cw_s[t];
-            const float dls = bit_seed(tp.s[row], tp.ps[row], wh, ce_s[t]);
-            if (tid == 0) tp.dls[row] = dls;
-            const float* ws = P.p[R_S_W];
-            for (int i = tid; i < R; i += nt) s_dh[i] += ws[i] * dls;
-        } else if (tid == 0) {
-            tp.dls[row] = 0.f;
-        }
-        __syncthreads();
-        // ---- class logits at the output step (NLL, model.py:1271) ----
-        if (t == tstar) {
-            const int tgt = (int)target[b];
-            float dsum = 0.f;
-            for (int d = tid; d < D; d += nt) {
-                const float v = (tp.sm[(size_t)b * D + d] - (d == tgt ? 1.f : 0.f)) / (float)dm.Bg;
-                s_dy[d] = v; tp.dy[(size_t)b * D + d] = v; dsum += v;
-            }
-            dsum = block_sum(dsum, s_misc);
-            if (tid == 0) tp.dysum[b] = dsum;
-            for (int i = tid; i < R; i += nt) { const float v = hn[i]; s_hs[i] = v; tp.hstar[(size_t)b * R + i] = v; }
-            __syncthreads();
-            gemv_rows<(MANY ? 2 : 4)>(P.p[R_Y1_W], R + V, R, R, s_hs, [&](int n, float acc) { s_A[n] = acc; });
-            __syncthreads();
-            const float* w2 = P.p[R_Y2_W];
-            for (int i = tid; i < R; i += nt) {
-                const float a = s_A[i];
-                float acc = 0.f;
-                for (int d = 0; d < D; d += 8) {                               // 8 class rows of Cd in flight, same add order
-                    float cv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) cv[u] = tp.Cd[(size_t)min(d + u, D - 1) * R + i];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) acc += (d + u < D && a + cv[u] > 0.f) ? s_dy[min(d + u, D - 1)] : 0.f;
-                }
-                const float v = acc * w2[i];
-                s_dA[i] = v; tp.dA[(size_t)b * R + i] = v; tp.Astar[(size_t)b * R + i] = a;
-            }
-            __syncthreads();
-            gemv_t<TU>(P.p[R_Y1_W], R + V, R, R, s_dA, s_dh, s_red, true);         // dh += W_y1h^T dA
-        }
-        // ---- GRU cell backward ----
-        {
-            const float* gr = tp.gru + row * 4 * R;
-            for (int i = tid; i < R; i += nt) {
-                const float rr = gr[i], uu = gr[R + i], nn = gr[2 * R + i], ghn = gr[3 * R + i];
-                const float dh = s_dh[i];
-                const float dn = dh * (1.f - uu), du = dh * (hp[i] - nn);
-                const float dnp = dn * (1.f - nn * nn), dup = du * uu * (1.f - uu);
-                const float drp = dnp * ghn * rr * (1.f - rr);
-                s_dgi[i] = drp; s_dgi[R + i] = dup; s_dgi[2 * R + i] = dnp;
-                s_dgh[i] = drp; s_dgh[R + i] = dup; s_dgh[2 * R + i] = dnp * rr;
-                s_dhn[i] = dh * uu;
-            }
-            __syncthreads();
-            for (int i = tid; i < 3 * R; i += nt) { tp.dgi[row * 3 * R + i] = s_dgi[i]; tp.dgh[row * 3 * R + i] = s_dgh[i]; }
-            gemv_t<TU>(P.p[R_WHH], R, 3 * R, R, s_dgh, s_dhn, s_red, true);        // dh_{t-1} += W_hh^T dgh
-            for (int i = tid; i < R; i += nt) s_dh[i] = s_dhn[i];
-            __syncthreads();
-        }
-        // ---- sender (stream 2) ----
-        if (binary) {
-            const float wh = (L - tp.bs[row]) * cw_z[t];
-            for (int j = tid; j < W; j += nt) {
-                const float v = bit_seed(tp.z[row * W + j], tp.pz[row * W + j], wh, ce_z[t]);
-                s_dlz[j] = v; tp.dlz[row * W + j] = v;
-                if (VAR && prod && t > 0) s_dc0[j] = tp.c[row * W + j];        // the step's code input (s_dc0 is free until t = 0)
-            }
-            __syncthreads();
-            // VAR: h_w = W_c c_t + b_c again (t = 0: tp.hw0), beside the product below -- no barrier of its own: gemv_t ends with one
-            if (VAR && prod && t > 0) gemv_rows<(MANY ? 2 : 4)>(P.p[S_CODE_W], W, H, W, s_dc0, [&](int n, float acc) { s_hw[n] = acc; });
-            gemv_t<TU>(P.p[S_BIN_W], H, W, H, s_dlz, s_da, s_red, false);          // da = W_b^T dlz
-            for (int i = tid; i < H; i += nt) {
-                const float a = tp.a[row * H + i];
-                const float v = s_da[i] * (1.f - a * a);
-                if (VAR && prod) {                                             // a = tanh(h_x * h_w), model.py:217-218
-                    const float hw = (t == 0) ? tp.hw0[i] : s_hw[i] + P.p[S_CODE_B][i];
-                    const float dhw = v * tp.hx[(size_t)b * H + i];
-                    s_dpre[i] = dhw; tp.dpre[row * H + i] = dhw; s_dhx[i] += v * hw;
-                } else if (VAR && no_code) {                                   // a = tanh(h_x), model.py:208-210: nothing reaches code_layer / code_bias
-                    s_dpre[i] = 0.f; tp.dpre[row * H + i] = 0.f; s_dhx[i] += v;
-                } else {
-                    s_dpre[i] = v; tp.dpre[row * H + i] = v; s_dhx[i] += v;
-                }
-            }
-            __syncthreads();
-            if (t == 0) {                                                      // code_bias path (model.py:199)
-                gemv_t<TU>(P.p[S_CODE_W], W, H, W, s_dpre, s_dc0, s_red, false);
-                for (int j = tid; j < W; j += nt) tp.dc0[(size_t)b * W + j] = s_dc0[j];
-            }
-            // ---- baselines (MSE, model.py:971-988) ----
-            const float dbs = lc.cb[t] * (tp.bs[row] - L), dbr = lc.cb[t] * (tp.br[row] - L);
-            // d hidden = dbeta * w2 * 1[hidden > 0] is formed on the fly by k_wgrad (virtual operand)
-            if (tid == 0) { tp.dbs[row] = dbs; tp.dbr[row] = dbr; }
-        } else {
-            for (int i = tid; i < W; i += nt) tp.dlz[row * W + i] = 0.f;
-            for (int i = tid; i < H; i += nt) tp.dpre[row * H + i] = 0.f;
-            if (tid == 0) { tp.dbs[row] = 0.f; tp.dbr[row] = 0.f; }
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < H; i += nt) tp.dhx[(size_t)b * H + i] = s_dhx[i];
-    if (!binary) for (int j = tid; j < W; j += nt) tp.dc0[(size_t)b * W + j] = 0.f;
 }
 
 // Active rows.  Every gradient tape row (t, b) with t > t*(b) is zero, and with early stopping that is most of them

@@ -432,338 +432,29 @@ __global__ __launch_bounds__(64) void k_xcc_probe(uint32_t* __restrict__ out) {
 // FLIP: the instantiations a handle with message flips runs (flip_msg at both message sites); a compile-time switch, so that
 // the kernels of every other handle stay what they were.  VAR: likewise for a handle with a sender variant (ar.sender_var: SV_* bits); a
 // handle has flips or a variant, never both, so FLIP && VAR is not instantiated
-template <int NT, bool FLIP = false, bool VAR = false>
-__global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp, ConvArgs ar) {
-    constexpr int GU = NT == 512 ? 8 : 4;               // row passes per load batch of gemv_rows
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int B = dm.B, H = dm.H, W = dm.W, R = dm.R, V = dm.V, D = dm.D, T = dm.T;
-    ConvSmem s;
-    {
-        float* p = smem;
-        s.hx = p; p += pad4(H);  s.a = p; p += pad4(H);
-        s.c = p; p += pad4(W);   s.z = p; p += pad4(W);  s.w = p; p += pad4(W);
-        s.lp = p; p += pad4(W);  s.ne = p; p += pad4(W);
-        s.h = p; p += pad4(R);   s.hn = p; p += pad4(R); s.A = p; p += pad4(R);
-        s.g = p; p += pad4(R);   s.g2 = p; p += pad4(R);
-        s.gi = p; p += pad4(3 * R); s.gh = p; p += pad4(3 * R);
-        s.y = p; p += pad4(D);   s.yout = p; p += pad4(D);
-        s.dbar = p; p += pad4(V);
-        s.red = p; p += 4 * NT;
-        s.misc = p;
-    }
-    float* s_ne = s.ne;
+#define MMG_CONV_ATTN 0
+#include "conversation_body.h"
+#undef MMG_CONV_ATTN
 
-    const bool do_sen = ar.phases & 1, do_rec = ar.phases & 2;
-    const bool binary = dm.use_binary != 0;
-    const bool train = ar.train != 0;
+__host__ __device__ inline int conv_attn_smem_floats(const Dims& d, int nthreads, int A, int NW) {
+    auto p4 = [](int n) { return (n + 3) & ~3; };
+    return conv_smem_floats(d, nthreads) + 2 * p4(NW) + p4(A);
+}
 
-    // ---- conversation state ----
-    if (do_sen) for (int i = tid; i < H; i += nt) s.hx[i] = tp.hx[(size_t)b * H + i];
-    if (do_rec) {
-        for (int i = tid; i < R; i += nt)
-            s.h[i] = ar.h_state ? ar.h_state[(size_t)b * R + i] : (ar.t_begin == 0 ? 0.f : tp.h[((size_t)ar.t_begin * B + b) * R + i]);
-        if (ar.t_begin == 0 && !ar.h_state) for (int i = tid; i < R; i += nt) tp.h[(size_t)b * R + i] = 0.f;
-    }
-    for (int j = tid; j < W; j += nt) {
-        float wv = dm.first_rec;                                   // model.py:786
-        if (ar.t_begin > 0) wv = ar.w_in ? ar.w_in[(size_t)b * W + j] : tp.w[((size_t)(ar.t_begin - 1) * B + b) * W + j];
-        s.w[j] = wv;
-    }
-    if (tid == 0) {
-        s.misc[0] = 1.f;                                           // running stop mask m_t
-        s.misc[1] = -1.f;                                          // t* (not yet known)
-        s.misc[2] = (ar.sprod_state && !ar.sprod_first) ? ar.sprod_state[b] : 1.f;   // running prod of p_s
-        if (ar.t_begin == 0 && do_rec) tp.mask[b] = 1;             // stop_mask[0] = ones   model.py:775
-    }
-    __syncthreads();
+#define MMG_CONV_ATTN 1
+#include "conversation_body.h"
+#undef MMG_CONV_ATTN
 
-    const uint32_t mb_counter = tp.counter[0];
-    const uint32_t gb = (uint32_t)(dm.boff + b);                   // index inside the GLOBAL minibatch
-
-    int t = ar.t_begin;
-    for (; t < ar.t_end; ++t) {
-        const size_t row = (size_t)t * B + b;
-        // ================= Sender (model.py:193-238) =================
-        if (do_sen) {
-            // code input: sigmoid(code_bias) at t == 0 (hw0 precomputed), else the receiver's last message
-            for (int j = tid; j < W; j += nt) {
-                const float cv = s.w[j];
-                s.c[j] = cv;
-                tp.zr[row * W + j] = cv;                           // z_r fed to baseline_sen (model.py:836)
-                tp.c[row * W + j] = (t == 0) ? sigmoidf_(P.p[S_CODE_BIAS][j]) : cv;
-            }
-            __syncthreads();
-            const bool no_code = VAR && (ar.sender_var & SV_IGNORE_CODE);     // model.py:208-210: h_w is not used (the reference computes and drops it)
-            if (t > 0 && !no_code) {
-                // (epilogues only park the sums in LDS: a bias / uniform load inside them would be one dependent
-                //  global round trip per row pass, executed by a single lane of each group)
-                gemv_rows<GU>(P.p[S_CODE_W], W, H, W, s.c, [&](int n, float acc) { s.a[n] = acc; });
-                __syncthreads();
-            }
-            const float* bc = P.p[S_CODE_B];
-            for (int i = tid; i < H; i += nt) {
-                float av;
-                if (VAR && no_code) {
-                    av = tanhf(s.hx[i]);                           // model.py:208-210
-                } else {
-                    const float hw = (t == 0) ? tp.hw0[i] : s.a[i] + bc[i];
-                    av = (VAR && (ar.sender_var & SV_PROD)) ? tanhf(s.hx[i] * hw)      // model.py:217-218
-                                                            : tanhf(s.hx[i] + hw);     // model.py:216
-                }
-                s.a[i] = av;
-                tp.a[row * H + i] = av;
-            }
-            __syncthreads();
-            {
-                const float* bb = P.p[S_BIN_B];
-                const float* uz = ar.u_z ? ar.u_z + row * W : nullptr;
-                gemv_rows<GU>(P.p[S_BIN_W], H, W, H, s.a, [&](int n, float acc) { s.z[n] = acc; });
-                __syncthreads();
-                for (int n = tid; n < W; n += nt) {
-                    const float lz = s.z[n] + bb[n];
-                    float zz = lz, lpv = 0.f, nev = 0.f;
-                    if (binary) {
-                        const float p = sigmoidf_(lz);             // model.py:223
-                        if (train) {
-                            const float u = uz ? uz[n] : philox_uniform(ar.seed, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, 0u);
-                            zz = (u < p) ? 1.f : 0.f;              // model.py:227
-                        } else {
-                            zz = rintf(p);                         // model.py:229 (torch.round = half-to-even)
-                        }
-                        if (FLIP) zz = flip_msg(ar, false, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, zz);   // model.py:233-234
-                        tp.pz[row * W + n] = p;
-                        const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
-                        lpv = zz * l1 + (1.f - zz) * l0;           // model.py:908-910
-                        nev = p * l1 + (1.f - p) * l0;             // model.py:919-922
-                    }
-                    zz = corrupt_msg(ar, n, zz);                   // model.py:813-820 (evaluation only)
-                    s.z[n] = zz; s.lp[n] = lpv; s_ne[n] = nev;
-                    tp.z[row * W + n] = zz;
-                }
-            }
-            __syncthreads();
-            if (binary) {
-                float lpv = 0.f, nev = 0.f;
-                for (int j = tid; j < W; j += nt) { lpv += s.lp[j]; nev += s_ne[j]; }
-                lpv = block_sum(lpv, s.misc + 8);
-                nev = block_sum(nev, s.misc + 16);
-                if (tid == 0) { tp.lp_z[row] = lpv; tp.ne_z[row] = nev; }
-            }
-        } else {
-            // receiver-only call: the message comes from the tape slot of this step
-            for (int j = tid; j < W; j += nt) s.z[j] = tp.z[row * W + j];
-            __syncthreads();
-        }
-        if (!do_rec) continue;
-
-        // ================= Receiver (model.py:333-342, 411-477) =================
-        {   // GRUCell (model.py:340); gate order r, z(u), n
-            const float* bih = P.p[R_BIH]; const float* bhh = P.p[R_BHH];
-            gemv_rows<GU>(P.p[R_WIH], W, 3 * R, W, s.z, [&](int n, float acc) { s.gi[n] = acc; });
-            gemv_rows<GU>(P.p[R_WHH], R, 3 * R, R, s.h, [&](int n, float acc) { s.gh[n] = acc; });
-            __syncthreads();
-            for (int i = tid; i < 3 * R; i += nt) { s.gi[i] += bih[i]; s.gh[i] += bhh[i]; }
-        }
-        __syncthreads();
-        for (int i = tid; i < R; i += nt) {
-            const float rr = sigmoidf_(s.gi[i] + s.gh[i]);
-            const float uu = sigmoidf_(s.gi[R + i] + s.gh[R + i]);
-            const float ghn = s.gh[2 * R + i];
-            const float nn = tanhf(s.gi[2 * R + i] + rr * ghn);
-            const float hv = nn + uu * (s.h[i] - nn);
-            s.hn[i] = hv;
-            float* gr = tp.gru + row * 4 * R;
-            gr[i] = rr; gr[R + i] = uu; gr[2 * R + i] = nn; gr[3 * R + i] = ghn;
-            tp.h[((size_t)(t + 1) * B + b) * R + i] = hv;
-        }
-        __syncthreads();
-        {   // stop head (model.py:414-427) and the h-half of y1 (Appendix A.2)
-            const float bsv = P.p[R_S_B][0];
-            gemv_rows<GU>(P.p[R_S_W], R, 1, R, s.hn, [&](int n, float acc) {
-                const float p = sigmoidf_(acc + bsv);
-                float sv;
-                if (train) {
-                    const float u = ar.u_s ? ar.u_s[row] : philox_uniform(ar.seed, (uint32_t)(t * dm.Bg + gb), mb_counter, 1u);
-                    sv = (u < p) ? 1.f : 0.f;                      // model.py:420
-                } else {
-                    const float prod = dm.s_prob_prod ? s.misc[2] * p : p;   // model.py:423-426 (misc[2] == 1 on a fresh conversation)
-                    s.misc[2] = prod;
-                    sv = rintf(prod);                              // model.py:427
-                }
-                tp.s[row] = sv; tp.ps[row] = p;
-                const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
-                tp.lp_s[row] = sv * l1 + (1.f - sv) * l0;
-                tp.ne_s[row] = p * l1 + (1.f - p) * l0;
-                s.misc[3] = sv;
-            });
-            gemv_rows<GU>(P.p[R_Y1_W], R + V, R, R, s.hn, [&](int n, float acc) { s.A[n] = acc; });
-        }
-        __syncthreads();
-        {   // y[d] = b_y2 + sum_r w_y2[r] * relu(A[r] + Cd[d,r])      (model.py:432-433)
-            const float* w2 = P.p[R_Y2_W];
-            const float b2 = P.p[R_Y2_B][0];
-            const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-            const bool vec = (R & 3) == 0;
-            const int items = vec ? (R >> 2) : R;
-            int G = 1; while (G < 64 && G < items) G <<= 1;
-            const int rpw = 64 / G, sub = lane / G, gl = lane - sub * G;
-            constexpr int U = 4;                                    // class passes loaded together (cf. gemv_rows)
-            const int stride = nw * rpw;
-            for (int d0 = wave * rpw + sub; d0 < D + sub; d0 += stride * U) {
-                float acc[U];
-                const float* crow[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) { acc[u] = 0.f; crow[u] = tp.Cd + (size_t)min(d0 + u * stride, D - 1) * R; }
-                if (vec) {
-                    for (int k = gl; k < items; k += G) {
-                        float4 cv[U];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) cv[u] = reinterpret_cast<const float4*>(crow[u])[k];
-                        const float4 av = reinterpret_cast<const float4*>(s.A)[k];
-                        const float4 wv = reinterpret_cast<const float4*>(w2)[k];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            acc[u] = fmaf(wv.x, fmax_nn(av.x + cv[u].x, 0.f), acc[u]); acc[u] = fmaf(wv.y, fmax_nn(av.y + cv[u].y, 0.f), acc[u]);
-                            acc[u] = fmaf(wv.z, fmax_nn(av.z + cv[u].z, 0.f), acc[u]); acc[u] = fmaf(wv.w, fmax_nn(av.w + cv[u].w, 0.f), acc[u]);
-                        }
-                    }
-                } else {
-                    for (int k = gl; k < items; k += G) {
-                        float cv[U];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) cv[u] = crow[u][k];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) acc[u] = fmaf(w2[k], fmax_nn(s.A[k] + cv[u], 0.f), acc[u]);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int d = d0 + u * stride;
-                    const float r = group_sum(acc[u], G);
-                    if (gl == 0 && d < D) { const float yv = r + b2; s.y[d] = yv; tp.y[row * D + d] = yv; }
-                }
-            }
-        }
-        __syncthreads();
-        {   // stop-mask bookkeeping (model.py:852) -- uniform decision for the whole workgroup
-            const float m_t = s.misc[0], sv = s.misc[3];
-            const float m_next = fminf(m_t, sv);
-            const bool first_stop = (m_next == 0.f) && (s.misc[1] < 0.f);
-            const bool last = (t == T - 1);
-            if (first_stop || (last && s.misc[1] < 0.f)) {
-                for (int d = tid; d < D; d += nt) s.yout[d] = s.y[d];   // the output step (model.py:1261-1264)
-            }
-            __syncthreads();
-            if (tid == 0) {
-                tp.mask[(size_t)(t + 1) * B + b] = (uint8_t)(m_next != 0.f);
-                if (first_stop || (last && s.misc[1] < 0.f)) s.misc[1] = (float)t;
-                s.misc[0] = m_next;
-            }
-            __syncthreads();
-            // a sample whose conversation has ended contributes nothing further to any loss (its
-            // query w_t is never read: the receiver-message stream is active only while m_{t+1} == 1)
-            if (!ar.run_all && !dm.fixed && train && m_next == 0.f) { ++t; break; }
-        }
-        // softmax(y) (detached, model.py:441) and the description mixture (model.py:442-449)
-        float mx = -3.4e38f;
-        for (int d = tid; d < D; d += nt) mx = fmaxf(mx, s.y[d]);
-        mx = block_max(mx, s.misc + 8);
-        float se = 0.f;
-        for (int d = tid; d < D; d += nt) { const float e = expf(s.y[d] - mx); s.y[d] = e; se += e; }
-        se = block_sum(se, s.misc + 16);
-        const float inv = 1.f / se;
-        for (int d = tid; d < D; d += nt) s.y[d] *= inv;
-        __syncthreads();
-        gemv_t(ar.desc, V, D, V, s.y, s.dbar, s.red, false);
-        for (int v = tid; v < V; v += nt) tp.dbar[row * V + v] = s.dbar[v];
-        {   // h_w = tanh(w_h(h) + w_d(dbar))   (model.py:452)
-            gemv_rows<GU>(P.p[R_WH_W], R, R, R, s.hn, [&](int n, float acc) { s.g[n] = acc; });
-            gemv_rows<GU>(P.p[R_WD_W], V, R, V, s.dbar, [&](int n, float acc) { s.g2[n] = acc; });
-        }
-        __syncthreads();
-        for (int i = tid; i < R; i += nt) {
-            const float gv = tanhf((s.g[i] + P.p[R_WH_B][i]) + s.g2[i]);
-            s.g[i] = gv;
-            tp.g[row * R + i] = gv;
-            s.h[i] = s.hn[i];                                       // advance the GRU state
-        }
-        __syncthreads();
-        {   // receiver message (model.py:454-475)
-            const float* bw = P.p[R_W_B];
-            const float* uw = ar.u_w ? ar.u_w + row * W : nullptr;
-            gemv_rows<GU>(P.p[R_W_W], R, W, R, s.g, [&](int n, float acc) { s.w[n] = acc; });
-            __syncthreads();
-            for (int n = tid; n < W; n += nt) {
-                const float lw = s.w[n] + bw[n];
-                float wv = lw, lpv = 0.f, nev = 0.f;
-                if (binary) {
-                    const float p = sigmoidf_(lw);
-                    if (train) {
-                        const float u = uw ? uw[n] : philox_uniform(ar.seed, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, 2u);
-                        wv = (u < p) ? 1.f : 0.f;                  // model.py:460
-                    } else {
-                        wv = rintf(p);                             // model.py:462
-                    }
-                    if (FLIP) wv = flip_msg(ar, true, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, wv);       // model.py:467-468
-                    if (VAR && (ar.sender_var & SV_IGNORE_REC)) wv = 0.f;                                          // model.py:470-472 (the draw above is still consumed)
-                    tp.pw[row * W + n] = p;
-                    const float l1 = logf(p + MMG_EPS), l0 = logf(1.f - p + MMG_EPS);
-                    lpv = wv * l1 + (1.f - wv) * l0;
-                    nev = p * l1 + (1.f - p) * l0;
-                }
-                s.w[n] = wv; s.lp[n] = lpv; s_ne[n] = nev;
-                tp.w[row * W + n] = wv;
-            }
-        }
-        __syncthreads();
-        if (binary) {
-            float lpv = 0.f, nev = 0.f;
-            for (int j = tid; j < W; j += nt) { lpv += s.lp[j]; nev += s_ne[j]; }
-            lpv = block_sum(lpv, s.misc + 8);
-            nev = block_sum(nev, s.misc + 16);
-            if (tid == 0) { tp.lp_w[row] = lpv; tp.ne_w[row] = nev; }
-        }
-        __syncthreads();
-    }
-    if (!do_rec) return;
-
-    // ---- agent-level state hand-back ----
-    if (ar.h_state) for (int i = tid; i < R; i += nt) ar.h_state[(size_t)b * R + i] = s.h[i];
-    if (ar.sprod_state && tid == 0) ar.sprod_state[b] = s.misc[2];
-    if (ar.t_end != T && s.misc[1] < 0.f) return;     // partial window without an output step
-    if (ar.t_begin != 0) return;
-
-    // ---- output selection, log-softmax, reward, top-k (model.py:1264-1275, 1333-1339) ----
-    const int tstar = dm.fixed ? (T - 1) : (int)s.misc[1];
-    if (dm.fixed) {
-        __syncthreads();
-        for (int d = tid; d < D; d += nt) s.yout[d] = tp.y[((size_t)(T - 1) * B + b) * D + d];
-        __syncthreads();
-    }
-    if (tid == 0) tp.tstar[b] = tstar;
-    float mx = -3.4e38f;
-    for (int d = tid; d < D; d += nt) mx = fmaxf(mx, s.yout[d]);
-    mx = block_max(mx, s.misc + 8);
-    float se = 0.f;
-    for (int d = tid; d < D; d += nt) se += expf(s.yout[d] - mx);
-    se = block_sum(se, s.misc + 16);
-    const float lse = mx + logf(se);
-    const int tgt = ar.target ? (int)ar.target[b] : -1;
-    const float dt = (tgt >= 0) ? (s.yout[tgt] - lse) : 0.f;
-    float above = 0.f;
-    for (int d = tid; d < D; d += nt) {
-        const float o = s.yout[d], ld = o - lse;
-        tp.outp[(size_t)b * D + d] = o;
-        tp.dist[(size_t)b * D + d] = ld;
-        tp.sm[(size_t)b * D + d] = expf(ld);
-        if (tgt >= 0 && ld > dt) above += 1.f;
-    }
-    above = block_sum(above, s.misc + 8);
-    if (tid == 0) {
-        tp.logs[b] = dt;
-        tp.hit[b] = (tgt >= 0 && above < (float)dm.top_k) ? 1 : 0;
-    }
+// The per-word tables of an attention handle, formed once per forward entry from the CURRENT parameters (as k_prep forms Cd / Dd), on the
+// matrix cores: DD = set . d_d.weight^T + d_d.bias | E = set . y1.weight[:, :V]^T | G = set . w_d.weight^T.  One workgroup per 16 x 16 tile.
+__host__ __device__ inline int attn_prep_tiles(int NW, int N) { return ((NW + 15) / 16) * ((N + 15) / 16); }
+__global__ __launch_bounds__(MMG_BLOCK) void k_attn_prep(Dims dm, Params P, AttnArgs at) {
+    const int NW = at.NW, A = at.A, R = dm.R, V = dm.V;
+    const int n_dd = attn_prep_tiles(NW, A), n_e = attn_prep_tiles(NW, R);
+    const int tile = blockIdx.x;
+    if (tile < n_dd) gemm_nt_tile(tile, at.tp.attn_set, V, at.P.p[A_DD_W], V, at.P.p[A_DD_B], at.tp.attn_DD, A, NW, A, V);
+    else if (tile < n_dd + n_e) gemm_nt_tile(tile - n_dd, at.tp.attn_set, V, P.p[R_Y1_W], R + V, nullptr, at.tp.attn_E, R, NW, R, V);
+    else gemm_nt_tile(tile - n_dd - n_e, at.tp.attn_set, V, P.p[R_WD_W], V, nullptr, at.tp.attn_G, R, NW, R, V);
 }
 
 // ---------------------------------------------------------------------------------------------

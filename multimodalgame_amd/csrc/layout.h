@@ -25,17 +25,35 @@ enum ParamId {
     P_COUNT
 };
 
+// Description attention (model.py:267-271): the receiver's three extra layers.  They exist on an attention handle only (mmg_attn_create,
+// attn_dim > 0) and lie BEHIND the receiver's fifteen tensors, inside its contiguous range -- the receiver's clip norm and optimizer
+// cover them with no special case, and every tensor of the other agents moves up by their size.  Kept out of ParamId / Params: those
+// travel by value to every kernel, and the kernels of a plain handle keep their arguments.
+enum AttnParamId { A_DD_W, A_DD_B, A_DH_W, A_DH_B, A_DA_W, A_DA_B, A_COUNT };
+#define MMG_MAX_ATTN 128       // desc_attn_dim
+#define MMG_MAX_WORDS 2048     // rows of the description set (the reference's 30- and 70-class files hold fewer than 1 000 words)
+#define MMG_ATTN_MAX_CLASSES 128
+#define MMG_ATTN_MAX_BATCH 512
+
 struct ParamLayout {
     int64_t off[P_COUNT];
     int32_t rows[P_COUNT], cols[P_COUNT], agent[P_COUNT];
     const char* name[P_COUNT];
     int64_t agent_begin[5];   // agent a occupies [agent_begin[a], agent_begin[a+1])
     int64_t total;
+    int32_t attn_dim;         // 0: no attention tensors (a_off then all equal the sender's begin, a_rows zero)
+    int64_t a_off[A_COUNT];
+    int32_t a_rows[A_COUNT], a_cols[A_COUNT];
+    const char* a_name[A_COUNT];
 };
 
-inline ParamLayout param_layout(const mmg_config& c) {
+inline ParamLayout param_layout(const mmg_config& c, int attn_dim = 0) {
     ParamLayout L;
-    const int H = c.h_dim, W = c.w_dim, R = c.rec_hidden, V = c.wv_dim, K = c.bas_hidden, F = c.feat_dim;
+    const int H = c.h_dim, W = c.w_dim, R = c.rec_hidden, V = c.wv_dim, K = c.bas_hidden, F = c.feat_dim, A = attn_dim;
+    struct AE { const char* n; int rows, cols; };
+    const AE atab[A_COUNT] = {{"d_d.weight", A, V}, {"d_d.bias", A, 0}, {"d_h.weight", A, R}, {"d_h.bias", A, 0},
+                              {"d_attn.weight", A > 0 ? 1 : 0, A}, {"d_attn.bias", A > 0 ? 1 : 0, 0}};
+    L.attn_dim = A;
     struct E { ParamId id; const char* n; int agent, rows, cols; };
     const E tab[P_COUNT] = {
         {R_WIH, "rnn.weight_ih", 0, 3 * R, W}, {R_WHH, "rnn.weight_hh", 0, 3 * R, R},
@@ -58,7 +76,14 @@ inline ParamLayout param_layout(const mmg_config& c) {
     int cur_agent = -1;
     for (int i = 0; i < P_COUNT; ++i) {
         const E& e = tab[i];
-        if (e.agent != cur_agent) { cur_agent = e.agent; L.agent_begin[cur_agent] = o; }
+        if (e.agent != cur_agent) {
+            if (cur_agent == 0) for (int k = 0; k < A_COUNT; ++k) {      // the receiver's range ends with the attention tensors
+                L.a_off[k] = o; L.a_rows[k] = atab[k].rows; L.a_cols[k] = atab[k].cols; L.a_name[k] = atab[k].n;
+                const int64_t n = (int64_t)atab[k].rows * (atab[k].cols ? atab[k].cols : 1);
+                o += (n + 3) & ~(int64_t)3;
+            }
+            cur_agent = e.agent; L.agent_begin[cur_agent] = o;
+        }
         L.off[e.id] = o; L.rows[e.id] = e.rows; L.cols[e.id] = e.cols; L.agent[e.id] = e.agent; L.name[e.id] = e.n;
         int64_t n = (int64_t)e.rows * (e.cols ? e.cols : 1);
         o += (n + 3) & ~(int64_t)3;     // every tensor starts on a 16-byte boundary (float4 loads)
@@ -74,6 +99,14 @@ struct Params { float* p[P_COUNT]; };
 inline Params resolve_params(const ParamLayout& L, float* base) {
     Params P;
     for (int i = 0; i < P_COUNT; ++i) P.p[i] = base + L.off[i];
+    return P;
+}
+
+struct AttnParams { float* p[A_COUNT]; };
+
+inline AttnParams resolve_attn_params(const ParamLayout& L, float* base) {
+    AttnParams P;
+    for (int i = 0; i < A_COUNT; ++i) P.p[i] = base + L.a_off[i];
     return P;
 }
 
@@ -266,6 +299,35 @@ struct Tape {
 #undef X
 };
 
+// The workspace arrays of an attention handle (mmg_attn_create), BEHIND the plain tape: the plain handle's workspace, Tape and kernel
+// arguments stay what they are.  Extra symbols in the dims: NW (words of the description set) and A (desc_attn_dim).  Nothing here
+// has B * D * V or B * NW * V entries: everything downstream of alpha is linear in the set, so the per-word tables DD / E / G hoist
+// out of the conversation the way Cd / Dd do.
+#define MMG_ATTN_TAPE_LIST(X)                                                      \
+    X(attn_set, float, 0, 2, NW, V, 1)     /* desc_set: the word vectors of all classes, concatenated (mmg_set_desc_set)      model.py:345 */ \
+    X(attn_seg, int32_t, 2, 1, D + 1, 1, 1) /* first word of every class's segment, [D] = NW                                   model.py:370-375 */ \
+    X(attn_cls, int32_t, 2, 1, NW, 1, 1)   /* class of every word                                                              */ \
+    X(attn_DD, float, 0, 2, NW, A, 1)      /* set . d_d.weight^T + d_d.bias                                                    model.py:352 */ \
+    X(attn_E, float, 0, 2, NW, R, 1)       /* set . y1.weight[:, :V]^T: a word's share of y1's pre-activation                  model.py:409-432 */ \
+    X(attn_G, float, 0, 2, NW, R, 1)       /* set . w_d.weight^T: a word's share of w_d(dbar) (the backward's query path)      model.py:452 */ \
+    X(alpha, float, 0, 3, T, B, NW)        /* attention weights: softmax of the scores inside each class's segment            model.py:377-380 */ \
+    X(attn_dh, float, 0, 3, T, B, A)       /* d_h(h_z)                                                                         model.py:359 */ \
+    /* ---- backward ---- */                                                       \
+    X(dscore, float, 0, 3, T, B, NW)       /* dL/d score on the live rows                                                      */ \
+    X(attn_ddh, float, 0, 3, T, B, A)      /* dL/d d_h(h_z): sum_j u[j, :]  -> d_h.weight, d_h.bias                            */ \
+    X(attn_dv, float, 0, 3, T, B, A)       /* sum_j dscore[j] tanh(DD[j] + dh)  -> d_attn.weight                               */ \
+    X(attn_dDD, float, 0, 2, NW, A, 1)     /* dL/d DD  -> d_d.weight, d_d.bias (k_attn_dDD)                                    */ \
+    X(attn_dE, float, 0, 2, NW, R, 1)      /* dL/d E   -> y1.weight[:, :V] (k_attn_dE)                                         */
+
+struct AttnTape {
+#define X(name, ctype, code, nd, d0, d1, d2) ctype* name;
+    MMG_ATTN_TAPE_LIST(X)
+#undef X
+};
+
+// What the ATTN instantiations get on top of the plain kernels' arguments
+struct AttnArgs { int A, NW; AttnParams P; AttnTape tp; };
+
 // row slices per output tile of k_wgrad's (step, sample)-row jobs: with thousands of rows the few dozen output tiles of the
 // small receiver matrices would otherwise be a handful of long-running workgroups
 __host__ __device__ inline int wgrad_nsplit(int TB, long long ptotal) {
@@ -308,14 +370,14 @@ __host__ __device__ inline bool persist_ll_shape(int B, int H, int W, int R, int
 __host__ __device__ inline int dc_slices(int B) { return B >= 1024 ? 4 : 1; }
 
 struct TapeLayout {
-    int n;
-    mmg_tape_entry e[176];
+    int n, n_plain;           // entries; of which the plain tape's (the attention arrays follow them)
+    mmg_tape_entry e[192];
     int64_t total;
 };
 
 constexpr bool tape_name_is(const char* a, const char* b) { return *a == *b && (*a == 0 || tape_name_is(a + 1, b + 1)); }
 
-inline TapeLayout tape_layout(const mmg_config& c) {
+inline TapeLayout tape_layout(const mmg_config& c, int attn_dim = 0, int n_words = 0) {
     TapeLayout L;
     L.n = 0;
     const int64_t B = c.batch, D = c.n_classes, F = c.feat_dim, H = c.h_dim, W = c.w_dim, R = c.rec_hidden,
@@ -334,11 +396,11 @@ inline TapeLayout tape_layout(const mmg_config& c) {
                   NRCT16 = rc_shape((int)B, (int)H, (int)W, (int)R, (int)V, (int)D) ? 16 * ((B + 15) / 16) : 1,
                   NRCW = rc_shape((int)B, (int)H, (int)W, (int)R, (int)V, (int)D) ? W / 16 : 1,
                   NMCB = mc_shape((int)H, (int)W, (int)R, (int)V, (int)D, (int)T) && !c.use_binary ? 16 : 0,
-                  NWP = wgrad_any_split((int)(T * B), param_layout(c).total) ? (int64_t)16 * (param_layout(c).total + 512 * 64) : 4;   /* (every job splits <= 16 ways) */
+                  NWP = wgrad_any_split((int)(T * B), param_layout(c, attn_dim).total) ? (int64_t)16 * (param_layout(c, attn_dim).total + 512 * 64) : 4;   /* (every job splits <= 16 ways) */
     (void)NPLT; (void)NPLS; (void)F; (void)V; (void)NPB; (void)NDCS; (void)NWP; (void)NS2P; (void)NTILE; (void)NHLP; (void)NZP; (void)NMC; (void)NMCB; (void)NRCB; (void)NRCJ; (void)NRCW; (void)NRCX; (void)NRCP; (void)NRCA; (void)NRCZ; (void)NRCH; (void)NRCT16;
     int64_t o = 0;
     const int64_t esz[4] = {4, 1, 4, 8};
-#define X(name_, ctype, code, nd, d0, d1, d2)                                        \
+#define MMG_TAPE_ENTRY(name_, ctype, code, nd, d0, d1, d2)                           \
     {                                                                               \
         mmg_tape_entry& e = L.e[L.n++];                                             \
         memset(&e, 0, sizeof(e));                                                   \
@@ -349,13 +411,19 @@ inline TapeLayout tape_layout(const mmg_config& c) {
         int64_t bytes = (int64_t)(d0) * (d1) * (d2) * esz[code];                    \
         o += (bytes + 255) & ~(int64_t)255;                                         \
     }
-    MMG_TAPE_LIST(X)
-#undef X
-#define X(name_, ctype, code, nd, d0, d1, d2) +1
-    static_assert(0 MMG_TAPE_LIST(X) <= (int)(sizeof(L.e) / sizeof(L.e[0])), "TapeLayout::e is too small for MMG_TAPE_LIST");
-#undef X
+    MMG_TAPE_LIST(MMG_TAPE_ENTRY)
 #define X(name_, ctype, code, nd, d0, d1, d2) && (!tape_name_is(#name_, "tables") || (d0) == MMG_TABLE_BYTES)
     static_assert(true MMG_TAPE_LIST(X), "MMG_TABLE_BYTES is not the size of tape.tables in MMG_TAPE_LIST");
+#undef X
+    L.n_plain = L.n;
+    if (attn_dim > 0) {
+        const int64_t A = attn_dim, NW = n_words;
+        (void)A; (void)NW;
+        MMG_ATTN_TAPE_LIST(MMG_TAPE_ENTRY)
+    }
+#undef MMG_TAPE_ENTRY
+#define X(name_, ctype, code, nd, d0, d1, d2) +1
+    static_assert(0 MMG_TAPE_LIST(X) MMG_ATTN_TAPE_LIST(X) <= (int)(sizeof(L.e) / sizeof(L.e[0])), "TapeLayout::e is too small for both lists");
 #undef X
     L.total = o;
     return L;
@@ -366,6 +434,17 @@ inline Tape resolve_tape(const TapeLayout& L, void* base) {
     int i = 0;
 #define X(name, ctype, code, nd, d0, d1, d2) t.name = (ctype*)((char*)base + L.e[i++].offset);
     MMG_TAPE_LIST(X)
+#undef X
+    return t;
+}
+
+inline AttnTape resolve_attn_tape(const TapeLayout& L, void* base) {
+    AttnTape t;
+    memset(&t, 0, sizeof(t));
+    if (L.n == L.n_plain) return t;
+    int i = L.n_plain;
+#define X(name, ctype, code, nd, d0, d1, d2) t.name = (ctype*)((char*)base + L.e[i++].offset);
+    MMG_ATTN_TAPE_LIST(X)
 #undef X
     return t;
 }

@@ -132,66 +132,97 @@ static int validate(const mmg_config* c) {
     return 0;
 }
 
-extern "C" int64_t mmg_param_count(const mmg_config* cfg) {
-    if (validate(cfg)) return -1;
-    return param_layout(*cfg).total;
+// Description attention (mmg_attn_*): attn_dim == 0 is the plain handle; otherwise the supported range, an error beyond it
+static int validate_attn(const mmg_config* c, int attn_dim, int n_words) {
+    if (validate(c)) return -1;
+    if (attn_dim == 0) return 0;
+    if (attn_dim < 0 || attn_dim > MMG_MAX_ATTN) return fail("desc_attn: attn_dim must be 1..%d (got %d)", MMG_MAX_ATTN, attn_dim);
+    if (c->n_classes > MMG_ATTN_MAX_CLASSES) return fail("desc_attn: n_classes must be <= %d (got %d)", MMG_ATTN_MAX_CLASSES, c->n_classes);
+    if (n_words < c->n_classes || n_words > MMG_MAX_WORDS)
+        return fail("desc_attn: n_words must be n_classes..%d, every description holding a word (got %d for %d classes)", MMG_MAX_WORDS, n_words, c->n_classes);
+    if (c->batch > MMG_ATTN_MAX_BATCH) return fail("desc_attn: batch must be <= %d (got %d)", MMG_ATTN_MAX_BATCH, c->batch);
+    if (c->global_batch > 0 && c->global_batch != c->batch) return fail("desc_attn runs on one GPU (global_batch %d != batch %d)", c->global_batch, c->batch);
+    return 0;
 }
 
-extern "C" int mmg_param_table(const mmg_config* cfg, mmg_param_entry* out, int max_entries) {
-    if (validate(cfg)) return -1;
-    ParamLayout L = param_layout(*cfg);
+extern "C" int64_t mmg_attn_param_count(const mmg_config* cfg, int attn_dim, int n_words) {
+    if (validate_attn(cfg, attn_dim, n_words)) return -1;
+    return param_layout(*cfg, attn_dim).total;
+}
+extern "C" int64_t mmg_param_count(const mmg_config* cfg) { return mmg_attn_param_count(cfg, 0, 0); }
+
+extern "C" int mmg_attn_param_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_param_entry* out, int max_entries) {
+    if (validate_attn(cfg, attn_dim, n_words)) return -1;
+    ParamLayout L = param_layout(*cfg, attn_dim);
+    const int n = P_COUNT + (attn_dim > 0 ? (int)A_COUNT : 0);
     if (out) {
-        if (max_entries < P_COUNT) return fail("need room for %d entries", (int)P_COUNT);
+        if (max_entries < n) return fail("need room for %d entries", n);
+        int k = 0;
+        auto put = [&](const char* name, int agent, int rows, int cols, int64_t off) {
+            memset(&out[k], 0, sizeof(out[k]));
+            strncpy(out[k].name, name, sizeof(out[k].name) - 1);
+            out[k].agent = agent; out[k].rows = rows; out[k].cols = cols; out[k].offset = off;
+            ++k;
+        };
         for (int i = 0; i < P_COUNT; ++i) {
-            memset(&out[i], 0, sizeof(out[i]));
-            strncpy(out[i].name, L.name[i], sizeof(out[i].name) - 1);
-            out[i].agent = L.agent[i]; out[i].rows = L.rows[i]; out[i].cols = L.cols[i]; out[i].offset = L.off[i];
+            if (i == S_IMG_W && attn_dim > 0)           // the attention tensors close the receiver's range
+                for (int a = 0; a < A_COUNT; ++a) put(L.a_name[a], MMG_AGENT_RECEIVER, L.a_rows[a], L.a_cols[a], L.a_off[a]);
+            put(L.name[i], L.agent[i], L.rows[i], L.cols[i], L.off[i]);
         }
     }
-    return P_COUNT;
+    return n;
 }
+extern "C" int mmg_param_table(const mmg_config* cfg, mmg_param_entry* out, int max_entries) { return mmg_attn_param_table(cfg, 0, 0, out, max_entries); }
 
-extern "C" int64_t mmg_grad_floats(const mmg_config* cfg) {
-    if (validate(cfg)) return -1;
-    return param_layout(*cfg).total + MMG_GRAD_TAIL;
+extern "C" int64_t mmg_attn_grad_floats(const mmg_config* cfg, int attn_dim, int n_words) {
+    if (validate_attn(cfg, attn_dim, n_words)) return -1;
+    return param_layout(*cfg, attn_dim).total + MMG_GRAD_TAIL;
 }
+extern "C" int64_t mmg_grad_floats(const mmg_config* cfg) { return mmg_attn_grad_floats(cfg, 0, 0); }
 
-extern "C" int64_t mmg_workspace_bytes(const mmg_config* cfg) {
-    if (validate(cfg)) return -1;
-    return tape_layout(*cfg).total;
+extern "C" int64_t mmg_attn_workspace_bytes(const mmg_config* cfg, int attn_dim, int n_words) {
+    if (validate_attn(cfg, attn_dim, n_words)) return -1;
+    return tape_layout(*cfg, attn_dim, n_words).total;
 }
+extern "C" int64_t mmg_workspace_bytes(const mmg_config* cfg) { return mmg_attn_workspace_bytes(cfg, 0, 0); }
 
-extern "C" int mmg_tape_table(const mmg_config* cfg, mmg_tape_entry* out, int max_entries) {
-    if (validate(cfg)) return -1;
-    TapeLayout L = tape_layout(*cfg);
+extern "C" int mmg_attn_tape_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_tape_entry* out, int max_entries) {
+    if (validate_attn(cfg, attn_dim, n_words)) return -1;
+    TapeLayout L = tape_layout(*cfg, attn_dim, n_words);
     if (out) {
         if (max_entries < L.n) return fail("need room for %d entries", L.n);
         memcpy(out, L.e, sizeof(mmg_tape_entry) * L.n);
     }
     return L.n;
 }
+extern "C" int mmg_tape_table(const mmg_config* cfg, mmg_tape_entry* out, int max_entries) { return mmg_attn_tape_table(cfg, 0, 0, out, max_entries); }
 
 // A handle with its layouts and the addresses inside the caller's buffers (no GPU call)
-static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, float* grads, float* opt_state) {
+static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, float* grads, float* opt_state, int attn_dim = 0, int n_words = 0) {
     mmg_handle* h = new mmg_handle();
     h->cfg = cfg;
     if (h->cfg.global_batch <= 0) h->cfg.global_batch = h->cfg.batch;
     h->dm = make_dims(h->cfg);
-    h->pl = param_layout(h->cfg);
-    h->tl = tape_layout(h->cfg);
+    h->attn_dim = attn_dim; h->n_words = attn_dim > 0 ? n_words : 0;
+    h->pl = param_layout(h->cfg, attn_dim);
+    h->tl = tape_layout(h->cfg, attn_dim, n_words);
     h->ws = ws; h->params = params; h->grads = grads; h->opt_state = opt_state;
     h->P = resolve_params(h->pl, params);
     h->G = resolve_params(h->pl, grads);
     h->tp = resolve_tape(h->tl, ws);
+    h->at.A = h->attn_dim; h->at.NW = h->n_words;
+    h->at.P = resolve_attn_params(h->pl, params);
+    h->AG = resolve_attn_params(h->pl, grads);
+    h->at.tp = resolve_attn_tape(h->tl, ws);
     h->d_jt = reinterpret_cast<JobTable*>(h->tp.tables);
     return h;
 }
 
-extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int64_t workspace_bytes,
-                                  float* d_params, float* d_grads, float* d_opt_state) {
-    if (validate(cfg)) return nullptr;
+extern "C" mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int n_words, void* d_workspace, int64_t workspace_bytes,
+                                       float* d_params, float* d_grads, float* d_opt_state) {
+    if (validate_attn(cfg, attn_dim, n_words)) return nullptr;
     if (!d_workspace || !d_params || !d_grads || !d_opt_state) { fail("NULL device buffer"); return nullptr; }
-    mmg_handle* h = new_handle(*cfg, d_workspace, d_params, d_grads, d_opt_state);
+    mmg_handle* h = new_handle(*cfg, d_workspace, d_params, d_grads, d_opt_state, attn_dim, n_words);
     if (workspace_bytes < h->tl.total) { fail("workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)h->tl.total); delete h; return nullptr; }
     if (hipHostMalloc((void**)&h->h_err, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) {
         *h->h_err = 0u;
@@ -229,6 +260,56 @@ extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int6
     if (e != hipSuccess) { fail("job table upload failed: %s", hipGetErrorString(e)); delete h; return nullptr; }
     if (upload_vjp_tables(h)) { delete h; return nullptr; }
     return h;
+}
+
+extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int64_t workspace_bytes,
+                                  float* d_params, float* d_grads, float* d_opt_state) {
+    return mmg_attn_create(cfg, 0, 0, d_workspace, workspace_bytes, d_params, d_grads, d_opt_state);
+}
+
+// The description set of an attention handle: the word vectors go into the workspace (the GEMM operand of the per-word tables and of
+// the y1 / d_d weight-gradient jobs), the segment table is built here from the lengths.  Blocking copies: a rare call, and nothing of
+// the handle may be in flight while the set changes.
+extern "C" int mmg_set_desc_set(mmg_handle* h, const float* d_set, const int32_t* lens, int n_words) {
+    if (!h) return fail("NULL handle");
+    if (!h->attn_dim) return fail("mmg_set_desc_set: not an attention handle (mmg_attn_create with attn_dim > 0)");
+    if (!d_set || !lens) return fail("mmg_set_desc_set: set / lens must not be NULL");
+    if (n_words != h->n_words) return fail("mmg_set_desc_set: %d words for a handle created for %d", n_words, h->n_words);
+    const int D = h->dm.D;
+    std::vector<int32_t> seg(D + 1), cls(n_words);
+    int64_t o = 0;
+    for (int d = 0; d < D; ++d) {
+        if (lens[d] <= 0) return fail("mmg_set_desc_set: description %d has %d words (every class needs at least one: its softmax is over its own words)", d, (int)lens[d]);
+        seg[d] = (int32_t)o;
+        if (o + lens[d] > n_words) return fail("mmg_set_desc_set: the %d lengths sum to more than n_words = %d", D, n_words);
+        for (int j = 0; j < lens[d]; ++j) cls[o + j] = d;
+        o += lens[d];
+    }
+    if (o != n_words) return fail("mmg_set_desc_set: the %d lengths sum to %lld, n_words is %d", D, (long long)o, n_words);
+    seg[D] = n_words;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(h->at.tp.attn_set, d_set, sizeof(float) * (size_t)n_words * h->dm.V, hipMemcpyDeviceToDevice));
+    HIP_OK(hipMemcpy(h->at.tp.attn_seg, seg.data(), sizeof(int32_t) * seg.size(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(h->at.tp.attn_cls, cls.data(), sizeof(int32_t) * cls.size(), hipMemcpyHostToDevice));
+    h->set_ready = true;
+    return 0;
+}
+
+// Gates of an attention handle: what it does not offer raises (never the plain receiver instead) ...
+static int refuse_attn(const mmg_handle* h, const char* who) {
+    if (h && h->attn_dim) return fail("%s is not available on a description-attention handle (desc_attn)", who);
+    return 0;
+}
+// ... and a conversation needs the description set
+static int attn_ready(const mmg_handle* h, const char* who) {
+    if (h->attn_dim && !h->set_ready) return fail("%s: desc_attn needs the description set first (mmg_set_desc_set)", who);
+    return 0;
+}
+static int launch_attn_prep(mmg_handle* h, hipStream_t st) {
+    Scope sc(h, st, "k_attn_prep");
+    const int tiles = attn_prep_tiles(h->n_words, h->attn_dim) + 2 * attn_prep_tiles(h->n_words, h->dm.R);
+    hipLaunchKernelGGL(k_attn_prep, dim3(tiles), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->at);
+    return launch_check("k_attn_prep");
 }
 
 extern "C" void mmg_destroy(mmg_handle* h) { delete h; }      // (~mmg_handle releases the events and the pinned error word)
@@ -416,7 +497,9 @@ static int launch_conv_sample(mmg_handle* h, hipStream_t st, ConvArgs ar, bool b
     if (s.family == FAM_FAST) {
         ar.nprep = p.merge_prep ? p.nprep_hx : 0; ar.prep_cpb = s.prep_cpb; ar.nbase = base_ready ? p.basehx_tiles : 0;
         hipLaunchKernelGGL(p.fast_fn, dim3(d.B + ar.nbase + (p.merge_prep ? ar.nprep + 1 : 0)), dim3(256), p.fast_smem, st, h->dm, h->P, h->tp, ar);
-    } else
+    } else if (s.attn)
+        hipLaunchKernelGGL(p.conv_attn_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar, h->at);
+    else
         hipLaunchKernelGGL(p.conv_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar);
     return launch_check("k_conversation");
 }
@@ -443,9 +526,11 @@ static int launch_baselines(mmg_handle* h, hipStream_t st, bool all_rows, bool d
 static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, const float* d_u_z,
                                  const float* d_u_s, const float* d_u_w, uint64_t seed, int train, TapeMode mode, void* stream, bool defer_bas = false) {
     if (!d_x || !d_desc) return fail("x / desc must not be NULL");
+    if (attn_ready(h, "exchange")) return -1;
     hipStream_t st = (hipStream_t)stream;
     const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
     if (!p.merge_prep && launch_prep(h, st, d_desc, d_x, train ? 1 : 0)) return -1;
+    if (s.attn && launch_attn_prep(h, st)) return -1;
     if (h->corrupt_on && train) return fail("a message corruption mask is set: training conversations are not corrupted (mmg_set_message_corruption(h, NULL, 0) clears it)");
     // TAPE_LOG (the minibatches whose log block reads the whole tape): the CONVERSATION runs every sample through all steps, everything else
     // is the training step's -- the baselines over the live rows only, in the statistics / backward launch (the log block prints no baseline score;
@@ -533,6 +618,7 @@ extern "C" int mmg_set_message_corruption(mmg_handle* h, const uint8_t* mask, in
 // k_conversation only (host_select.h).  The job table goes to the device again only where the family changed it.
 extern "C" int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec, float p_rec, int flipout_dev, uint64_t eval_seed) {
     if (!h) return fail("NULL handle");
+    if ((has_sen || has_rec) && refuse_attn(h, "mmg_set_message_flipout")) return -1;
     if (has_sen && !(p_sen >= 0.f && p_sen <= 1.f)) return fail("mmg_set_message_flipout: p_sen = %g is not a probability in [0, 1]", (double)p_sen);
     if (has_rec && !(p_rec >= 0.f && p_rec <= 1.f)) return fail("mmg_set_message_flipout: p_rec = %g is not a probability in [0, 1]", (double)p_rec);
     const bool o_sen = h->flip_sen, o_rec = h->flip_rec, o_dev = h->flip_dev; const float o_ps = h->flip_p_sen, o_pr = h->flip_p_rec;
@@ -566,6 +652,7 @@ extern "C" int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, i
     if (mix != MMG_MIX_SUM && mix != MMG_MIX_PROD)
         return fail("mmg_set_sender_variant: mix = %d is not MMG_MIX_SUM or MMG_MIX_PROD (-sender_mix mou needs a 4H binary layer, another parameter layout)", mix);
     const int want = (mix == MMG_MIX_PROD ? SV_PROD : 0) | (ignore_code ? SV_IGNORE_CODE : 0) | (ignore_receiver ? SV_IGNORE_REC : 0);
+    if (want && refuse_attn(h, "mmg_set_sender_variant")) return -1;
     if (want && (h->flip_sen || h->flip_rec))
         return fail("mmg_set_sender_variant: the handle has message flips (mmg_set_message_flipout); flips and a variant do not combine");
     const int old_var = h->sender_var;
@@ -645,6 +732,13 @@ static int launch_bwd_mc(mmg_handle* h, hipStream_t st, const int64_t* d_target,
 // FAM_FAST (sample roles + statistics / class / dbar / deferred baseline roles) and the per-sample k_bwd_conv of every other shape
 static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_target, bool with_stats) {
     const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
+    if (s.attn) {
+        // the reverse pass, then the two reductions that are no GEMM over (step, sample) rows: dE | Py2 per class, dDD per word
+        { Scope sc(h, st, "k_bwd_conv"); hipLaunchKernelGGL(k_bwd_conv_attn, dim3(d.B), dim3(MMG_BLOCK), s.bwd_smem, st, h->dm, h->P, h->tp, d_target, h->at); }
+        { Scope sc(h, st, "k_attn_dE"); hipLaunchKernelGGL(k_attn_dE, dim3(d.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, h->at); }
+        { Scope sc(h, st, "k_attn_dDD"); hipLaunchKernelGGL(k_attn_dDD, dim3(h->n_words), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, h->at); }
+        return launch_check("k_bwd_conv_attn");
+    }
     Scope sc(h, st, p.bwd_name);
     if (s.family == FAM_FAST) {      // (a 512-thread variant of this kernel measured slower: 31.8 vs 28.8 us -- it is not issue-bound)
         const int n_stats = with_stats ? p.n_stats : 0, n_bas = (with_stats && h->fwd.bas_deferred) ? p.n_bas : 0, n_class = with_stats ? d.D : p.n_class;
@@ -796,6 +890,7 @@ extern "C" int mmg_dp_set_allreduce(mmg_handle* h, void* nccl_all_reduce, void* 
 }
 static int dp_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                         const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, int full_tape, int reduce, void* stream) {
+    if (refuse_attn(h, "the data-parallel step")) return -1;
     hipStream_t st = (hipStream_t)stream;
     mmg_allreduce_fn ar = (mmg_allreduce_fn)h->ar_fn;
     if (reduce && !ar) return fail("mmg_dp_train_step: no collective set (mmg_dp_set_allreduce)");
@@ -911,12 +1006,14 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
                                     float* d_h_w, void* stream) {
     if (!h) return fail("NULL handle");
     if (!d_z || !d_desc || !d_h_z) return fail("z / desc / h_z must not be NULL");
+    if (attn_ready(h, "mmg_receiver_forward")) return -1;
     if (t < 0 || t >= h->dm.T) return fail("t out of range");
     hipStream_t st = (hipStream_t)stream;
     const Dims& d = h->dm;
     const size_t offW = (size_t)t * d.B * d.W, offB = (size_t)t * d.B;
     HIP_OK(hipMemcpyAsync(h->tp.z + offW, d_z, sizeof(float) * d.B * d.W, hipMemcpyDeviceToDevice, st));
     if (launch_prep(h, st, d_desc, nullptr, train ? 1 : 0)) return -1;
+    if (h->sel.attn && launch_attn_prep(h, st)) return -1;
     ConvArgs ar;
     memset(&ar, 0, sizeof(ar));
     ar.desc = d_desc; ar.seed = seed; ar.train = train; ar.run_all = 1;
@@ -924,7 +1021,8 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 2; ar.h_state = d_h_z; ar.sprod_state = d_s_prob_prod; ar.sprod_first = first;
     flip_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
-    hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
+    if (h->sel.attn) hipLaunchKernelGGL(h->sel.plan.agent_attn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->at);
+    else hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(receiver)")) return -1;
     if (d_s) HIP_OK(hipMemcpyAsync(d_s, h->tp.s + offB, sizeof(float) * d.B, hipMemcpyDeviceToDevice, st));
     if (d_s_prob) HIP_OK(hipMemcpyAsync(d_s_prob, h->tp.ps + offB, sizeof(float) * d.B, hipMemcpyDeviceToDevice, st));
@@ -968,6 +1066,7 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
                                 const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
                                 void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_exchange_vjp")) return -1;
     const Dims& d = h->dm;
     if (agent < 0 || agent > 3) return fail("unknown agent %d", agent);
     if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
@@ -1007,6 +1106,7 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
 extern "C" int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float* d_x, const float* d_desc, const float* d_dy,
                                         const float* d_dz, const float* d_dw, const float* d_dps, void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_exchange_vjp_channel")) return -1;
     const Dims& d = h->dm;
     if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
     if (!d_x || !d_desc) return fail("x / desc must not be NULL");
@@ -1069,6 +1169,7 @@ static int launch_vjp_nn_rows(mmg_handle* h, hipStream_t st, int rows, const NnP
 extern "C" int mmg_vjp_input_grads(mmg_handle* h, int per_call, int n_steps, const float* d_y, float* d_ddx, float* d_ddesc,
                                    void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_vjp_input_grads")) return -1;
     const Dims& d = h->dm;
     if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
     if (per_call && d_ddesc && !d_y) return fail("y of the call must not be NULL (per_call)");
@@ -1097,6 +1198,7 @@ extern "C" int mmg_vjp_input_grads(mmg_handle* h, int per_call, int n_steps, con
 extern "C" int mmg_sender_vjp(mmg_handle* h, const float* d_x, const float* d_w, int t, const float* d_h_x, const float* d_probs,
                               const float* d_dout, const float* d_dh_x, float* d_dx, float* d_dw, void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_sender_vjp")) return -1;
     const Dims& d = h->dm;
     if (!d_x || !d_h_x) return fail("x / h_x must not be NULL");
     if (t < 0 || t >= d.T) return fail("t out of range");
@@ -1132,6 +1234,7 @@ extern "C" int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_
                                 const float* d_dw, const float* d_dps, const float* d_dh_w, const float* d_dh_new,
                                 float* d_dz, float* d_dh_prev, void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_receiver_vjp")) return -1;
     const Dims& d = h->dm;
     if (!d_z || !d_desc || !d_h_new || !d_y) return fail("z / desc / h_new / y must not be NULL");
     if (d.use_binary && d_dw && !d_w_probs) return fail("w_probs must not be NULL when d w_probs is given (binary messages)");
@@ -1161,6 +1264,7 @@ extern "C" int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_
 extern "C" int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
                                 const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream) {
     if (!h) return fail("NULL handle");
+    if (refuse_attn(h, "mmg_baseline_vjp")) return -1;
     const Dims& d = h->dm;
     if (which != MMG_AGENT_BASELINE_REC && which != MMG_AGENT_BASELINE_SEN)
         return fail("which must be MMG_AGENT_BASELINE_REC or MMG_AGENT_BASELINE_SEN");

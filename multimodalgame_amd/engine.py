@@ -11,10 +11,29 @@ from . import _lib
 _TORCH_DTYPE = {0: torch.float32, 1: torch.uint8, 2: torch.int32, 3: torch.float64}
 
 
+def check_desc_set(desc_set, lens, n_classes, wv_dim):
+    """What an attention receiver needs of (desc_set, lens): [n_words, wv_dim] word vectors and n_classes positive lengths that sum
+    to n_words (a class without a word has no softmax segment).  Raises ValueError."""
+    if desc_set is None or lens is None:
+        raise ValueError("desc_attn needs desc_set and desc_set_lens")
+    lens = [int(v) for v in lens]
+    if desc_set.dim() != 2 or desc_set.size(1) != wv_dim:
+        raise ValueError("desc_set must be [n_words, %d], got %s" % (wv_dim, tuple(desc_set.shape)))
+    if len(lens) != n_classes:
+        raise ValueError("desc_set_lens has %d entries for %d classes" % (len(lens), n_classes))
+    if any(v <= 0 for v in lens):
+        raise ValueError("desc_set_lens: every class needs at least one word (zero-length description at class %d)"
+                         % [i for i, v in enumerate(lens) if v <= 0][0])
+    if sum(lens) != desc_set.size(0):
+        raise ValueError("desc_set_lens sum to %d, desc_set has %d words" % (sum(lens), desc_set.size(0)))
+
+
 class Engine(object):
-    def __init__(self, device="cuda:0", share=None, **cfg_kwargs):
+    def __init__(self, device="cuda:0", share=None, attn_dim=0, n_words=0, **cfg_kwargs):
         """share: another Engine whose flat parameter / gradient / optimizer-state buffers this one
-        uses too (same model, different batch size or class count)."""
+        uses too (same model, different batch size or class count).
+        attn_dim > 0: a description-attention handle (include/mmg.h: mmg_attn_create) for description sets of n_words words --
+        six more receiver tensors, more tape arrays ("alpha", ...); set_desc_set() uploads a set before the first conversation."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.MmgError("no GPU visible: the exchange path runs on MI355X only (no CPU fallback)")
@@ -22,7 +41,10 @@ class Engine(object):
         self.cfg = _lib.make_config(**cfg_kwargs)
         self.cfg_kwargs = dict(cfg_kwargs)
         self.use_binary = bool(self.cfg.use_binary)
-        n = self.lib.mmg_param_count(C.byref(self.cfg))
+        self.attn_dim, self.n_words = int(attn_dim), int(n_words) if attn_dim else 0
+        attn = (self.attn_dim, self.n_words)
+        self._set_key = None
+        n = self.lib.mmg_attn_param_count(C.byref(self.cfg), *attn)
         if n < 0:
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         self.n_params = int(n)
@@ -33,18 +55,18 @@ class Engine(object):
             else:
                 self.flat_params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
                 # gradients + the library's tail quad (dependency-error flag; all-reduced WITH the gradients in DP)
-                self.flat_grads = torch.zeros(int(self.lib.mmg_grad_floats(C.byref(self.cfg))), dtype=torch.float32, device=self.device)
+                self.flat_grads = torch.zeros(int(self.lib.mmg_attn_grad_floats(C.byref(self.cfg), *attn)), dtype=torch.float32, device=self.device)
                 self.opt_state = torch.zeros(2 * self.n_params, dtype=torch.float32, device=self.device)
-            ws_bytes = int(self.lib.mmg_workspace_bytes(C.byref(self.cfg)))
+            ws_bytes = int(self.lib.mmg_attn_workspace_bytes(C.byref(self.cfg), *attn))
             self.workspace = torch.zeros(ws_bytes, dtype=torch.uint8, device=self.device)
             torch.cuda.synchronize(self.device)
-            self.handle = self.lib.mmg_create(C.byref(self.cfg), self.workspace.data_ptr(), ws_bytes,
-                                              self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
-                                              self.opt_state.data_ptr())
+            self.handle = self.lib.mmg_attn_create(C.byref(self.cfg), attn[0], attn[1], self.workspace.data_ptr(), ws_bytes,
+                                                   self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
+                                                   self.opt_state.data_ptr())
         if not self.handle:
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         # parameter views: {agent: {state_dict key: tensor view into flat_params}}
-        self.param_entries = _lib.param_table(self.cfg)
+        self.param_entries = _lib.param_table(self.cfg, *attn)
         self.params = {a: {} for a in _lib.AGENTS}
         self.grads = {a: {} for a in _lib.AGENTS}
         for e in self.param_entries:
@@ -59,7 +81,7 @@ class Engine(object):
             self.agent_range[e["agent"]] = (min(lo, e["offset"]), max(hi, e["offset"] + ((numel + 3) // 4) * 4))
         # tape views
         self.tape = {}
-        for e in _lib.tape_table(self.cfg):
+        for e in _lib.tape_table(self.cfg, *attn):
             dt = _TORCH_DTYPE[e["dtype"]]
             numel = 1
             for d in e["dims"]:
@@ -181,6 +203,24 @@ class Engine(object):
         _lib.check(self.lib.mmg_set_sender_variant(self.handle, _lib.MIX[mix], int(bool(ignore_code)), int(bool(ignore_receiver))))
         variant = (mix, bool(ignore_code), bool(ignore_receiver))
         self.sender_variant = None if variant == ("sum", False, False) else variant
+
+    def set_desc_set(self, desc_set, lens):
+        """The description set of an attention engine (include/mmg.h: mmg_set_desc_set): desc_set [n_words, V], the word vectors of
+        all classes concatenated; lens: n_classes positive lengths that sum to n_words.  Copied into the workspace (a blocking
+        call); an unchanged (tensor, lens) pair is not uploaded again."""
+        if not self.attn_dim:
+            raise _lib.MmgError("set_desc_set: not an attention engine (Engine(attn_dim=...))")
+        lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+        key = (desc_set.data_ptr(), desc_set._version, tuple(desc_set.shape), tuple(lens))
+        if key == self._set_key:
+            return
+        check_desc_set(desc_set, lens, self.cfg.n_classes, self.cfg.wv_dim)
+        if desc_set.size(0) != self.n_words:
+            raise ValueError("desc_set has %d words, the engine was created for %d" % (desc_set.size(0), self.n_words))
+        dset = desc_set.detach().to(self.device, torch.float32).contiguous()
+        arr = (C.c_int32 * len(lens))(*lens)
+        _lib.check(self.lib.mmg_set_desc_set(self.handle, self._ptr(dset, torch.float32), arr, int(dset.size(0))))
+        self._set_key = key
 
     def loss_stats(self):
         _lib.check(self.lib.mmg_loss_stats(self.handle, self._stream()))

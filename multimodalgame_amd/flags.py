@@ -251,7 +251,7 @@ def default_flags(argv=None):
 # ---------------------------------------------------------------------------------------------------------------------
 UNSUPPORTED = (
     # (flag, predicate on its value and the flags object, reference lines that read it)
-    ("desc_attn", lambda v, fl: bool(v), "model.py:344-409 (description attention)"),
+    ("desc_attn", lambda v, fl: bool(v), "model.py:344-410 (description attention; the library option: Receiver(..., desc_attn=True, desc_attn_dim=A) with Game.set_desc_set / exchange_args[\"desc_set\"])"),
     ("sender_mix", lambda v, fl: v not in (None, "sum"), "model.py:201-221 (prod / mou mixing of h_x and h_w; the library option for prod: Game(..., sender_mix=\"prod\"); mou needs a 4H binary layer)"),
     ("flipout_sen", lambda v, fl: v is not None, "model.py:233-234, 554-568 (random bit flips of the sender message; the library option: Game(..., flipout_sen=P))"),
     ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message; the library option: Game(..., flipout_rec=P))"),

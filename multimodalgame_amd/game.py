@@ -239,7 +239,13 @@ class Game(object):
     470-472) -- the sender's hidden layer is tanh(h_x * h_w) / tanh(h_x) instead of tanh(h_x + h_w), and the receiver's binary
     message is replaced by zeros after it was sampled or rounded (Engine.set_sender_variant).  They hold for every entry of every
     engine the game creates, on every rank; plain autograd works with them, channel_grad, input_grad and message flips do not.
-    Separate from `flags` as well: -sender_mix, -ignore_code and -ignore_receiver stay refused there."""
+    Separate from `flags` as well: -sender_mix, -ignore_code and -ignore_receiver stay refused there.
+    Description attention (model.py:267-271, 344-410) is read from the module: Receiver(..., desc_attn=True, desc_attn_dim=A).  The
+    receiver then attends over the words of every description: exchange() takes exchange_args["desc_set"] / ["desc_set_lens"] as
+    the reference does, Receiver.forward its desc_set / desc_set_lens arguments, and set_desc_set() states the pair for the entries
+    that have no such argument (train_step(s), eval_forward, eval_steps).  Training, evaluation and the agent-level forward run the
+    attention kernels; autograd / channel_grad / input_grad, message flips, sender variants and data-parallel training are not
+    available with it and raise.  The -desc_attn switch of `flags` stays refused."""
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
                  channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False,
@@ -279,6 +285,14 @@ class Game(object):
             raise NotImplementedError("a sender variant (sender_mix / ignore_code / ignore_receiver) with message flips: a handle "
                                       "has one or the other")
         self._refuse_variant_graph(self.channel_grad, self.input_grad)
+        self.attn_dim = int(getattr(receiver, "attn_dim", 0) or 0)       # Receiver(desc_attn=True, desc_attn_dim=A)
+        self._desc_set = None                                            # (desc_set, lens) of the next conversation (set_desc_set)
+        if self.attn_dim:
+            for name, on in (("autograd", self.autograd), ("channel_grad", self.channel_grad), ("input_grad", self.input_grad),
+                             ("message flips (flipout_sen / flipout_rec)", self.flipout),
+                             ("a sender variant (sender_mix / ignore_code / ignore_receiver)", self.sender_variant)):
+                if on:
+                    raise NotImplementedError("desc_attn with %s is not available" % name)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -310,7 +324,27 @@ class Game(object):
         """Data-parallel training (dist.DataParallel): train_step() then takes THIS rank's rows of the global minibatch --
         [rank * B / world, (rank + 1) * B / world) of the reference's batch (misc.py:257-302 order) -- and every rank ends
         each step with the parameters of the single-process step on the whole batch."""
+        if self.attn_dim and int(world) > 1:
+            raise NotImplementedError("desc_attn with world > 1 is not available: an attention receiver trains on one GPU")
         self.rank, self.world, self.group = int(rank), int(world), group
+
+    def set_desc_set(self, desc_set, desc_set_lens):
+        """The description set of an attention receiver (model.py:1081-1084; misc.desc_set_of builds it from misc.cbow's output):
+        desc_set [n_words, wv_dim], the word vectors of all classes concatenated, and desc_set_lens, one positive length per
+        class.  It holds for every later entry until the next call; exchange() and Receiver.forward call this with their own
+        arguments.  A pair that differs from the last one is uploaded to the engine that serves the call (include/mmg.h:
+        mmg_set_desc_set); engines are cached per (batch, classes, words), so changing the lengths creates no new handle."""
+        if not self.attn_dim:
+            if desc_set is None and desc_set_lens is None:
+                return
+            raise NotImplementedError("desc_set / desc_set_lens need a Receiver built with desc_attn=True")
+        from .engine import check_desc_set
+        lens = None if desc_set_lens is None else [int(v) for v in desc_set_lens]
+        check_desc_set(desc_set, lens, len(lens or ()), self.cfg["wv_dim"])
+        if desc_set.size(0) > _lib.ATTN_MAX_WORDS or len(lens) > _lib.ATTN_MAX_CLASSES:
+            raise NotImplementedError("desc_attn: at most %d words and %d classes (got %d, %d)"
+                                      % (_lib.ATTN_MAX_WORDS, _lib.ATTN_MAX_CLASSES, desc_set.size(0), len(lens)))
+        self._desc_set = (desc_set, lens)
 
     def _adopt(self, eng):
         """Move the modules' parameters into the engine's flat buffer (values preserved)."""
@@ -323,12 +357,23 @@ class Game(object):
                 p.data = view
 
     def engine_for(self, batch, n_classes=None, global_batch=None, batch_offset=0):
+        given = n_classes
         n_classes = n_classes or getattr(self, "_last_classes", None) or 1
+        attn = {}
+        if self.attn_dim:
+            if self._desc_set is None:
+                raise ValueError("desc_attn needs desc_set and desc_set_lens (exchange_args, Receiver.forward or Game.set_desc_set)")
+            if batch > _lib.ATTN_MAX_BATCH:
+                raise NotImplementedError("desc_attn: batch must be <= %d (got %d)" % (_lib.ATTN_MAX_BATCH, batch))
+            if given and given != len(self._desc_set[1]):
+                raise ValueError("desc has %d classes, desc_set_lens %d" % (given, len(self._desc_set[1])))
+            n_classes = len(self._desc_set[1])
+            attn = dict(attn_dim=self.attn_dim, n_words=int(self._desc_set[0].size(0)))
         self._last_classes = n_classes
-        key = (batch, n_classes, global_batch or batch, batch_offset)
+        key = (batch, n_classes, global_batch or batch, batch_offset) + ((attn["n_words"],) if attn else ())
         if key not in self.engines:
             eng = Engine(device=self.device, share=self.engine, batch=batch, n_classes=n_classes,
-                         global_batch=global_batch, batch_offset=batch_offset, **self.cfg)
+                         global_batch=global_batch, batch_offset=batch_offset, **attn, **self.cfg)
             if self.flipout:
                 eng.set_message_flipout(self.flipout[0], self.flipout[1], dev=self.flipout[2], eval_seed=self.seed)
             if self.sender_variant:
@@ -337,6 +382,8 @@ class Game(object):
                 self.engine = eng
                 self._adopt(eng)
             self.engines[key] = eng
+        if attn:
+            self.engines[key].set_desc_set(*self._desc_set)              # (an unchanged pair is not uploaded again)
         return self.engines[key]
 
     def train_engine_for(self, local_batch, n_classes=None):
@@ -391,6 +438,11 @@ class Game(object):
             corrupt_mask = misc.build_mask(exchange_args.get("corrupt_region"), self.cfg["w_dim"])
         if exchange_args.get("data_context") is not None:
             raise NotImplementedError("attention context is outside the accelerated hot path")
+        if self.attn_dim:
+            if autograd:
+                raise NotImplementedError("desc_attn with autograd is not available: Game.train_step trains an attention receiver")
+            if exchange_args.get("desc_set") is not None or self._desc_set is None:
+                self.set_desc_set(exchange_args.get("desc_set"), exchange_args.get("desc_set_lens"))     # model.py:765-766
         for k, m in self.modules.items():
             if m is not None and (train or k in ("sender", "receiver")):
                 m.train(train)

@@ -167,6 +167,16 @@ def cbow(descr, word_dict):
     return descr
 
 
+def desc_set_of(descr):
+    """cbow()'s output as the pair an attention receiver reads (model.py:1081-1084): desc_set [n_words, V], the 'set' rows of all
+    classes concatenated in the order of descr's keys (the order of the desc matrix, model.py:1078-1079), and desc_set_lens, the
+    number of tokens of every description -- words GloVe lacks included: their zero rows are attended over as well."""
+    keys = list(descr.keys())
+    dim = int(descr[keys[0]]["cbow"].numel())
+    desc_set = torch.cat([descr[i]["set"].view(-1, dim) for i in keys], 0)
+    return desc_set, [len(descr[i]["desc"]) for i in keys]
+
+
 # ------------------------------------------------------------------ HDF5 feed (misc.py:257-302)
 _DATASET_CACHE = {}
 
