@@ -17,7 +17,7 @@
  *                             accuracy / confusion / length / Hamming arithmetic   model.py:620-691
  *   mmg_dp_train_step[s]   <- the same block on one rank of a data-parallel job (statistics + gradient
  *                             all-reduce; couplings model.py:912-915, 947-961, 1310)
- *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (non-attention, sender_mix=sum)
+ *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (sender_mix=sum; the attention branch on a handle of mmg_vattn_create)
  *   mmg_receiver_forward   <- Receiver.forward              model.py:303-477 (the desc_attn branch on a handle of mmg_attn_create)
  *   mmg_baseline_forward   <- Baseline.forward              model.py:496-516
  *   mmg_exchange_vjp       <- loss.backward() of ONE agent's graph for any loss built from exchange()'s outputs
@@ -259,6 +259,51 @@ int     mmg_attn_tape_table(const mmg_config* cfg, int attn_dim, int n_words, mm
 mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int n_words, void* d_workspace, int64_t workspace_bytes,
                             float* d_params, float* d_grads, float* d_opt_state);
 int     mmg_set_desc_set(mmg_handle* h, const float* d_set, const int32_t* lens, int n_words);
+
+/* Visual attention, the reference's -visual_attn / -attn_extra_context (model.py:80-86, 114-142, 168-195): the SENDER attends over the
+ * N = h * w locations of a feature map with the receiver's last message as the query.  On such a handle x of every entry is the map
+ * [B, C, N] as the caller holds it -- C == feat_dim channels, the locations contiguous (the reference's x.view(B, C, N).transpose(1, 2)
+ * is a view) -- read in place, never transposed.  With A = attn_dim, X[b, i] = x[b, :, i], g [B, G] the optional context:
+ *   per conversation: HX[b, i] = attn_W_x(X[b, i]);  HG[b] = attn_W_g(g[b])                               (cached by the reference)
+ *   step 0:           alpha = 1 / N (the scores are computed and dropped)
+ *   step t >= 1:      beta[b, i] = attn_U(tanh(attn_W_w(w_{t-1}[b]) + HX[b, i] (+ HG[b])));  alpha = softmax_i beta
+ *   every step:       x_attn = sum_i alpha[b, i] X[b, i];  h_x = image_layer(x_attn) -- h_x is per STEP, and baseline_sen reads the step's
+ * The twins below take (cfg, attn_dim, n_feats, context_dim); with attn_dim == 0 each returns exactly what its plain twin returns.
+ * attn_dim > 0:
+ *   - six more sender tensors under the reference's state_dict names, BEHIND its seven and inside its contiguous range (the other
+ *     agents' tensors move up): attn_W_x.weight [A, C], attn_W_x.bias [A], attn_W_w.weight [A, W], attn_W_w.bias [A], attn_U.weight
+ *     [1, A], attn_U.bias [1]; with context_dim = G > 0 two more: attn_W_g.weight [A, G], attn_W_g.bias [A];
+ *     attn_U.bias shifts every score of a softmax alike: its gradient is EXACTLY zero here (the reference's autograd leaves rounding
+ *     noise there, which RMSprop turns into steps of the size of the learning rate) -- it stays bit-identical under every optimizer;
+ *     the three other biases add into one pre-activation and get one gradient, bit for bit;
+ *   - more workspace arrays behind the plain ones: "vattn_HX" [B, N, A], "vattn_HG" [B, A], "vattn_alpha" [T, B, N], "vattn_xa"
+ *     [T, B, C] (x_attn), "vattn_hx" [T, B, H] (the step's h_x; "hx" is not written), the reverse pass's "vattn_dq" / "vattn_dv"
+ *     [T, B, A] and "vattn_dHX" [B, N, A]; nothing of size T B N C or T B N A exists;
+ *   - supported: attn_dim 1..256, n_feats 1..256, feat_dim <= 4096, context_dim 0..4096, batch <= 512, batch * n_feats * attn_dim <= 2^25, one GPU
+ *     (global_batch == batch); anything else is an error.
+ * mmg_set_data_context states the context (DEVICE memory [B, G], or [n * B, G] for mmg_eval_steps, which advances through it as it
+ * advances through d_x -- by B * C * N floats per batch there -- and so does mmg_train_steps); it is read in place by every later forward entry, so it must stay valid;
+ * required before a conversation iff context_dim > 0.  Host state only.
+ * Kernels: k_vattn_prep (HX on the matrix cores with a K-major A operand, HG) -> k_conversation_vattn, the generic per-sample
+ * conversation compiled once more -> k_baselines over the per-step h_x -> statistics -> k_bwd_conv (it leaves dh_x of every step) ->
+ * k_vattn_bwd (per sample: dx_attn, dalpha, dbeta, the tapes dq / dv, dHX summed over the steps in order) -> k_vattn_dwx
+ * (attn_W_x.weight = dHX^T X, X channel-major) -> k_wgrad (the other tensors; image_layer from the per-step x_attn, baseline_sen from the
+ * per-step h_x) -> k_gradnorm + k_opt.  Fixed-order reductions, no float atomics.  Served: mmg_exchange_forward (train = 0 / 1, every
+ * tape mode), mmg_eval_steps, mmg_loss_stats, mmg_backward, mmg_clip_step, mmg_train_step[s], mmg_sender_forward (HX / HG are formed
+ * by the first call after mmg_vattn_reset_state and kept), mmg_receiver_forward, mmg_baseline_forward.  Not offered, each an error:
+ * mmg_set_message_flipout / mmg_set_sender_variant with anything set, description attention together with it, mmg_dp_train_step[s],
+ * mmg_exchange_vjp[_channel], mmg_vjp_input_grads and the per-call VJPs.  No entry runs the plain sender on such a handle. */
+int64_t mmg_vattn_param_count(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim);
+int64_t mmg_vattn_grad_floats(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim);
+int     mmg_vattn_param_table(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, mmg_param_entry* out, int max_entries);
+int64_t mmg_vattn_workspace_bytes(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim);
+int     mmg_vattn_tape_table(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, mmg_tape_entry* out, int max_entries);
+mmg_handle* mmg_vattn_create(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, void* d_workspace, int64_t workspace_bytes,
+                             float* d_params, float* d_grads, float* d_opt_state);
+int     mmg_set_data_context(mmg_handle* h, const float* d_context);
+/* Sender.reset_state() (model.py:99-112) for mmg_sender_forward: the next call forms HX / HG from its x, the context and the current
+ * parameters, whatever its t; later calls reuse them.  A new handle, and a handle on which a whole conversation ran, is in that state. */
+int     mmg_vattn_reset_state(mmg_handle* h);
 
 /* Dev evaluation inside the library (eval_dev's loop body, model.py:620-691): n consecutive evaluation conversations, each
  * followed on the same stream by ONE reduction launch (k_eval_reduce) that leaves what the reference computes per dev batch

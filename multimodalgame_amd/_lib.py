@@ -51,10 +51,15 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_loss_save_doubles", "mmg_loss_binary_forward", "mmg_loss_binary_vjp", "mmg_loss_bas_forward", "mmg_loss_bas_vjp",
            "mmg_rec_outp_forward", "mmg_rec_outp_vjp", "mmg_exchange_vjp_channel", "mmg_vjp_input_grads", "mmg_set_message_flipout",
            "mmg_plan_text", "mmg_plan_for", "mmg_set_sender_variant", "mmg_attn_param_count", "mmg_attn_grad_floats",
-           "mmg_attn_param_table", "mmg_attn_workspace_bytes", "mmg_attn_tape_table", "mmg_attn_create", "mmg_set_desc_set"]
+           "mmg_attn_param_table", "mmg_attn_workspace_bytes", "mmg_attn_tape_table", "mmg_attn_create", "mmg_set_desc_set",
+           "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
+           "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
+# visual attention (include/mmg.h: mmg_vattn_create): attn_dim, locations of the map, context_dim, batch, batch * locations * attn_dim
+VATTN_MAX_DIM, VATTN_MAX_FEATS, VATTN_MAX_CTX, VATTN_MAX_BATCH, VATTN_MAX_HX = 256, 256, 4096, 512, 1 << 25
+VATTN_MAX_CHANNELS = 4096      # feat_dim of the map
 
 # the caps of mmg_plan_for / the last line of mmg_plan_text (include/mmg.h: MMG_CAP_*): the CU count, then one occupancy per role kernel
 PLAN_CAPS = ("n_cu", "split", "persist", "rc_bwd", "rc_persist", "mc", "mc3", "mc3p", "game", "wgrad_opt", "wgrad")
@@ -92,6 +97,14 @@ def load():
     lib.mmg_attn_tape_table.restype = i32; lib.mmg_attn_tape_table.argtypes = [cfgp, i32, i32, C.POINTER(TapeEntry), i32]
     lib.mmg_attn_create.restype = vp; lib.mmg_attn_create.argtypes = [cfgp, i32, i32, vp, i64, fp, fp, fp]
     lib.mmg_set_desc_set.restype = i32; lib.mmg_set_desc_set.argtypes = [vp, fp, C.POINTER(C.c_int32), i32]
+    lib.mmg_vattn_param_count.restype = i64; lib.mmg_vattn_param_count.argtypes = [cfgp, i32, i32, i32]
+    lib.mmg_vattn_grad_floats.restype = i64; lib.mmg_vattn_grad_floats.argtypes = [cfgp, i32, i32, i32]
+    lib.mmg_vattn_param_table.restype = i32; lib.mmg_vattn_param_table.argtypes = [cfgp, i32, i32, i32, C.POINTER(ParamEntry), i32]
+    lib.mmg_vattn_workspace_bytes.restype = i64; lib.mmg_vattn_workspace_bytes.argtypes = [cfgp, i32, i32, i32]
+    lib.mmg_vattn_tape_table.restype = i32; lib.mmg_vattn_tape_table.argtypes = [cfgp, i32, i32, i32, C.POINTER(TapeEntry), i32]
+    lib.mmg_vattn_create.restype = vp; lib.mmg_vattn_create.argtypes = [cfgp, i32, i32, i32, vp, i64, fp, fp, fp]
+    lib.mmg_set_data_context.restype = i32; lib.mmg_set_data_context.argtypes = [vp, fp]
+    lib.mmg_vattn_reset_state.restype = i32; lib.mmg_vattn_reset_state.argtypes = [vp]
     lib.mmg_exchange_forward.restype = i32
     lib.mmg_exchange_forward.argtypes = [vp, fp, vp, fp, fp, fp, fp, u64, i32, i32, vp]
     lib.mmg_loss_stats.restype = i32; lib.mmg_loss_stats.argtypes = [vp, vp]
@@ -173,24 +186,27 @@ def make_config(batch, n_classes, feat_dim, h_dim, w_dim, rec_hidden, wv_dim, ba
     return c
 
 
-def param_table(cfg, attn_dim=0, n_words=0):
-    """The flat buffer's tensors; attn_dim > 0: of an attention handle (include/mmg.h: mmg_attn_param_table)."""
+def param_table(cfg, attn_dim=0, n_words=0, vattn=None):
+    """The flat buffer's tensors; attn_dim > 0: of an attention handle (include/mmg.h: mmg_attn_param_table); vattn = (attn_dim,
+    n_feats, context_dim): of a visual-attention handle (mmg_vattn_param_table)."""
     lib = load()
-    n = lib.mmg_attn_param_table(C.byref(cfg), attn_dim, n_words, None, 0)
+    fn, dims = (lib.mmg_vattn_param_table, tuple(vattn)) if vattn else (lib.mmg_attn_param_table, (attn_dim, n_words))
+    n = fn(C.byref(cfg), *dims, None, 0)
     if n < 0:
         raise MmgError(lib.mmg_last_error().decode())
     arr = (ParamEntry * n)()
-    check(0 if lib.mmg_attn_param_table(C.byref(cfg), attn_dim, n_words, arr, n) == n else -1)
+    check(0 if fn(C.byref(cfg), *dims, arr, n) == n else -1)
     return [dict(name=e.name.decode(), agent=AGENTS[e.agent], rows=e.rows, cols=e.cols, offset=e.offset) for e in arr]
 
 
-def tape_table(cfg, attn_dim=0, n_words=0):
+def tape_table(cfg, attn_dim=0, n_words=0, vattn=None):
     lib = load()
-    n = lib.mmg_attn_tape_table(C.byref(cfg), attn_dim, n_words, None, 0)
+    fn, dims = (lib.mmg_vattn_tape_table, tuple(vattn)) if vattn else (lib.mmg_attn_tape_table, (attn_dim, n_words))
+    n = fn(C.byref(cfg), *dims, None, 0)
     if n < 0:
         raise MmgError(lib.mmg_last_error().decode())
     arr = (TapeEntry * n)()
-    check(0 if lib.mmg_attn_tape_table(C.byref(cfg), attn_dim, n_words, arr, n) == n else -1)
+    check(0 if fn(C.byref(cfg), *dims, arr, n) == n else -1)
     return [dict(name=e.name.decode(), dtype=e.dtype, dims=[int(e.dims[i]) for i in range(e.ndim)], offset=e.offset)
             for e in arr]
 

@@ -218,24 +218,41 @@ class _BaselineCall(_CallVJP):
 
 
 class Sender(_Agent):
-    """model.py:49-238 (non-attention, sender_mix == 'sum')."""
+    """model.py:49-238 (sender_mix == 'sum').  use_attn=True (the reference's -visual_attn / -attn_dim / -attn_extra_context /
+    -attn_context_dim, model.py:80-86, 114-142, 168-191): the sender attends over the locations of a feature map -- forward() then
+    takes x [B, feat_dim, h, w] and, with attn_extra_context, the context g [B, attn_context_dim]; the module owns attn_W_x, attn_W_w,
+    attn_U (and attn_W_g) under the reference's state_dict names and in its order.  Conversations, evaluation, forward() and
+    Game.train_step(s) run the attention kernels; attn_U.bias has an exactly zero gradient and never moves."""
     agent_name = "sender"
 
     def __init__(self, feature_type, feat_dim, h_dim, w_dim, bin_dim_out, use_binary,
                  use_attn=False, attn_dim=256, attn_extra_context=False, attn_context_dim=4096):
         super().__init__()
-        if use_attn:
-            raise NotImplementedError("visual attention (-visual_attn) is outside the accelerated hot path "
-                                      "(SURVEY.md §2); use -model_type Fixed/Adaptive")
         self.feature_type, self.feat_dim, self.h_dim, self.w_dim = feature_type, feat_dim, h_dim, w_dim
-        self.bin_dim_out, self.use_binary, self.use_attn = bin_dim_out, use_binary, use_attn
-        self.attn_dim, self.attn_extra_context, self.attn_context_dim = attn_dim, attn_extra_context, attn_context_dim
+        self.bin_dim_out, self.use_binary, self.use_attn = bin_dim_out, use_binary, bool(use_attn)
+        self.attn_dim, self.attn_extra_context, self.attn_context_dim = attn_dim, bool(attn_extra_context), attn_context_dim
         self.image_layer = nn.Linear(feat_dim, h_dim)
         self.code_layer = nn.Linear(w_dim, h_dim)
         self.code_bias = nn.Parameter(torch.zeros(bin_dim_out))
         self.binary_layer = nn.Linear(h_dim, bin_dim_out)
+        if self.use_attn:                                                 # model.py:80-86
+            if not 1 <= int(attn_dim) <= _lib.VATTN_MAX_DIM:
+                raise NotImplementedError("attn_dim must be 1..%d (got %s)" % (_lib.VATTN_MAX_DIM, attn_dim))
+            if self.attn_extra_context and not 1 <= int(attn_context_dim) <= _lib.VATTN_MAX_CTX:
+                raise NotImplementedError("attn_context_dim must be 1..%d (got %s)" % (_lib.VATTN_MAX_CTX, attn_context_dim))
+            self.attn_W_x = nn.Linear(feat_dim, attn_dim)
+            self.attn_W_w = nn.Linear(w_dim, attn_dim)
+            self.attn_U = nn.Linear(attn_dim, 1)
+            if self.attn_extra_context:
+                self.attn_W_g = nn.Linear(attn_context_dim, attn_dim)
         self.h_x = None
         self.reset_parameters()
+        self.reset_state()
+
+    @property
+    def vattn(self):
+        """(attn_dim, context_dim) of an attention sender -- context_dim 0 without attn_W_g --, None of a plain one."""
+        return (int(self.attn_dim), int(self.attn_context_dim) if self.attn_extra_context else 0) if self.use_attn else None
 
     def reset_parameters(self):                                           # model.py:90-97
         for m in self.modules():
@@ -246,8 +263,32 @@ class Sender(_Agent):
 
     def reset_state(self):                                                # model.py:99-112
         self.attn_scores = []
+        self._state_gen = getattr(self, "_state_gen", 0) + 1              # (the cached attn_W_x(X) / attn_W_g(g) are stale)
+
+    def _forward_attn(self, x, w, g, t):
+        """model.py:168-195 on the attention kernels: attn_W_x(X) and attn_W_g(g) are formed by the first call after reset_state()
+        and kept, as the reference caches them -- from THAT call's x and g: a later call with another map needs reset_state()
+        first, as in the reference.  A whole conversation on the same engine in between (Game.exchange, eval_forward,
+        train_step) replaces the tables and the context; the next call here then forms its own again."""
+        game = self._bound_game(x.size(0))
+        if getattr(game, "autograd", False) and self.training and torch.is_grad_enabled():
+            raise NotImplementedError("autograd through Sender.forward with visual attention is not available (the per-call VJPs "
+                                      "do not form the attention)")
+        eng = game.vattn_engine_for(x)
+        B = x.size(0)
+        if getattr(eng, "_vattn_gen", None) != (id(self), self._state_gen):
+            eng.set_data_context(game.check_context(g, B))
+            eng.vattn_reset_state()
+            eng._vattn_gen = (id(self), self._state_gen)
+        xm = x.detach().to(eng.device, torch.float32).contiguous().view(B, x.size(1), -1)
+        msg, probs, h_x = eng.sender_forward(xm, None if t == 0 else w.contiguous(), t, self.training, seed=game.next_seed())
+        self.h_x = h_x                                                    # model.py:195 side effect
+        self.attn_scores.append(eng.tape["vattn_alpha"][t].clone())       # model.py:189
+        return msg, probs
 
     def forward(self, x, w, g, t):
+        if self.use_attn:
+            return self._forward_attn(x, w, g, t)
         game = self._bound_game(x.size(0))
         if self._graph_on(game):
             eng = game.engine_for(x.size(0))

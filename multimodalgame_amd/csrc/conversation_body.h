@@ -7,7 +7,17 @@
 //   pre[d] = y1.weight[:, V:] h + b_y1 + sum_{j in d} alpha[j] E[j]   -- the attention branch puts the description FIRST (model.py:409-410)
 //   dbar = sum_j softmax(y)[class j] alpha[j] set[j]                  -- model.py:441-449 over the weighted descriptions
 // Nothing per (sample, class, V) or per (sample, word, V) is formed: everything behind alpha is linear in the set.
-#if MMG_CONV_ATTN
+// A third inclusion, with MMG_CONV_VATTN 1, is k_conversation_vattn<NT>, the instantiation of a visual-attention handle (mmg_vattn_create;
+// model.py:114-142, 168-195): the SENDER attends over the N locations of the feature map x [B, C, N] (channel-major, read in place) with
+// the receiver's last message as the query.  `va` carries the extra parameters and what k_vattn_prep formed per conversation (HX, HG).
+// Per step, in front of the tanh site:
+//   t == 0: alpha = 1 / N;   t >= 1: q = attn_W_w(w);  beta[i] = attn_U(tanh(q + HX[i] + HG));  alpha = softmax_i beta
+//   x_attn = sum_i alpha[i] x[:, i];   h_x = image_layer(x_attn)        -- h_x is per STEP here (tape: vattn_hx), tape.hx is not read
+#if MMG_CONV_VATTN
+template <int NT>
+__global__ __launch_bounds__(NT) void k_conversation_vattn(Dims dm, Params P, Tape tp, ConvArgs ar, VattnArgs va) {
+    constexpr bool FLIP = false, VAR = false;
+#elif MMG_CONV_ATTN
 template <int NT>
 __global__ __launch_bounds__(NT) void k_conversation_attn(Dims dm, Params P, Tape tp, ConvArgs ar, AttnArgs at) {
     constexpr bool FLIP = false, VAR = false;
@@ -40,13 +50,21 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
     float* s_coef = s_alpha + pad4(at.NW);
     float* s_dhv = s_coef + pad4(at.NW);
 #endif
+#if MMG_CONV_VATTN
+    // (conv_vattn_smem_floats) the step's scores / attention weights | q + HG | x_attn
+    float* s_val = s.misc + 32;
+    float* s_vq = s_val + pad4(va.N);
+    float* s_vxa = s_vq + pad4(va.A);
+#endif
 
     const bool do_sen = ar.phases & 1, do_rec = ar.phases & 2;
     const bool binary = dm.use_binary != 0;
     const bool train = ar.train != 0;
 
     // ---- conversation state ----
+#if !MMG_CONV_VATTN
     if (do_sen) for (int i = tid; i < H; i += nt) s.hx[i] = tp.hx[(size_t)b * H + i];
+#endif
     if (do_rec) {
         for (int i = tid; i < R; i += nt)
             s.h[i] = ar.h_state ? ar.h_state[(size_t)b * R + i] : (ar.t_begin == 0 ? 0.f : tp.h[((size_t)ar.t_begin * B + b) * R + i]);
@@ -81,6 +99,62 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                 tp.c[row * W + j] = (t == 0) ? sigmoidf_(P.p[S_CODE_BIAS][j]) : cv;
             }
             __syncthreads();
+#if MMG_CONV_VATTN
+            {
+                const int A = va.A, N = va.N, C = dm.F;
+                const float* xb = ar.x + (size_t)b * C * N;                // x[b, c, i]: locations contiguous (model.py:171-172 transposes a VIEW)
+                if (t == 0) {
+                    for (int i = tid; i < N; i += nt) s_val[i] = va.inv_n;  // model.py:177-180 (attention_func's scores are computed and dropped)
+                } else {
+                    gemv_rows<GU>(va.P.p[VA_WW_W], W, A, W, s.c, [&](int n, float acc) { s_vq[n] = acc; });
+                    __syncthreads();
+                    {
+                        const float* bw = va.P.p[VA_WW_B];
+                        const float* hg = va.tp.vattn_HG + (size_t)b * A;
+                        for (int a = tid; a < A; a += nt) s_vq[a] += bw[a];
+                        __syncthreads();
+                        // beta[i] = attn_U(tanh((q + HX[i]) + HG)) (model.py:136-140): 16 lanes per location
+                        const float* ua = va.P.p[VA_U_W];
+                        const float cu = va.P.p[VA_U_B][0];
+                        const bool ctx = va.G > 0;
+                        const int grp = tid >> 4, gl = tid & 15, ngrp = nt >> 4;
+                        for (int i0 = 0; i0 < N; i0 += ngrp) {              // (uniform trip count: every lane takes part in the DPP sum)
+                            const int i = min(i0 + grp, N - 1);
+                            const float* hxr = va.tp.vattn_HX + ((size_t)b * N + i) * A;
+                            float acc = 0.f;
+                            for (int a = gl; a < A; a += 16) {
+                                float pre = s_vq[a] + hxr[a];
+                                if (ctx) pre += hg[a];
+                                acc = fmaf(ua[a], tanhf(pre), acc);
+                            }
+                            acc = dpp_group_sum<16>(acc);
+                            if (gl == 0 && i0 + grp < N) s_val[i] = acc + cu;
+                        }
+                    }
+                    __syncthreads();
+                    float mx = -3.4e38f;                                    // softmax over the locations (model.py:182-183)
+                    for (int i = tid; i < N; i += nt) mx = fmaxf(mx, s_val[i]);
+                    mx = block_max(mx, s.misc + 8);
+                    float se = 0.f;
+                    for (int i = tid; i < N; i += nt) { const float e = expf(s_val[i] - mx); s_val[i] = e; se += e; }
+                    se = block_sum(se, s.misc + 16);
+                    const float inv = 1.f / se;
+                    for (int i = tid; i < N; i += nt) s_val[i] *= inv;
+                }
+                __syncthreads();
+                for (int i = tid; i < N; i += nt) va.tp.vattn_alpha[row * N + i] = s_val[i];
+                // x_attn[c] = sum_i alpha[i] x[c, i] (model.py:186): a row of x per channel
+                gemv_rows<GU>(xb, N, C, N, s_val, [&](int n, float acc) { s_vxa[n] = acc; va.tp.vattn_xa[row * C + n] = acc; });
+                __syncthreads();
+                gemv_rows<GU>(P.p[S_IMG_W], C, H, C, s_vxa, [&](int n, float acc) { s.hx[n] = acc; });     // model.py:195
+                __syncthreads();
+                {
+                    const float* bi = P.p[S_IMG_B];
+                    for (int i = tid; i < H; i += nt) { const float v = s.hx[i] + bi[i]; s.hx[i] = v; va.tp.vattn_hx[row * H + i] = v; }
+                }
+                __syncthreads();
+            }
+#endif
             const bool no_code = VAR && (ar.sender_var & SV_IGNORE_CODE);     // model.py:208-210: h_w is not used (the reference computes and drops it)
             if (t > 0 && !no_code) {
                 // (epilogues only park the sums in LDS: a bias / uniform load inside them would be one dependent

@@ -122,6 +122,21 @@ static int build_jobs(mmg_handle* h, CodeBiasJob code_bias, bool small_split) {
         jb.col(tp.h + (size_t)B * R, R, TB, R, G.p[R_S_W], nullptr).wrow = tp.dls;        // s.weight = dls^T . h_after
         jb.col(tp.dls, 1, TB, 1, G.p[R_S_B], nullptr);
         // ---- sender ----
+        if (h->vd.A) {
+            // visual attention: h_x is per step -- image_layer's input is the step's x_attn, its delta the step's dpre (at t == 0 too, where
+            // x_attn is the mean over the locations); the attention tensors from the (step, sample) tapes of k_vattn_bwd.  attn_W_x.weight has
+            // no job (k_vattn_dwx: its operand is channel-major), attn_U.bias none at all: its gradient is exactly zero, the buffer keeps
+            // mmg_vattn_create's zero.  The three biases add into one pre-activation: the same column sums, three times the same reduction
+            const VattnTape& vtp = h->va.tp; const VattnParams& VG = h->VG;
+            const int A = h->vd.A, Gc = h->vd.G;
+            jb.gemm(tp.dpre, H, vtp.vattn_xa, F, 0, SRC_STATIC, G.p[S_IMG_W], F, TB, H, F);
+            jb.gemm(vtp.vattn_dq, A, tp.zr, W, 0, SRC_STATIC, VG.p[VA_WW_W], W, TB, A, W);
+            if (Gc > 0) jb.gemm(vtp.vattn_dq, A, vtp.vattn_g, Gc, B, SRC_STATIC, VG.p[VA_WG_W], Gc, TB, A, Gc);
+            jb.bias(vtp.vattn_dq, A, TB, A, VG.p[VA_WX_B]);
+            jb.bias(vtp.vattn_dq, A, TB, A, VG.p[VA_WW_B]);
+            if (Gc > 0) jb.bias(vtp.vattn_dq, A, TB, A, VG.p[VA_WG_B]);
+            jb.bias(vtp.vattn_dv, A, TB, A, VG.p[VA_U_W]);
+        } else
         jb.gemm(tp.dhx, H, nullptr, F, 0, SRC_X, G.p[S_IMG_W], F, B, H, F);               // image_layer (sum over steps first)
         jb.col(tp.dhx, H, B, H, G.p[S_IMG_B], nullptr);
         jb.gemm(tp.dpre, H, tp.c, W, 0, SRC_STATIC, G.p[S_CODE_W], W, TB, H, W);          // code_layer
@@ -149,7 +164,8 @@ static int build_jobs(mmg_handle* h, CodeBiasJob code_bias, bool small_split) {
         jb.col(tp.hid_r, K, TB, K, G.p[BR_L2_W], nullptr).wrow = tp.dbr;
         jb.col(tp.dbr, 1, TB, 1, G.p[BR_L2_B], nullptr);
         // ---- baseline_sen: input [h_x || z_r] ----
-        jb.gemm_virt(tp.dbs, tp.hid_s, P.p[BS_L2_W], tp.hx, H, B, G.p[BS_L1_W], H + W, TB, K, H);
+        if (h->vd.A) jb.gemm_virt(tp.dbs, tp.hid_s, P.p[BS_L2_W], h->va.tp.vattn_hx, H, 0, G.p[BS_L1_W], H + W, TB, K, H);   // (the step's h_x)
+        else jb.gemm_virt(tp.dbs, tp.hid_s, P.p[BS_L2_W], tp.hx, H, B, G.p[BS_L1_W], H + W, TB, K, H);
         jb.gemm_virt(tp.dbs, tp.hid_s, P.p[BS_L2_W], tp.zr, W, 0, G.p[BS_L1_W] + H, H + W, TB, K, W);
         ColJob& s1 = jb.col(tp.hid_s, K, TB, K, G.p[BS_L1_B], nullptr);
         s1.vbeta = tp.dbs; s1.vw2 = P.p[BS_L2_W];

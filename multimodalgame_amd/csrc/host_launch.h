@@ -45,6 +45,7 @@ struct LaunchPlan {
     decltype(&k_conversation_fast3<256, 32, 64, 100, false>) fast_fn = nullptr;
     decltype(&k_conversation<256>) conv_fn = nullptr, agent_fn = nullptr;   // whole conversation / the agent-level entries' step window (k_conversation<256>)
     decltype(&k_conversation_attn<256>) conv_attn_fn = nullptr, agent_attn_fn = nullptr;   // ... of an attention handle (the receiver's entries; the sender's run agent_fn)
+    decltype(&k_conversation_vattn<256>) conv_vattn_fn = nullptr, agent_vattn_fn = nullptr;   // ... of a visual-attention handle (the sender's entries; the receiver's run agent_fn)
     int fast_smem = 0;                          // dynamic LDS of fast_fn
     const char *conv_name = "k_conversation", *bwd_name = "k_bwd_conv";
     bool bas_defer_ok = false, bas_pending_ok = false;   // roles of the backward launch (fused step) / of k_bas_stats (phased step)
@@ -70,6 +71,7 @@ struct LaunchPlan {
 // timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant when the routing changes).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
+    int vattn_bwd_smem = 0;      // dynamic LDS of k_vattn_bwd (a visual-attention handle)
     bool sw_merge_bas = false;   // (= merge_roles) the baselines' forward pass rides in the backward / statistics launch; off: its own launch
     bool sw_merge_prep = false;  // k_prep's blocks as roles of k_conversation_fast3's launch (MMG_NO_MERGE_PREP=1: a launch of their own)
     bool game_ok = false;        // fused step of the small Adaptive agents: conversation + statistics + baselines + backward in ONE launch (kernels_game.h); MMG_NO_GAME=1: off
@@ -79,6 +81,7 @@ struct Selection {
     bool wgrad_opt_ok = false;   // the clip + optimizer step can run inside k_wgrad's launch (k_wgrad<true>: every block co-resident, no row splits); MMG_NO_WGRAD_OPT=1: off
     bool flip = false;           // message flips are set on a binary handle (mmg_set_message_flipout): k_conversation_fast3<FLIP> / k_conversation<FLIP> serve it, nothing else
     bool attn = false;           // an attention handle (mmg_attn_create): the generic per-sample family with k_conversation_attn / k_bwd_conv_attn serves it, nothing else
+    bool vattn = false;          // a visual-attention handle (mmg_vattn_create): the generic per-sample family with k_conversation_vattn serves it, nothing else
     int variant = 0;             // the sender variant in effect (mmg_set_sender_variant; SV_* bits, SV_IGNORE_REC on a binary handle only): != 0: the generic
                                  // per-sample family with k_conversation<NT, false, VAR> / k_bwd_conv<MANY, VAR> serves the handle, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
@@ -175,6 +178,15 @@ struct mmg_handle {
     AttnArgs at = {};
     AttnParams AG = {};
     bool set_ready = false;
+    // mmg_vattn_create: the sender's attn_dim (0: a plain handle), the locations of the map, context_dim; `va` is what the VATTN
+    // instantiations get on top of the plain kernels' arguments; d_ctx: the data context of the next conversation (mmg_set_data_context)
+    VattnDims vd = VattnDims();
+    VattnArgs va = {};
+    const float* d_ctx = nullptr;
+    VattnParams VG = {};         // the visual-attention tensors' gradients
+    const float* bwd_x = nullptr;     // x of the backward call in flight (the attention's reverse pass reads the map)
+    const float* ctx_cur = nullptr;   // the context rows the last forward entry read (the backward pass reads the same)
+    bool vattn_stale = true;     // mmg_sender_forward forms HX / HG before its launch (mmg_vattn_reset_state; a whole conversation ran)
     WgHead vjp_hd[8] = {};       // launch geometry of k_wgrad over the VJP job tables (tape.vtables: exchange 0-3, per-call 4-7)
     ~mmg_handle() {
         for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }

@@ -130,11 +130,15 @@ static void plan_launches(mmg_handle* h) {
         p.conv_attn_fn = s.conv_threads == 512 ? k_conversation_attn<512> : k_conversation_attn<256>;
         p.agent_attn_fn = k_conversation_attn<256>;
     }
+    if (s.vattn) {                               // visual attention: the VATTN instantiations (shape_pass has cleared every other family)
+        p.conv_vattn_fn = s.conv_threads == 512 ? k_conversation_vattn<512> : k_conversation_vattn<256>;
+        p.agent_vattn_fn = k_conversation_vattn<256>;
+    }
     if (s.variant) {                             // a sender variant: the VAR instantiations (shape_pass has cleared every other conversation kernel)
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, true> : k_conversation<256, false, true>;
         p.agent_fn = k_conversation<256, false, true>;
     }
-    p.conv_name = wide ? "k_conversation_wv" : "k_conversation";
+    p.conv_name = s.vattn ? "k_conversation_vattn" : wide ? "k_conversation_wv" : "k_conversation";     // (the profiling scope says which sender ran)
     p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
     // ---- baselines (training minibatch that did not run all rows) ----
     // Fused step: the baselines' live-row pass (k_baselines3's body) as workgroup roles of the backward launch, beside the sample
@@ -237,8 +241,11 @@ static Switches read_switches() {
 // settle alone.  A capability that also needs a co-residency budget (tile_split, tile_persist, mc_ok) leaves here as a CANDIDATE: its
 // preconditions hold and s.ask names the occupancy it waits for; decide() confirms or clears it.
 static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool err_word, Selection& s,
-                      int attn_dim = 0, int n_words = 0) {
+                      int attn_dim = 0, int n_words = 0, VattnDims vd = VattnDims()) {
     s = Selection();
+    // visual attention: the generic per-sample family with the sender's VATTN instantiation; every other family is cleared below
+    s.vattn = vd.A > 0;
+    if (s.vattn && (flips || variant || attn_dim > 0)) return fail("visual attention with message flips, a sender variant or description attention");
     // description attention: the generic per-sample family in its ATTN instantiations; every other family is cleared below (use_fast, tile_ok)
     s.attn = attn_dim > 0;
     if (s.attn && (flips || variant)) return fail("desc_attn with message flips or a sender variant");
@@ -248,7 +255,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // family with the one-launch step, the many-class kernels, the sample tiles and the wide receiver do not, so all of them are cleared here
     s.variant = variant & (d.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
     if (s.variant && s.flip) return fail("message flips and a sender variant on one handle");
-    s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.attn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
+    s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.attn && !s.vattn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
     s.sw_merge_prep = !w[SW_NO_MERGE_PREP] && !no_roles;
     s.sw_merge_bas = s.merge_roles;
     s.persist_ll = !w[SW_NO_PERSIST_LL] && persist_ll_shape(cfg.batch, cfg.h_dim, cfg.w_dim, cfg.rec_hidden, cfg.wv_dim, cfg.n_classes, cfg.max_exchange);
@@ -266,11 +273,16 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
         s.conv_smem_agent = conv_attn_smem_floats(d, MMG_BLOCK, attn_dim, n_words) * 4;
         s.bwd_smem = bwd_attn_smem_floats(d, attn_dim, n_words) * 4;
     }
+    if (s.vattn) {
+        s.conv_smem = conv_vattn_smem_floats(d, s.conv_threads, vd.A, vd.N) * 4;
+        s.conv_smem_agent = conv_vattn_smem_floats(d, MMG_BLOCK, vd.A, vd.N) * 4;
+        s.vattn_bwd_smem = vattn_bwd_smem_floats(d, vd.A, vd.N) * 4;
+    }
     s.prep_smem = ((d.V > d.W ? d.V : d.W) + 16) * 4;
     // hundreds of classes: 8 per class block of k_prep (weight rows in registers across them); few classes: one per block (latency)
     s.prep_cpb = (d.D >= 256 && d.R <= 64 && d.V <= 128 && !(d.V & 3) && 2 * d.R <= MMG_BLOCK) ? 2 : 1;
     if (s.prep_cpb > 1 && (int)(s.prep_cpb * (d.V + d.R) * 4) > s.prep_smem) s.prep_smem = s.prep_cpb * (d.V + d.R) * 4;
-    if (s.conv_smem > 160 * 1024 || s.bwd_smem > 160 * 1024) return fail("dimensions need more than 160 KB of LDS per sample");
+    if (s.conv_smem > 160 * 1024 || s.bwd_smem > 160 * 1024 || s.vattn_bwd_smem > 160 * 1024) return fail("dimensions need more than 160 KB of LDS per sample");
     const int tiles = sample_tiles(d.B);
     // few tiles and a large sender MLP: one step's sender products as chip-wide launches of their own
     s.tile_ext = tiles < 64 && (int64_t)d.H * d.W >= 65536;
@@ -292,7 +304,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
     //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
     // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
-    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.attn;
+    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.attn && !s.vattn;
     s.tile_force = w[SW_TILE];
     // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
     // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -395,6 +407,8 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     if (s.conv_smem > 48 * 1024 && s.variant) raise_lds(s.conv_smem, k_conversation<256, false, true>, k_conversation<512, false, true>);
     if (s.conv_smem > 48 * 1024 && s.attn) raise_lds(s.conv_smem, k_conversation_attn<256>, k_conversation_attn<512>);
     if (s.bwd_smem > 48 * 1024 && s.attn) raise_lds(s.bwd_smem, k_bwd_conv_attn);
+    if (s.conv_smem > 48 * 1024 && s.vattn) raise_lds(s.conv_smem, k_conversation_vattn<256>, k_conversation_vattn<512>);
+    if (s.vattn_bwd_smem > 48 * 1024) raise_lds(s.vattn_bwd_smem, k_vattn_bwd);
     if (s.bwd_smem > 48 * 1024) raise_lds(s.bwd_smem, k_bwd_conv<false>, k_bwd_conv<true>);
     if (s.bwd_smem > 48 * 1024 && (s.variant & SV_IGNORE_CODE)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_IGNORE_CODE>, k_bwd_conv<true, SV_IGNORE_CODE>);
     else if (s.bwd_smem > 48 * 1024 && (s.variant & SV_PROD)) raise_lds(s.bwd_smem, k_bwd_conv<false, SV_PROD>, k_bwd_conv<true, SV_PROD>);
@@ -465,6 +479,7 @@ static int decide(mmg_handle* h, const Switches& w) {
         // the optimizer inside k_wgrad: its blocks spin on the norm role of the same launch, so ALL of them must be resident together
         s.wgrad_resident = (!s.any_split && s.ask[MMG_CAP_WGRAD_OPT] && s.caps[MMG_CAP_WGRAD_OPT] > 0) ? s.caps[MMG_CAP_WGRAD_OPT] : 0;
         s.wgrad_opt_ok = s.wgrad_resident > 0 && h->jt.n_wblocks + 5 <= s.wgrad_resident * n_cu - 8;
+        if (s.vattn) s.wgrad_opt_ok = false;      // (attn_W_x.weight comes from k_vattn_dwx, not from a job: the norm is taken over d_grads, k_gradnorm + k_opt)
         const int nb2 = s.caps[MMG_CAP_WGRAD] > 0 ? s.caps[MMG_CAP_WGRAD] : 0;
         const int others = h->jt.n_wblocks + 1 - h->jt.gemm_tiles;
         const int slots = ((nb2 * n_cu - others) / 8) * 8;
@@ -488,7 +503,7 @@ static int decide(mmg_handle* h, const Switches& w) {
 
 static int shape_pass(mmg_handle* h, const Switches& w) {
     h->no_roles = h->no_roles || w.roles_off();
-    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words);
+    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words, h->vd);
 }
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();

@@ -1516,4 +1516,117 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_log_snapshot(Dims dm, Tape tp, co
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Visual attention (mmg_vattn_create): the reverse pass through the sender's attention, behind k_bwd_conv -- which on such a handle leaves
+// dh_x of every (step, sample) row in tape.dpre (h_x + h_w is one pre-activation; zeros on the rows a sample never took).  The sender has no
+// recurrence, so a step needs nothing of another one; a workgroup per sample still walks ITS steps in order, because dHX[b] = sum_t u[t, b]
+// is accumulated in place by the thread that owns the entry -- a fixed order, no float atomics.  Per live step t >= 1 (at t == 0 alpha is
+// the constant 1 / N: the attention tensors get nothing, image_layer does through x_attn):
+//   dx_attn = image_layer.weight^T dh_x;   dalpha[i] = x[:, i] . dx_attn;   dbeta = alpha (dalpha - sum_i alpha dalpha)
+//   th[i, a] = tanh((q[a] + HX[i, a]) + HG[a]) again, q = attn_W_w(z_r) + b;   u[i, a] = dbeta[i] attn_U[a] (1 - th^2)
+//   dq[a] = sum_i u[i, a]  -> tape vattn_dq;   dv[a] = sum_i dbeta[i] th[i, a]  -> tape vattn_dv;   dHX[i, a] += u[i, a]
+// k_wgrad's jobs read vattn_dq (attn_W_w.weight, attn_W_g.weight, the three biases -- one gradient, model.py:136) and vattn_dv
+// (attn_U.weight); attn_U.bias has NO job: a shift of every score of a softmax, its gradient is exactly zero.  The context rows are copied
+// to vattn_g, the static operand of attn_W_g.weight's job.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline int vattn_bwd_smem_floats(const Dims& d, int A, int N) {
+    auto p4 = [](int n) { return (n + 3) & ~3; };
+    return p4(d.F) + 2 * p4(N) + p4(A) + p4(d.H) + p4(d.W) + 4 * MMG_BLOCK + 32;
+}
+__global__ __launch_bounds__(MMG_BLOCK) void k_vattn_bwd(Dims dm, Params P, Tape tp, const float* __restrict__ x, VattnArgs va) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int B = dm.B, H = dm.H, W = dm.W, T = dm.T, C = dm.F, A = va.A, N = va.N, G = va.G;
+    auto p4 = [](int n) { return (n + 3) & ~3; };
+    float* p = smem;
+    float* s_dxa = p; p += p4(C);   float* s_dal = p; p += p4(N);   float* s_al = p; p += p4(N);
+    float* s_q = p; p += p4(A);     float* s_dhx = p; p += p4(H);   float* s_zr = p; p += p4(W);
+    float* s_red = p; p += 4 * MMG_BLOCK;
+    float* s_misc = p;
+    const int tstar = tp.tstar[b];
+    const float* xb = x + (size_t)b * C * N;
+    float* dHX = va.tp.vattn_dHX + (size_t)b * N * A;
+    const float* HX = va.tp.vattn_HX + (size_t)b * N * A;
+    const float* hg = va.tp.vattn_HG + (size_t)b * A;
+    if (G > 0) for (int g = tid; g < G; g += nt) va.tp.vattn_g[(size_t)b * G + g] = va.ctx[(size_t)b * G + g];
+    bool first = true;                                             // dHX[b] not written yet (uniform)
+    for (int t = 0; t < T; ++t) {
+        const size_t row = (size_t)t * B + b;
+        if (t == 0 || t > tstar) {
+            for (int a = tid; a < A; a += nt) { va.tp.vattn_dq[row * A + a] = 0.f; va.tp.vattn_dv[row * A + a] = 0.f; }
+            continue;
+        }
+        for (int i = tid; i < H; i += nt) s_dhx[i] = tp.dpre[row * H + i];
+        for (int j = tid; j < W; j += nt) s_zr[j] = tp.zr[row * W + j];
+        for (int i = tid; i < N; i += nt) s_al[i] = va.tp.vattn_alpha[row * N + i];
+        __syncthreads();
+        gemv_rows<4>(va.P.p[VA_WW_W], W, A, W, s_zr, [&](int n, float acc) { s_q[n] = acc; });
+        gemv_t<8>(P.p[S_IMG_W], C, H, C, s_dhx, s_dxa, s_red, false);              // dx_attn = W_i^T dh_x
+        {
+            const float* bw = va.P.p[VA_WW_B];
+            for (int a = tid; a < A; a += nt) s_q[a] += bw[a];
+        }
+        gemv_t<8>(xb, N, C, N, s_dxa, s_dal, s_red, false);                        // dalpha[i] = sum_c x[c, i] dx_attn[c]
+        float sm = 0.f;
+        for (int i = tid; i < N; i += nt) sm = fmaf(s_al[i], s_dal[i], sm);
+        sm = block_sum(sm, s_misc);
+        for (int i = tid; i < N; i += nt) s_dal[i] = s_al[i] * (s_dal[i] - sm);    // dbeta
+        __syncthreads();
+        {
+            const float* ua = va.P.p[VA_U_W];
+            for (int a = tid; a < A; a += nt) {                                    // a thread per unit, the locations in order
+                const float qa = s_q[a], uu = ua[a], hga = G > 0 ? hg[a] : 0.f;
+                float dq = 0.f, dv = 0.f;
+                for (int i = 0; i < N; ++i) {
+                    float pre = qa + HX[(size_t)i * A + a];
+                    if (G > 0) pre += hga;
+                    const float th = tanhf(pre), db = s_dal[i];
+                    const float u = db * uu * (1.f - th * th);
+                    dq += u; dv = fmaf(db, th, dv);
+                    dHX[(size_t)i * A + a] = first ? u : dHX[(size_t)i * A + a] + u;
+                }
+                va.tp.vattn_dq[row * A + a] = dq; va.tp.vattn_dv[row * A + a] = dv;
+            }
+        }
+        first = false;
+        __syncthreads();
+    }
+    if (first) for (int k = tid; k < N * A; k += nt) dHX[k] = 0.f;
+}
+
+// attn_W_x.weight's gradient [A, C] = dHX^T . X over the B * N rows (b, i), X[(b, i), c] = x[b, c, i] in the map's own channel-major
+// layout -- which no job of k_wgrad addresses, hence a kernel of its own: one workgroup per 16 x 16 tile of the output, fp32 MFMA 16x16x4,
+// its 4 waves split the rows and meet in LDS in wave order.
+__global__ __launch_bounds__(MMG_BLOCK) void k_vattn_dwx(Dims dm, const float* __restrict__ x, VattnArgs va, float* __restrict__ out) {
+    __shared__ float s_acc[4][16][17];
+    const int A = va.A, N = va.N, C = dm.F, M = dm.B * N;
+    const int tiles_n = (C + 15) >> 4;
+    const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int a = tm * 16 + i, c = tn * 16 + i;
+    const bool av = a < A, cv = c < C;
+    const float* dHX = va.tp.vattn_dHX;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int ksteps = (M + 3) >> 2;
+    const int per = (ksteps + 3) >> 2;
+    const int s0 = wave * per, s1 = min(ksteps, s0 + per);
+    for (int st = s0; st < s1; ++st) {
+        const int k = st * 4 + q;
+        const bool kv = k < M;
+        const int kb = (kv ? k : 0) / N, ki = (kv ? k : 0) - kb * N;
+        const float fa = (av && kv) ? dHX[(size_t)k * A + a] : 0.f;
+        const float fb = (cv && kv) ? x[((size_t)kb * C + c) * N + ki] : 0.f;
+        acc = mfma16(fa, fb, acc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s_acc[wave][q * 4 + r][i] = acc[r];
+    __syncthreads();
+    {
+        const int r = threadIdx.x >> 4, cidx = threadIdx.x & 15;
+        const int ao = tm * 16 + r, co = tn * 16 + cidx;
+        if (ao < A && co < C) out[(size_t)ao * C + co] = s_acc[0][r][cidx] + s_acc[1][r][cidx] + s_acc[2][r][cidx] + s_acc[3][r][cidx];
+    }
+}
+
 }  // namespace mmg

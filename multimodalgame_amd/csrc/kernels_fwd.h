@@ -457,6 +457,94 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_attn_prep(Dims dm, Params P, Attn
     else gemm_nt_tile(tile - n_dd - n_e, at.tp.attn_set, V, P.p[R_WD_W], V, nullptr, at.tp.attn_G, R, NW, R, V);
 }
 
+// Visual attention (mmg_vattn_create): the sender's instantiation of the conversation, and the per-conversation tables in front of it
+__host__ __device__ inline int conv_vattn_smem_floats(const Dims& d, int nthreads, int A, int N) {
+    auto p4 = [](int n) { return (n + 3) & ~3; };
+    return conv_smem_floats(d, nthreads) + p4(N) + p4(A) + p4(d.F);
+}
+
+#define MMG_CONV_ATTN 0
+#define MMG_CONV_VATTN 1
+#include "conversation_body.h"
+#undef MMG_CONV_VATTN
+#undef MMG_CONV_ATTN
+
+// out[(b, i), n] = sum_c x[b, c, i] Wm[n, c] + bias[n] over the M = B * NF rows (b, i): x is the feature map as the caller holds it,
+// [B, C, NF] with the LOCATIONS contiguous, so the A operand of the 16x16x4 fp32 MFMA is K-major -- the 16 lanes of a k-group read 16
+// consecutive locations of one channel (one 64-byte segment), four channels per instruction, which is that instruction's own lane
+// layout and not what gemm_nt_tile addresses (K contiguous per row).  One workgroup per 16 x 16 output tile, its 4 waves split the
+// channels and combine through LDS in a fixed order.  C % 16 == 0: the weight fragment is one float4 per lane per four MFMAs.
+__device__ __forceinline__ void gemm_kmajor_tile(int tile, const float* __restrict__ x, int NF, int C, const float* __restrict__ Wm, int ldw,
+                                                 const float* __restrict__ bias, float* __restrict__ out, int ldo, int M, int N) {
+    __shared__ float s_acc[4][16][17];
+    const int tiles_n = (N + 15) >> 4;
+    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int m = tm * 16 + i, n = tn * 16 + i;
+    const bool mv = m < M, nv = n < N;
+    const int mb = (mv ? m : 0) / NF, mi = (mv ? m : 0) - mb * NF;
+    const float* xr = x + (size_t)mb * C * NF + mi;                   // + c * NF
+    const float* wr = Wm + (size_t)(nv ? n : 0) * ldw;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const bool vec = ((C & 15) == 0) && ((ldw & 3) == 0) && ((((uintptr_t)Wm) & 15) == 0);
+    if (vec) {
+        const int kchunks = C >> 4;
+        const int per = (kchunks + 3) >> 2;
+        const int c0 = wave * per, c1 = min(kchunks, c0 + per);
+        for (int cb0 = c0; cb0 < c1; cb0 += 4) {                      // 4 chunks (16 scalar + 4 float4 loads) in flight per pass
+            float a[4][4]; float4 bq[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = min(cb0 + u, c1 - 1) * 16 + q * 4;
+                const bool kv = (cb0 + u) < c1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[u][j] = (mv && kv) ? xr[(size_t)(k + j) * NF] : 0.f;
+                bq[u] = (nv && kv) ? *reinterpret_cast<const float4*>(wr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (cb0 + u < c1) {
+                    acc = mfma16(a[u][0], bq[u].x, acc); acc = mfma16(a[u][1], bq[u].y, acc);
+                    acc = mfma16(a[u][2], bq[u].z, acc); acc = mfma16(a[u][3], bq[u].w, acc);
+                }
+            }
+        }
+    } else {
+        const int ksteps = (C + 3) >> 2;
+        const int per = (ksteps + 3) >> 2;
+        const int s0 = wave * per, s1 = min(ksteps, s0 + per);
+        for (int st = s0; st < s1; ++st) {
+            const int k = st * 4 + q;
+            const float a = (mv && k < C) ? xr[(size_t)k * NF] : 0.f;
+            const float b = (nv && k < C) ? wr[k] : 0.f;
+            acc = mfma16(a, b, acc);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s_acc[wave][q * 4 + r][i] = acc[r];
+    __syncthreads();
+    {
+        const int r = threadIdx.x >> 4, cidx = threadIdx.x & 15;
+        const int mo = tm * 16 + r, no = tn * 16 + cidx;
+        if (mo < M && no < N) {
+            float v = s_acc[0][r][cidx] + s_acc[1][r][cidx] + s_acc[2][r][cidx] + s_acc[3][r][cidx];
+            v += bias ? bias[no] : 0.f;
+            out[(size_t)mo * ldo + no] = v;
+        }
+    }
+}
+
+// HX = attn_W_x(X) [B, NF, A] and, with a context, HG = attn_W_g(g) [B, A], both with their bias: formed once per forward entry from the
+// CURRENT parameters (the reference caches them per conversation, model.py:123-133).  grid = HX tiles + HG tiles.
+__host__ __device__ inline int vattn_prep_tiles(int M, int N) { return ((M + 15) / 16) * ((N + 15) / 16); }
+__global__ __launch_bounds__(MMG_BLOCK) void k_vattn_prep(Dims dm, const float* __restrict__ x, VattnArgs va) {
+    const int n_hx = vattn_prep_tiles(dm.B * va.N, va.A);
+    const int tile = blockIdx.x;
+    if (tile < n_hx) gemm_kmajor_tile(tile, x, va.N, dm.F, va.P.p[VA_WX_W], dm.F, va.P.p[VA_WX_B], va.tp.vattn_HX, va.A, dm.B * va.N, va.A);
+    else gemm_nt_tile(tile - n_hx, va.ctx, va.G, va.P.p[VA_WG_W], va.G, va.P.p[VA_WG_B], va.tp.vattn_HG, va.A, dm.B, va.A, va.G);
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_baselines: grid (ceil(rows/16), 2).  blockIdx.y == 0: baseline_rec over [z_t || h_{t+1}]
 // (model.py:842-843), == 1: baseline_sen over [h_x || z_r] (model.py:835-836) with the h_x part

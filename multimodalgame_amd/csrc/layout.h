@@ -35,6 +35,20 @@ enum AttnParamId { A_DD_W, A_DD_B, A_DH_W, A_DH_B, A_DA_W, A_DA_B, A_COUNT };
 #define MMG_ATTN_MAX_CLASSES 128
 #define MMG_ATTN_MAX_BATCH 512
 
+// Visual attention (model.py:80-86, 114-142, 168-191): the sender's extra layers.  They exist on a handle of mmg_vattn_create
+// (attn_dim > 0) only and lie BEHIND the sender's seven tensors, inside its contiguous range, in the reference's state_dict order;
+// attn_W_g only with a context (context_dim > 0: attn_extra_context).  Kept out of ParamId / Params like the receiver's.
+enum VattnParamId { VA_WX_W, VA_WX_B, VA_WW_W, VA_WW_B, VA_U_W, VA_U_B, VA_WG_W, VA_WG_B, VA_COUNT };
+#define MMG_VATTN_MAX_DIM 256      // attn_dim
+#define MMG_VATTN_MAX_FEATS 256    // locations of the feature map, h * w
+#define MMG_VATTN_MAX_CTX 4096     // attn_context_dim
+#define MMG_VATTN_MAX_CHANNELS 4096   // feat_dim of the map: x_attn and dx_attn of a sample live in LDS (the conversation, k_vattn_bwd)
+#define MMG_VATTN_MAX_BATCH 512
+#define MMG_VATTN_MAX_HX (int64_t(1) << 25)   // batch * locations * attn_dim, the entries of the cached attn_W_x(X)
+struct VattnDims { int A, N, G; };  // attn_dim (0: a plain sender), locations of the map, context_dim (0: no attn_W_g)
+
+struct AEntry { const char* n; int rows, cols; };
+
 struct ParamLayout {
     int64_t off[P_COUNT];
     int32_t rows[P_COUNT], cols[P_COUNT], agent[P_COUNT];
@@ -45,13 +59,20 @@ struct ParamLayout {
     int64_t a_off[A_COUNT];
     int32_t a_rows[A_COUNT], a_cols[A_COUNT];
     const char* a_name[A_COUNT];
+    int32_t v_n;              // visual-attention tensors: 0 (a plain sender), 6, or 8 with a context
+    int64_t v_off[VA_COUNT];
+    int32_t v_rows[VA_COUNT], v_cols[VA_COUNT];
+    const char* v_name[VA_COUNT];
 };
 
-inline ParamLayout param_layout(const mmg_config& c, int attn_dim = 0) {
+inline ParamLayout param_layout(const mmg_config& c, int attn_dim = 0, VattnDims va = VattnDims()) {
     ParamLayout L;
+    const AEntry vtab[VA_COUNT] = {{"attn_W_x.weight", va.A, c.feat_dim}, {"attn_W_x.bias", va.A, 0}, {"attn_W_w.weight", va.A, c.w_dim},
+                                   {"attn_W_w.bias", va.A, 0}, {"attn_U.weight", va.A > 0 ? 1 : 0, va.A}, {"attn_U.bias", va.A > 0 ? 1 : 0, 0},
+                                   {"attn_W_g.weight", va.G > 0 ? va.A : 0, va.G}, {"attn_W_g.bias", va.G > 0 ? va.A : 0, 0}};
+    L.v_n = va.A > 0 ? (va.G > 0 ? 8 : 6) : 0;
     const int H = c.h_dim, W = c.w_dim, R = c.rec_hidden, V = c.wv_dim, K = c.bas_hidden, F = c.feat_dim, A = attn_dim;
-    struct AE { const char* n; int rows, cols; };
-    const AE atab[A_COUNT] = {{"d_d.weight", A, V}, {"d_d.bias", A, 0}, {"d_h.weight", A, R}, {"d_h.bias", A, 0},
+    const AEntry atab[A_COUNT] = {{"d_d.weight", A, V}, {"d_d.bias", A, 0}, {"d_h.weight", A, R}, {"d_h.bias", A, 0},
                               {"d_attn.weight", A > 0 ? 1 : 0, A}, {"d_attn.bias", A > 0 ? 1 : 0, 0}};
     L.attn_dim = A;
     struct E { ParamId id; const char* n; int agent, rows, cols; };
@@ -82,6 +103,11 @@ inline ParamLayout param_layout(const mmg_config& c, int attn_dim = 0) {
                 const int64_t n = (int64_t)atab[k].rows * (atab[k].cols ? atab[k].cols : 1);
                 o += (n + 3) & ~(int64_t)3;
             }
+            if (cur_agent == 1) for (int k = 0; k < VA_COUNT; ++k) {     // the sender's range ends with the visual-attention tensors
+                L.v_off[k] = o; L.v_rows[k] = vtab[k].rows; L.v_cols[k] = vtab[k].cols; L.v_name[k] = vtab[k].n;
+                const int64_t n = (int64_t)vtab[k].rows * (vtab[k].cols ? vtab[k].cols : 1);
+                o += (n + 3) & ~(int64_t)3;
+            }
             cur_agent = e.agent; L.agent_begin[cur_agent] = o;
         }
         L.off[e.id] = o; L.rows[e.id] = e.rows; L.cols[e.id] = e.cols; L.agent[e.id] = e.agent; L.name[e.id] = e.n;
@@ -107,6 +133,14 @@ struct AttnParams { float* p[A_COUNT]; };
 inline AttnParams resolve_attn_params(const ParamLayout& L, float* base) {
     AttnParams P;
     for (int i = 0; i < A_COUNT; ++i) P.p[i] = base + L.a_off[i];
+    return P;
+}
+
+struct VattnParams { float* p[VA_COUNT]; };
+
+inline VattnParams resolve_vattn_params(const ParamLayout& L, float* base) {
+    VattnParams P;
+    for (int i = 0; i < VA_COUNT; ++i) P.p[i] = base + L.v_off[i];
     return P;
 }
 
@@ -328,6 +362,31 @@ struct AttnTape {
 // What the ATTN instantiations get on top of the plain kernels' arguments
 struct AttnArgs { int A, NW; AttnParams P; AttnTape tp; };
 
+// The workspace arrays of a visual-attention handle (mmg_vattn_create), BEHIND the plain tape.  Extra symbols: NF (locations of the map),
+// A (attn_dim), G1 (context_dim, 1 without a context).  F is the channel count C of the map.  Nothing here has T * B * NF * C or
+// T * B * NF * A entries: HX is per conversation, the scores and x_attn are formed per step inside the sample's workgroup.
+#define MMG_VATTN_TAPE_LIST(X)                                                     \
+    X(vattn_HX, float, 0, 3, B, NF, A)     /* attn_W_x(X) incl. its bias, per conversation                                     model.py:120-125 */ \
+    X(vattn_HG, float, 0, 2, B, A, 1)      /* attn_W_g(g) incl. its bias (zeros without a context)                             model.py:127-138 */ \
+    X(vattn_alpha, float, 0, 3, T, B, NF)  /* attention weights: 1 / NF at t == 0, softmax of the scores behind                model.py:177-183 */ \
+    X(vattn_xa, float, 0, 3, T, B, F)      /* x_attn = sum_i alpha[i] X[i]                                                     model.py:186 */ \
+    X(vattn_hx, float, 0, 3, T, B, H)      /* the step's h_x = image_layer(x_attn)                                             model.py:195 */ \
+    /* ---- backward (k_vattn_bwd) ---- */                                         \
+    X(vattn_g, float, 0, 2, B, G1, 1)      /* the context of the minibatch, copied: the static operand of attn_W_g.weight's job */ \
+    X(vattn_dq, float, 0, 3, T, B, A)      /* dL/d (attn_W_w(w) + b): sum_i u[i, :]  -> attn_W_w / attn_W_g weights, the three biases */ \
+    X(vattn_dv, float, 0, 3, T, B, A)      /* sum_i dbeta[i] tanh(..)[i, :]  -> attn_U.weight                                  */ \
+    X(vattn_dHX, float, 0, 3, B, NF, A)    /* dL/d HX = sum_t u[t]  -> attn_W_x.weight (k_vattn_dwx)                           */
+
+struct VattnTape {
+#define X(name, ctype, code, nd, d0, d1, d2) ctype* name;
+    MMG_VATTN_TAPE_LIST(X)
+#undef X
+};
+
+// What the VATTN instantiations get on top of the plain kernels' arguments (ctx: the data context [B, G] of the call, NULL without one)
+// inv_n: 1 / N rounded once to fp32 on the host, the weight of every location at t == 0
+struct VattnArgs { int A, N, G; float inv_n; VattnParams P; VattnTape tp; const float* ctx; };
+
 // row slices per output tile of k_wgrad's (step, sample)-row jobs: with thousands of rows the few dozen output tiles of the
 // small receiver matrices would otherwise be a handful of long-running workgroups
 __host__ __device__ inline int wgrad_nsplit(int TB, long long ptotal) {
@@ -371,13 +430,14 @@ __host__ __device__ inline int dc_slices(int B) { return B >= 1024 ? 4 : 1; }
 
 struct TapeLayout {
     int n, n_plain;           // entries; of which the plain tape's (the attention arrays follow them)
-    mmg_tape_entry e[192];
+    int n_vattn;              // first entry of the visual-attention arrays (== n without them)
+    mmg_tape_entry e[208];
     int64_t total;
 };
 
 constexpr bool tape_name_is(const char* a, const char* b) { return *a == *b && (*a == 0 || tape_name_is(a + 1, b + 1)); }
 
-inline TapeLayout tape_layout(const mmg_config& c, int attn_dim = 0, int n_words = 0) {
+inline TapeLayout tape_layout(const mmg_config& c, int attn_dim = 0, int n_words = 0, VattnDims va = VattnDims()) {
     TapeLayout L;
     L.n = 0;
     const int64_t B = c.batch, D = c.n_classes, F = c.feat_dim, H = c.h_dim, W = c.w_dim, R = c.rec_hidden,
@@ -396,7 +456,7 @@ inline TapeLayout tape_layout(const mmg_config& c, int attn_dim = 0, int n_words
                   NRCT16 = rc_shape((int)B, (int)H, (int)W, (int)R, (int)V, (int)D) ? 16 * ((B + 15) / 16) : 1,
                   NRCW = rc_shape((int)B, (int)H, (int)W, (int)R, (int)V, (int)D) ? W / 16 : 1,
                   NMCB = mc_shape((int)H, (int)W, (int)R, (int)V, (int)D, (int)T) && !c.use_binary ? 16 : 0,
-                  NWP = wgrad_any_split((int)(T * B), param_layout(c, attn_dim).total) ? (int64_t)16 * (param_layout(c, attn_dim).total + 512 * 64) : 4;   /* (every job splits <= 16 ways) */
+                  NWP = wgrad_any_split((int)(T * B), param_layout(c, attn_dim, va).total) ? (int64_t)16 * (param_layout(c, attn_dim, va).total + 512 * 64) : 4;   /* (every job splits <= 16 ways) */
     (void)NPLT; (void)NPLS; (void)F; (void)V; (void)NPB; (void)NDCS; (void)NWP; (void)NS2P; (void)NTILE; (void)NHLP; (void)NZP; (void)NMC; (void)NMCB; (void)NRCB; (void)NRCJ; (void)NRCW; (void)NRCX; (void)NRCP; (void)NRCA; (void)NRCZ; (void)NRCH; (void)NRCT16;
     int64_t o = 0;
     const int64_t esz[4] = {4, 1, 4, 8};
@@ -421,9 +481,15 @@ inline TapeLayout tape_layout(const mmg_config& c, int attn_dim = 0, int n_words
         (void)A; (void)NW;
         MMG_ATTN_TAPE_LIST(MMG_TAPE_ENTRY)
     }
+    L.n_vattn = L.n;
+    if (va.A > 0) {
+        const int64_t A = va.A, NF = va.N, G1 = va.G > 0 ? va.G : 1;
+        (void)A; (void)NF; (void)G1;
+        MMG_VATTN_TAPE_LIST(MMG_TAPE_ENTRY)
+    }
 #undef MMG_TAPE_ENTRY
 #define X(name_, ctype, code, nd, d0, d1, d2) +1
-    static_assert(0 MMG_TAPE_LIST(X) MMG_ATTN_TAPE_LIST(X) <= (int)(sizeof(L.e) / sizeof(L.e[0])), "TapeLayout::e is too small for both lists");
+    static_assert(0 MMG_TAPE_LIST(X) MMG_ATTN_TAPE_LIST(X) MMG_VATTN_TAPE_LIST(X) <= (int)(sizeof(L.e) / sizeof(L.e[0])), "TapeLayout::e is too small for the three lists");
 #undef X
     L.total = o;
     return L;
@@ -441,10 +507,21 @@ inline Tape resolve_tape(const TapeLayout& L, void* base) {
 inline AttnTape resolve_attn_tape(const TapeLayout& L, void* base) {
     AttnTape t;
     memset(&t, 0, sizeof(t));
-    if (L.n == L.n_plain) return t;
+    if (L.n_vattn == L.n_plain) return t;
     int i = L.n_plain;
 #define X(name, ctype, code, nd, d0, d1, d2) t.name = (ctype*)((char*)base + L.e[i++].offset);
     MMG_ATTN_TAPE_LIST(X)
+#undef X
+    return t;
+}
+
+inline VattnTape resolve_vattn_tape(const TapeLayout& L, void* base) {
+    VattnTape t;
+    memset(&t, 0, sizeof(t));
+    if (L.n == L.n_vattn) return t;
+    int i = L.n_vattn;
+#define X(name, ctype, code, nd, d0, d1, d2) t.name = (ctype*)((char*)base + L.e[i++].offset);
+    MMG_VATTN_TAPE_LIST(X)
 #undef X
     return t;
 }

@@ -145,16 +145,39 @@ static int validate_attn(const mmg_config* c, int attn_dim, int n_words) {
     return 0;
 }
 
-extern "C" int64_t mmg_attn_param_count(const mmg_config* cfg, int attn_dim, int n_words) {
-    if (validate_attn(cfg, attn_dim, n_words)) return -1;
-    return param_layout(*cfg, attn_dim).total;
+// Visual attention (mmg_vattn_*): attn_dim == 0 is the plain handle; otherwise the supported range, an error beyond it
+static int validate_vattn(const mmg_config* c, VattnDims v) {
+    if (validate(c)) return -1;
+    if (v.A == 0) return 0;
+    if (v.A < 0 || v.A > MMG_VATTN_MAX_DIM) return fail("visual_attn: attn_dim must be 1..%d (got %d)", MMG_VATTN_MAX_DIM, v.A);
+    if (v.N < 1 || v.N > MMG_VATTN_MAX_FEATS) return fail("visual_attn: n_feats (h * w of the map) must be 1..%d (got %d)", MMG_VATTN_MAX_FEATS, v.N);
+    if (c->feat_dim > MMG_VATTN_MAX_CHANNELS)
+        return fail("visual_attn: feat_dim (the channels of the map) must be <= %d (got %d)", MMG_VATTN_MAX_CHANNELS, c->feat_dim);
+    if (v.G < 0 || v.G > MMG_VATTN_MAX_CTX) return fail("visual_attn: context_dim must be 0..%d (got %d)", MMG_VATTN_MAX_CTX, v.G);
+    if (c->batch > MMG_VATTN_MAX_BATCH) return fail("visual_attn: batch must be <= %d (got %d)", MMG_VATTN_MAX_BATCH, c->batch);
+    if ((int64_t)c->batch * v.N * v.A > MMG_VATTN_MAX_HX)
+        return fail("visual_attn: batch * n_feats * attn_dim must be <= %lld (got %lld)", (long long)MMG_VATTN_MAX_HX, (long long)c->batch * v.N * v.A);
+    if (c->global_batch > 0 && c->global_batch != c->batch) return fail("visual_attn runs on one GPU (global_batch %d != batch %d)", c->global_batch, c->batch);
+    return 0;
+}
+static int validate_any(const mmg_config* c, int attn_dim, int n_words, VattnDims v) {
+    return v.A ? validate_vattn(c, v) : validate_attn(c, attn_dim, n_words);
+}
+
+static int64_t param_count_impl(const mmg_config* cfg, int attn_dim, int n_words, VattnDims vd) {
+    if (validate_any(cfg, attn_dim, n_words, vd)) return -1;
+    return param_layout(*cfg, attn_dim, vd).total;
+}
+extern "C" int64_t mmg_attn_param_count(const mmg_config* cfg, int attn_dim, int n_words) { return param_count_impl(cfg, attn_dim, n_words, VattnDims()); }
+extern "C" int64_t mmg_vattn_param_count(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim) {
+    return param_count_impl(cfg, 0, 0, VattnDims{attn_dim, n_feats, context_dim});
 }
 extern "C" int64_t mmg_param_count(const mmg_config* cfg) { return mmg_attn_param_count(cfg, 0, 0); }
 
-extern "C" int mmg_attn_param_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_param_entry* out, int max_entries) {
-    if (validate_attn(cfg, attn_dim, n_words)) return -1;
-    ParamLayout L = param_layout(*cfg, attn_dim);
-    const int n = P_COUNT + (attn_dim > 0 ? (int)A_COUNT : 0);
+static int param_table_impl(const mmg_config* cfg, int attn_dim, int n_words, VattnDims vd, mmg_param_entry* out, int max_entries) {
+    if (validate_any(cfg, attn_dim, n_words, vd)) return -1;
+    ParamLayout L = param_layout(*cfg, attn_dim, vd);
+    const int n = P_COUNT + (attn_dim > 0 ? (int)A_COUNT : 0) + L.v_n;
     if (out) {
         if (max_entries < n) return fail("need room for %d entries", n);
         int k = 0;
@@ -167,10 +190,18 @@ extern "C" int mmg_attn_param_table(const mmg_config* cfg, int attn_dim, int n_w
         for (int i = 0; i < P_COUNT; ++i) {
             if (i == S_IMG_W && attn_dim > 0)           // the attention tensors close the receiver's range
                 for (int a = 0; a < A_COUNT; ++a) put(L.a_name[a], MMG_AGENT_RECEIVER, L.a_rows[a], L.a_cols[a], L.a_off[a]);
+            if (i == BR_L1_W)                           // the visual-attention tensors close the sender's range
+                for (int a = 0; a < L.v_n; ++a) put(L.v_name[a], MMG_AGENT_SENDER, L.v_rows[a], L.v_cols[a], L.v_off[a]);
             put(L.name[i], L.agent[i], L.rows[i], L.cols[i], L.off[i]);
         }
     }
     return n;
+}
+extern "C" int mmg_attn_param_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_param_entry* out, int max_entries) {
+    return param_table_impl(cfg, attn_dim, n_words, VattnDims(), out, max_entries);
+}
+extern "C" int mmg_vattn_param_table(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, mmg_param_entry* out, int max_entries) {
+    return param_table_impl(cfg, 0, 0, VattnDims{attn_dim, n_feats, context_dim}, out, max_entries);
 }
 extern "C" int mmg_param_table(const mmg_config* cfg, mmg_param_entry* out, int max_entries) { return mmg_attn_param_table(cfg, 0, 0, out, max_entries); }
 
@@ -178,34 +209,51 @@ extern "C" int64_t mmg_attn_grad_floats(const mmg_config* cfg, int attn_dim, int
     if (validate_attn(cfg, attn_dim, n_words)) return -1;
     return param_layout(*cfg, attn_dim).total + MMG_GRAD_TAIL;
 }
+extern "C" int64_t mmg_vattn_grad_floats(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim) {
+    const int64_t n = mmg_vattn_param_count(cfg, attn_dim, n_feats, context_dim);
+    return n < 0 ? -1 : n + MMG_GRAD_TAIL;
+}
 extern "C" int64_t mmg_grad_floats(const mmg_config* cfg) { return mmg_attn_grad_floats(cfg, 0, 0); }
 
 extern "C" int64_t mmg_attn_workspace_bytes(const mmg_config* cfg, int attn_dim, int n_words) {
     if (validate_attn(cfg, attn_dim, n_words)) return -1;
     return tape_layout(*cfg, attn_dim, n_words).total;
 }
+extern "C" int64_t mmg_vattn_workspace_bytes(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim) {
+    const VattnDims vd{attn_dim, n_feats, context_dim};
+    if (validate_vattn(cfg, vd)) return -1;
+    return tape_layout(*cfg, 0, 0, vd).total;
+}
 extern "C" int64_t mmg_workspace_bytes(const mmg_config* cfg) { return mmg_attn_workspace_bytes(cfg, 0, 0); }
 
-extern "C" int mmg_attn_tape_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_tape_entry* out, int max_entries) {
-    if (validate_attn(cfg, attn_dim, n_words)) return -1;
-    TapeLayout L = tape_layout(*cfg, attn_dim, n_words);
+static int tape_table_impl(const mmg_config* cfg, int attn_dim, int n_words, VattnDims vd, mmg_tape_entry* out, int max_entries) {
+    if (validate_any(cfg, attn_dim, n_words, vd)) return -1;
+    TapeLayout L = tape_layout(*cfg, attn_dim, n_words, vd);
     if (out) {
         if (max_entries < L.n) return fail("need room for %d entries", L.n);
         memcpy(out, L.e, sizeof(mmg_tape_entry) * L.n);
     }
     return L.n;
 }
+extern "C" int mmg_attn_tape_table(const mmg_config* cfg, int attn_dim, int n_words, mmg_tape_entry* out, int max_entries) {
+    return tape_table_impl(cfg, attn_dim, n_words, VattnDims(), out, max_entries);
+}
+extern "C" int mmg_vattn_tape_table(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, mmg_tape_entry* out, int max_entries) {
+    return tape_table_impl(cfg, 0, 0, VattnDims{attn_dim, n_feats, context_dim}, out, max_entries);
+}
 extern "C" int mmg_tape_table(const mmg_config* cfg, mmg_tape_entry* out, int max_entries) { return mmg_attn_tape_table(cfg, 0, 0, out, max_entries); }
 
 // A handle with its layouts and the addresses inside the caller's buffers (no GPU call)
-static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, float* grads, float* opt_state, int attn_dim = 0, int n_words = 0) {
+static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, float* grads, float* opt_state, int attn_dim = 0, int n_words = 0,
+                              VattnDims vd = VattnDims()) {
     mmg_handle* h = new mmg_handle();
     h->cfg = cfg;
     if (h->cfg.global_batch <= 0) h->cfg.global_batch = h->cfg.batch;
     h->dm = make_dims(h->cfg);
     h->attn_dim = attn_dim; h->n_words = attn_dim > 0 ? n_words : 0;
-    h->pl = param_layout(h->cfg, attn_dim);
-    h->tl = tape_layout(h->cfg, attn_dim, n_words);
+    h->vd = vd.A > 0 ? vd : VattnDims();
+    h->pl = param_layout(h->cfg, attn_dim, h->vd);
+    h->tl = tape_layout(h->cfg, attn_dim, n_words, h->vd);
     h->ws = ws; h->params = params; h->grads = grads; h->opt_state = opt_state;
     h->P = resolve_params(h->pl, params);
     h->G = resolve_params(h->pl, grads);
@@ -214,15 +262,19 @@ static mmg_handle* new_handle(const mmg_config& cfg, void* ws, float* params, fl
     h->at.P = resolve_attn_params(h->pl, params);
     h->AG = resolve_attn_params(h->pl, grads);
     h->at.tp = resolve_attn_tape(h->tl, ws);
+    h->va.A = h->vd.A; h->va.N = h->vd.N; h->va.G = h->vd.G; h->va.inv_n = h->vd.N > 0 ? 1.0f / (float)h->vd.N : 0.f;
+    h->va.P = resolve_vattn_params(h->pl, params);
+    h->va.tp = resolve_vattn_tape(h->tl, ws);
+    h->VG = resolve_vattn_params(h->pl, grads);
     h->d_jt = reinterpret_cast<JobTable*>(h->tp.tables);
     return h;
 }
 
-extern "C" mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int n_words, void* d_workspace, int64_t workspace_bytes,
-                                       float* d_params, float* d_grads, float* d_opt_state) {
-    if (validate_attn(cfg, attn_dim, n_words)) return nullptr;
+static mmg_handle* create_impl(const mmg_config* cfg, int attn_dim, int n_words, VattnDims vd, void* d_workspace, int64_t workspace_bytes,
+                               float* d_params, float* d_grads, float* d_opt_state) {
+    if (validate_any(cfg, attn_dim, n_words, vd)) return nullptr;
     if (!d_workspace || !d_params || !d_grads || !d_opt_state) { fail("NULL device buffer"); return nullptr; }
-    mmg_handle* h = new_handle(*cfg, d_workspace, d_params, d_grads, d_opt_state, attn_dim, n_words);
+    mmg_handle* h = new_handle(*cfg, d_workspace, d_params, d_grads, d_opt_state, attn_dim, n_words, vd);
     if (workspace_bytes < h->tl.total) { fail("workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)h->tl.total); delete h; return nullptr; }
     if (hipHostMalloc((void**)&h->h_err, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) {
         *h->h_err = 0u;
@@ -262,6 +314,32 @@ extern "C" mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int 
     return h;
 }
 
+extern "C" mmg_handle* mmg_attn_create(const mmg_config* cfg, int attn_dim, int n_words, void* d_workspace, int64_t workspace_bytes,
+                                       float* d_params, float* d_grads, float* d_opt_state) {
+    return create_impl(cfg, attn_dim, n_words, VattnDims(), d_workspace, workspace_bytes, d_params, d_grads, d_opt_state);
+}
+extern "C" mmg_handle* mmg_vattn_create(const mmg_config* cfg, int attn_dim, int n_feats, int context_dim, void* d_workspace, int64_t workspace_bytes,
+                                        float* d_params, float* d_grads, float* d_opt_state) {
+    return create_impl(cfg, 0, 0, VattnDims{attn_dim, n_feats, context_dim}, d_workspace, workspace_bytes, d_params, d_grads, d_opt_state);
+}
+
+// The data context g [B, G] of a visual-attention handle's next conversations (DEVICE memory, read in place by k_vattn_prep; the
+// multi-minibatch entries advance through it by B * G per minibatch).  Host state only.  NULL clears it.
+extern "C" int mmg_set_data_context(mmg_handle* h, const float* d_context) {
+    if (!h) return fail("NULL handle");
+    if (!h->vd.A) return fail("mmg_set_data_context: not a visual-attention handle (mmg_vattn_create with attn_dim > 0)");
+    h->d_ctx = d_context;
+    return 0;
+}
+
+// Sender.reset_state() for the agent-level entry: the next mmg_sender_forward forms HX / HG again, whatever its t.  Host state only.
+extern "C" int mmg_vattn_reset_state(mmg_handle* h) {
+    if (!h) return fail("NULL handle");
+    if (!h->vd.A) return fail("mmg_vattn_reset_state: not a visual-attention handle (mmg_vattn_create with attn_dim > 0)");
+    h->vattn_stale = true;
+    return 0;
+}
+
 extern "C" mmg_handle* mmg_create(const mmg_config* cfg, void* d_workspace, int64_t workspace_bytes,
                                   float* d_params, float* d_grads, float* d_opt_state) {
     return mmg_attn_create(cfg, 0, 0, d_workspace, workspace_bytes, d_params, d_grads, d_opt_state);
@@ -298,7 +376,22 @@ extern "C" int mmg_set_desc_set(mmg_handle* h, const float* d_set, const int32_t
 // Gates of an attention handle: what it does not offer raises (never the plain receiver instead) ...
 static int refuse_attn(const mmg_handle* h, const char* who) {
     if (h && h->attn_dim) return fail("%s is not available on a description-attention handle (desc_attn)", who);
+    if (h && h->vd.A) return fail("%s is not available on a visual-attention handle (visual_attn)", who);
     return 0;
+}
+// ... and a conversation of a sender with attn_W_g needs the context
+static int vattn_ready(const mmg_handle* h, const char* who) {
+    if (h->vd.A && h->vd.G > 0 && !h->d_ctx) return fail("%s: visual_attn with a context needs the data context first (mmg_set_data_context)", who);
+    return 0;
+}
+// x of minibatch i of a multi-minibatch entry: B * F features, times the locations of the map on a visual-attention handle
+static size_t x_stride(const mmg_handle* h) { return (size_t)h->dm.B * h->dm.F * (h->vd.A ? h->vd.N : 1); }
+static int launch_vattn_prep(mmg_handle* h, hipStream_t st, const float* d_x, const float* d_ctx) {
+    Scope sc(h, st, "k_vattn_prep");
+    VattnArgs va = h->va; va.ctx = d_ctx;
+    const int tiles = vattn_prep_tiles(h->dm.B * va.N, va.A) + (va.G > 0 ? vattn_prep_tiles(h->dm.B, va.A) : 0);
+    hipLaunchKernelGGL(k_vattn_prep, dim3(tiles), dim3(MMG_BLOCK), 0, st, h->dm, d_x, va);
+    return launch_check("k_vattn_prep");
 }
 // ... and a conversation needs the description set
 static int attn_ready(const mmg_handle* h, const char* who) {
@@ -384,6 +477,7 @@ static int launch_baselines_fused(mmg_handle* h, hipStream_t st) {
     rec.W1 = P.p[BR_L1_W]; rec.ldw = d.W + d.R; rec.col0 = 0; rec.b1 = P.p[BR_L1_B];
     rec.W2 = P.p[BR_L2_W]; rec.b2 = P.p[BR_L2_B]; rec.hid = tp.hid_r; rec.score = tp.br;
     sen.rows = rows; sen.x1 = tp.hx; sen.ld1 = d.H; sen.k1 = d.H; sen.mod1 = d.B;      // h_x is per sample, not per step
+    if (h->sel.vattn) { sen.x1 = h->va.tp.vattn_hx; sen.mod1 = 0; }                    // (visual attention: per step, model.py:832-836)
     sen.x2 = tp.zr; sen.ld2 = d.W; sen.k2 = d.W;
     sen.W1 = P.p[BS_L1_W]; sen.ldw = d.H + d.W; sen.col0 = 0; sen.b1 = P.p[BS_L1_B];
     sen.W2 = P.p[BS_L2_W]; sen.b2 = P.p[BS_L2_B]; sen.hid = tp.hid_s; sen.score = tp.bs;
@@ -499,6 +593,8 @@ static int launch_conv_sample(mmg_handle* h, hipStream_t st, ConvArgs ar, bool b
         hipLaunchKernelGGL(p.fast_fn, dim3(d.B + ar.nbase + (p.merge_prep ? ar.nprep + 1 : 0)), dim3(256), p.fast_smem, st, h->dm, h->P, h->tp, ar);
     } else if (s.attn)
         hipLaunchKernelGGL(p.conv_attn_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar, h->at);
+    else if (s.vattn)
+        hipLaunchKernelGGL(p.conv_vattn_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar, h->va);
     else
         hipLaunchKernelGGL(p.conv_fn, dim3(d.B), dim3(s.conv_threads), s.conv_smem, st, h->dm, h->P, h->tp, ar);
     return launch_check("k_conversation");
@@ -508,7 +604,7 @@ static int launch_conv_sample(mmg_handle* h, hipStream_t st, ConvArgs ar, bool b
 // left to the backward launch (fused step) or to k_bas_stats (phased step) where the plan allows, or the plan's standalone kernel
 static int launch_baselines(mmg_handle* h, hipStream_t st, bool all_rows, bool defer_bas, bool base_ready) {
     const Dims& d = h->dm; const LaunchPlan& p = h->sel.plan;
-    if (all_rows) return launch_baselines_fused(h, st);
+    if (all_rows || h->sel.vattn) return launch_baselines_fused(h, st);    // (visual attention: the live-row kernels hoist h_x over the steps)
     h->fwd.scores_in_parts = true;
     if (base_ready && defer_bas && p.bas_defer_ok) { h->fwd.bas_deferred = true; return 0; }
     if (base_ready && !defer_bas && p.bas_pending_ok) { h->fwd.bas_pending = true; return 0; }
@@ -524,13 +620,19 @@ static int launch_baselines(mmg_handle* h, hipStream_t st, bool all_rows, bool d
 
 // defer_bas (the fused step's forward): the baselines may ride in the backward launch
 static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, const float* d_u_z,
-                                 const float* d_u_s, const float* d_u_w, uint64_t seed, int train, TapeMode mode, void* stream, bool defer_bas = false) {
+                                 const float* d_u_s, const float* d_u_w, uint64_t seed, int train, TapeMode mode, void* stream, bool defer_bas = false,
+                                 int64_t mb = 0) {
     if (!d_x || !d_desc) return fail("x / desc must not be NULL");
-    if (attn_ready(h, "exchange")) return -1;
+    if (attn_ready(h, "exchange") || vattn_ready(h, "exchange")) return -1;
     hipStream_t st = (hipStream_t)stream;
     const Dims& d = h->dm; const Selection& s = h->sel; const LaunchPlan& p = s.plan;
-    if (!p.merge_prep && launch_prep(h, st, d_desc, d_x, train ? 1 : 0)) return -1;
+    // (visual attention: x is the [B, C, N] map -- no h_x tiles in k_prep, the conversation forms h_x per step; mb: the minibatch of a
+    //  multi-minibatch entry, whose rows of the context are read)
+    if (!p.merge_prep && launch_prep(h, st, d_desc, s.vattn ? nullptr : d_x, train ? 1 : 0)) return -1;
     if (s.attn && launch_attn_prep(h, st)) return -1;
+    h->ctx_cur = (s.vattn && h->vd.G > 0) ? h->d_ctx + (size_t)mb * d.B * h->vd.G : nullptr;
+    if (s.vattn && launch_vattn_prep(h, st, d_x, h->ctx_cur)) return -1;
+    h->vattn_stale = true;                         // (the tables are this conversation's: an agent-level call forms its own)
     if (h->corrupt_on && train) return fail("a message corruption mask is set: training conversations are not corrupted (mmg_set_message_corruption(h, NULL, 0) clears it)");
     // TAPE_LOG (the minibatches whose log block reads the whole tape): the CONVERSATION runs every sample through all steps, everything else
     // is the training step's -- the baselines over the live rows only, in the statistics / backward launch (the log block prints no baseline score;
@@ -586,7 +688,7 @@ extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_
     const int nsb = eval_sample_blocks(d.B);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t* tgt = d_target + (size_t)i * d.B;
-        if (exchange_forward_impl(h, d_x + (size_t)i * d.B * d.F, tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, TAPE_ALL, stream)) return -1;
+        if (exchange_forward_impl(h, d_x + (size_t)i * x_stride(h), tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, TAPE_ALL, stream, false, i)) return -1;
         Scope sc(h, st, "k_eval_reduce");
         hipLaunchKernelGGL(k_eval_reduce, dim3(nsb + 2 * d.T), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_acc,
                            d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
@@ -739,6 +841,18 @@ static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_tar
         { Scope sc(h, st, "k_attn_dDD"); hipLaunchKernelGGL(k_attn_dDD, dim3(h->n_words), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, h->at); }
         return launch_check("k_bwd_conv_attn");
     }
+    if (s.vattn) {
+        // the plain reverse pass (it leaves dh_x of every step in tape.dpre), then the attention's: k_vattn_bwd per sample, k_vattn_dwx per
+        // output tile of attn_W_x.weight.  Continuous messages train the receiver alone: nothing more
+        { Scope sc(h, st, "k_bwd_conv"); hipLaunchKernelGGL(p.bwd_conv_fn, dim3(d.B), dim3(MMG_BLOCK), s.bwd_smem, st, h->dm, h->P, h->tp, d_target); }
+        if (launch_check("k_bwd_conv")) return -1;
+        if (!d.use_binary) return 0;
+        VattnArgs va = h->va; va.ctx = h->ctx_cur;
+        const size_t smem = (size_t)s.vattn_bwd_smem;           // (sized by shape_pass, its limit raised by probe_device)
+        { Scope sc(h, st, "k_vattn_bwd"); hipLaunchKernelGGL(k_vattn_bwd, dim3(d.B), dim3(MMG_BLOCK), smem, st, h->dm, h->P, h->tp, h->bwd_x, va); }
+        { Scope sc(h, st, "k_vattn_dwx"); hipLaunchKernelGGL(k_vattn_dwx, dim3(((va.A + 15) / 16) * ((d.F + 15) / 16)), dim3(MMG_BLOCK), 0, st, h->dm, h->bwd_x, va, h->VG.p[VA_WX_W]); }
+        return launch_check("k_vattn_bwd");
+    }
     Scope sc(h, st, p.bwd_name);
     if (s.family == FAM_FAST) {      // (a 512-thread variant of this kernel measured slower: 31.8 vs 28.8 us -- it is not issue-bound)
         const int n_stats = with_stats ? p.n_stats : 0, n_bas = (with_stats && h->fwd.bas_deferred) ? p.n_bas : 0, n_class = with_stats ? d.D : p.n_class;
@@ -753,6 +867,7 @@ static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_tar
 static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, hipStream_t st, bool with_stats,
                          bool with_opt = false, bool conv_done = false) {
     const LaunchPlan& p = h->sel.plan;
+    h->bwd_x = d_x;
     if (!conv_done) {
         if (h->sel.family == FAM_TILE ? launch_bwd_tile(h, st, d_target) : mc_bwd(h) ? launch_bwd_mc(h, st, d_target, with_stats)
                                                                                      : launch_bwd_sample(h, st, d_target, with_stats)) return -1;
@@ -824,7 +939,7 @@ extern "C" int mmg_clip_step(mmg_handle* h, void* stream) {
 }
 
 static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
-                           const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, void* stream) {
+                           const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, void* stream, int64_t mb = 0) {
     if (h->sel.game_ok) {
         // the small Adaptive agents: conversation, baselines, statistics and the reverse pass in ONE launch (kernels_game.h), then
         // k_wgrad and k_opt -- three launches per minibatch
@@ -846,12 +961,13 @@ static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
         if (backward_impl(h, d_x, d_target, d_desc, st, true, h->sel.wgrad_opt_ok, true)) return -1;
         return h->sel.wgrad_opt_ok ? 0 : clip_step_impl(h, st, true, true);
     }
-    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, TAPE_MINIMAL, stream, true)) return -1;
+    if (exchange_forward_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, 1, TAPE_MINIMAL, stream, true, mb)) return -1;
     const bool merged = merge_stats(h);
     if (h->fwd.bas_deferred && !merged) return fail("internal: deferred baselines without the merged backward launch");
     if (!merged && mmg_loss_stats(h, stream)) return -1;
     if (backward_impl(h, d_x, d_target, d_desc, (hipStream_t)stream, merged, h->sel.wgrad_opt_ok)) return -1;
-    return h->sel.wgrad_opt_ok ? 0 : clip_step_impl(h, (hipStream_t)stream, true);
+    // (visual attention: one gradient tensor is no job of k_wgrad, so the norms are taken over d_grads -- the phased step's k_gradnorm + k_opt)
+    return h->sel.wgrad_opt_ok ? 0 : clip_step_impl(h, (hipStream_t)stream, !h->sel.vattn);
 }
 
 extern "C" int mmg_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
@@ -871,7 +987,7 @@ extern "C" int mmg_train_steps(mmg_handle* h, const float* d_x, const int64_t* d
     if (h->cfg.global_batch != h->cfg.batch) return fail("mmg_train_steps is single-GPU; with several ranks: mmg_dp_train_steps");
     if (!d_x || !d_target || !d_desc || n < 0) return fail("x / target / desc must not be NULL, n >= 0");
     return run_minibatches(h, n, stream, [&](int64_t i) {
-        return train_step_impl(h, d_x + (size_t)i * h->dm.B * h->dm.F, d_target + (size_t)i * h->dm.B, d_desc, nullptr, nullptr, nullptr, seed, stream);
+        return train_step_impl(h, d_x + (size_t)i * x_stride(h), d_target + (size_t)i * h->dm.B, d_desc, nullptr, nullptr, nullptr, seed, stream, i);
     });
 }
 
@@ -982,7 +1098,14 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
                            (const float*)nullptr, 1, train ? 1 : 0);
         if (launch_check("k_prep")) return -1;
     }
-    if (launch_gemm_nt(h, st, "k_gemm_nt(h_x)", d_x, d.F, h->P.p[S_IMG_W], d.F, h->P.p[S_IMG_B], h->tp.hx, d.H, d.B, d.H, d.F)) return -1;
+    // visual attention: HX / HG are formed by the first call after mmg_vattn_reset_state (or after any whole conversation on the handle)
+    // and kept for the later calls, as the reference caches them from reset_state() on (model.py:107-108, 123-133); the step's h_x
+    // comes out of the conversation kernel
+    if (h->sel.vattn) {
+        if (vattn_ready(h, "mmg_sender_forward")) return -1;
+        if (h->vattn_stale && launch_vattn_prep(h, st, d_x, h->vd.G > 0 ? h->d_ctx : nullptr)) return -1;
+        h->vattn_stale = false;
+    } else if (launch_gemm_nt(h, st, "k_gemm_nt(h_x)", d_x, d.F, h->P.p[S_IMG_W], d.F, h->P.p[S_IMG_B], h->tp.hx, d.H, d.B, d.H, d.F)) return -1;
     ConvArgs ar;
     memset(&ar, 0, sizeof(ar));
     ar.x = d_x; ar.u_z = d_u_z ? d_u_z - (size_t)t * d.B * d.W : nullptr; ar.seed = seed; ar.train = train; ar.run_all = 1;
@@ -990,12 +1113,13 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
     flip_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
     if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
-    hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
+    if (h->sel.vattn) hipLaunchKernelGGL(h->sel.plan.agent_vattn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->va);
+    else hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(sender)")) return -1;
     const size_t off = (size_t)t * d.B * d.W;
     HIP_OK(hipMemcpyAsync(d_message, h->tp.z + off, sizeof(float) * d.B * d.W, hipMemcpyDeviceToDevice, st));
     if (d_probs && d.use_binary) HIP_OK(hipMemcpyAsync(d_probs, h->tp.pz + off, sizeof(float) * d.B * d.W, hipMemcpyDeviceToDevice, st));
-    if (d_h_x) HIP_OK(hipMemcpyAsync(d_h_x, h->tp.hx, sizeof(float) * d.B * d.H, hipMemcpyDeviceToDevice, st));
+    if (d_h_x) HIP_OK(hipMemcpyAsync(d_h_x, h->sel.vattn ? h->va.tp.vattn_hx + (size_t)t * d.B * d.H : h->tp.hx, sizeof(float) * d.B * d.H, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 

@@ -29,11 +29,14 @@ def check_desc_set(desc_set, lens, n_classes, wv_dim):
 
 
 class Engine(object):
-    def __init__(self, device="cuda:0", share=None, attn_dim=0, n_words=0, **cfg_kwargs):
+    def __init__(self, device="cuda:0", share=None, attn_dim=0, n_words=0, vattn=None, **cfg_kwargs):
         """share: another Engine whose flat parameter / gradient / optimizer-state buffers this one
         uses too (same model, different batch size or class count).
         attn_dim > 0: a description-attention handle (include/mmg.h: mmg_attn_create) for description sets of n_words words --
-        six more receiver tensors, more tape arrays ("alpha", ...); set_desc_set() uploads a set before the first conversation."""
+        six more receiver tensors, more tape arrays ("alpha", ...); set_desc_set() uploads a set before the first conversation.
+        vattn = (attn_dim, n_feats, context_dim): a visual-attention handle (include/mmg.h: mmg_vattn_create) -- x of every entry is
+        the [B, C, n_feats] feature map, six (eight with a context) more sender tensors, the tape arrays "vattn_alpha", "vattn_xa",
+        "vattn_hx", ...; set_data_context() states the context before a conversation.  Not together with attn_dim."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.MmgError("no GPU visible: the exchange path runs on MI355X only (no CPU fallback)")
@@ -44,7 +47,19 @@ class Engine(object):
         self.attn_dim, self.n_words = int(attn_dim), int(n_words) if attn_dim else 0
         attn = (self.attn_dim, self.n_words)
         self._set_key = None
-        n = self.lib.mmg_attn_param_count(C.byref(self.cfg), *attn)
+        self.vattn = tuple(int(v) for v in vattn) if vattn and int(vattn[0]) else None
+        self._ctx = None
+        if self.vattn and self.attn_dim:
+            raise _lib.MmgError("visual attention together with description attention is not available")
+        lib = self.lib
+        if self.vattn:             # the (cfg, attn_dim, n_feats, context_dim) twins in place of the (cfg, attn_dim, n_words) ones
+            attn = self.vattn
+            count, grad_floats, ws_size, create = (lib.mmg_vattn_param_count, lib.mmg_vattn_grad_floats, lib.mmg_vattn_workspace_bytes,
+                                                   lib.mmg_vattn_create)
+        else:
+            count, grad_floats, ws_size, create = (lib.mmg_attn_param_count, lib.mmg_attn_grad_floats, lib.mmg_attn_workspace_bytes,
+                                                   lib.mmg_attn_create)
+        n = count(C.byref(self.cfg), *attn)
         if n < 0:
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         self.n_params = int(n)
@@ -55,18 +70,17 @@ class Engine(object):
             else:
                 self.flat_params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
                 # gradients + the library's tail quad (dependency-error flag; all-reduced WITH the gradients in DP)
-                self.flat_grads = torch.zeros(int(self.lib.mmg_attn_grad_floats(C.byref(self.cfg), *attn)), dtype=torch.float32, device=self.device)
+                self.flat_grads = torch.zeros(int(grad_floats(C.byref(self.cfg), *attn)), dtype=torch.float32, device=self.device)
                 self.opt_state = torch.zeros(2 * self.n_params, dtype=torch.float32, device=self.device)
-            ws_bytes = int(self.lib.mmg_attn_workspace_bytes(C.byref(self.cfg), *attn))
+            ws_bytes = int(ws_size(C.byref(self.cfg), *attn))
             self.workspace = torch.zeros(ws_bytes, dtype=torch.uint8, device=self.device)
             torch.cuda.synchronize(self.device)
-            self.handle = self.lib.mmg_attn_create(C.byref(self.cfg), attn[0], attn[1], self.workspace.data_ptr(), ws_bytes,
-                                                   self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
-                                                   self.opt_state.data_ptr())
+            self.handle = create(C.byref(self.cfg), *attn, self.workspace.data_ptr(), ws_bytes,
+                                 self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state.data_ptr())
         if not self.handle:
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         # parameter views: {agent: {state_dict key: tensor view into flat_params}}
-        self.param_entries = _lib.param_table(self.cfg, *attn)
+        self.param_entries = _lib.param_table(self.cfg, vattn=self.vattn) if self.vattn else _lib.param_table(self.cfg, *attn)
         self.params = {a: {} for a in _lib.AGENTS}
         self.grads = {a: {} for a in _lib.AGENTS}
         for e in self.param_entries:
@@ -81,7 +95,7 @@ class Engine(object):
             self.agent_range[e["agent"]] = (min(lo, e["offset"]), max(hi, e["offset"] + ((numel + 3) // 4) * 4))
         # tape views
         self.tape = {}
-        for e in _lib.tape_table(self.cfg, *attn):
+        for e in (_lib.tape_table(self.cfg, vattn=self.vattn) if self.vattn else _lib.tape_table(self.cfg, *attn)):
             dt = _TORCH_DTYPE[e["dtype"]]
             numel = 1
             for d in e["dims"]:
@@ -146,6 +160,7 @@ class Engine(object):
         engine may serve a training step next."""
         f32 = torch.float32
         self.generation += 1
+        self._vattn_gen = None        # (a whole conversation replaces the tables and the context an agent-level Sender.forward left)
         if corrupt_mask is not None:
             if train:
                 raise NotImplementedError("message corruption applies to evaluation conversations only (model.py:637-638)")
@@ -222,6 +237,26 @@ class Engine(object):
         _lib.check(self.lib.mmg_set_desc_set(self.handle, self._ptr(dset, torch.float32), arr, int(dset.size(0))))
         self._set_key = key
 
+    def set_data_context(self, context, n=1):
+        """The data context of a visual-attention engine's next conversations (include/mmg.h: mmg_set_data_context): [n * B, G],
+        read in place -- the engine keeps the fp32 device tensor alive.  None clears it.  Host only."""
+        if not self.vattn:
+            raise _lib.MmgError("set_data_context: not a visual-attention engine (Engine(vattn=...))")
+        if context is not None:
+            G = self.vattn[2]
+            if not G:
+                context = None                                            # (a sender without attn_W_g ignores g, model.py:127-138)
+            elif context.dim() != 2 or context.size(1) != G or context.size(0) != n * self.cfg.batch:
+                raise ValueError("data_context must be [%d, %d], got %s" % (n * self.cfg.batch, G, tuple(context.shape)))
+            else:
+                context = context.detach().to(self.device, torch.float32).contiguous()
+        self._ctx = context
+        _lib.check(self.lib.mmg_set_data_context(self.handle, self._ptr(context, torch.float32)))
+
+    def vattn_reset_state(self):
+        """Sender.reset_state() for sender_forward (include/mmg.h: mmg_vattn_reset_state): the next call forms attn_W_x(X) / attn_W_g(g)."""
+        _lib.check(self.lib.mmg_vattn_reset_state(self.handle))
+
     def loss_stats(self):
         _lib.check(self.lib.mmg_loss_stats(self.handle, self._stream()))
 
@@ -236,6 +271,7 @@ class Engine(object):
     def train_step(self, x, target, desc, u_z=None, u_s=None, u_w=None, seed=0):
         f32 = torch.float32
         self.generation += 1
+        self._vattn_gen = None
         self.bump_param_version()
         _lib.check(self.lib.mmg_train_step(
             self.handle, self._ptr(x, f32), self._ptr(target, torch.int64), self._ptr(desc, f32),
@@ -247,6 +283,7 @@ class Engine(object):
         B = self.cfg.batch
         assert x.size(0) >= n * B and target.size(0) >= n * B
         self.generation += 1
+        self._vattn_gen = None
         self.bump_param_version()
         _lib.check(self.lib.mmg_train_steps(self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n),
                                             self._ptr(desc, torch.float32), C.c_uint64(seed), self._stream()))
@@ -274,6 +311,7 @@ class Engine(object):
             batch = torch.empty(n, 1 + 2 * T, dtype=torch.int64, device=self.device)
         assert lens.numel() >= n * B and batch.numel() >= n * (1 + 2 * T)
         self.generation += 1
+        self._vattn_gen = None
         if corrupt_mask is not None:
             self.set_message_corruption(corrupt_mask)
         try:

@@ -257,7 +257,7 @@ UNSUPPORTED = (
     ("flipout_rec", lambda v, fl: v is not None, "model.py:467-470, 554-568 (random bit flips of the receiver message; the library option: Game(..., flipout_rec=P))"),
     ("ignore_receiver", lambda v, fl: bool(v), "model.py:470-472 (the receiver's message is replaced by zeros; the library option: Game(..., ignore_receiver=True))"),
     ("ignore_code", lambda v, fl: bool(v), "model.py:208-210 (sender ignores its code input; the library option: Game(..., ignore_code=True))"),
-    ("visual_attn", lambda v, fl: bool(v), "model.py:114-191 (visual attention over layer4_2)"),
+    ("visual_attn", lambda v, fl: bool(v), "model.py:114-191 (visual attention over layer4_2; the library option: Sender(..., use_attn=True, attn_dim=A, attn_extra_context=..., attn_context_dim=G) with exchange_args[\"data\"] [B, C, h, w] and exchange_args[\"data_context\"])"),
     # -bit_flip WITH a region corrupts every dev evaluation's messages (model.py:637-638, 813-820); without one the reference
     # crashes at its first dev evaluation (build_mask(None, ...), misc.py:390)
     ("bit_flip", lambda v, fl: bool(v) and not _flag(fl, "corrupt_region"),

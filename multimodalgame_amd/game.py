@@ -245,7 +245,15 @@ class Game(object):
     the reference does, Receiver.forward its desc_set / desc_set_lens arguments, and set_desc_set() states the pair for the entries
     that have no such argument (train_step(s), eval_forward, eval_steps).  Training, evaluation and the agent-level forward run the
     attention kernels; autograd / channel_grad / input_grad, message flips, sender variants and data-parallel training are not
-    available with it and raise.  The -desc_attn switch of `flags` stays refused."""
+    available with it and raise.  The -desc_attn switch of `flags` stays refused.
+    Visual attention (model.py:80-86, 114-142, 168-195) is read from the module as well: Sender(..., use_attn=True, attn_dim=A,
+    attn_extra_context=bool, attn_context_dim=G).  exchange_args["data"] is then the feature map [B, feat_dim, h, w] and
+    exchange_args["data_context"] the context [B, G] -- required iff the sender has attn_W_g, ignored otherwise, as the reference
+    ignores g; eval_forward / eval_steps take data_context=, Sender.forward its g.  Conversations (training-mode ones with both
+    baselines included), evaluation, the agent-level forward and train_step(s) (which take data_context= too) run the attention
+    kernels, and sender.attn_scores holds the per-step [B, h * w] weights after exchange().  autograd / channel_grad / input_grad,
+    message flips, sender variants, description attention together with it and world > 1 raise.  Engines are cached per (batch,
+    classes, h * w).  The -visual_attn switch of `flags` stays refused."""
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
                  channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False,
@@ -293,6 +301,14 @@ class Game(object):
                              ("a sender variant (sender_mix / ignore_code / ignore_receiver)", self.sender_variant)):
                 if on:
                     raise NotImplementedError("desc_attn with %s is not available" % name)
+        self.vattn = getattr(sender, "vattn", None)                      # Sender(use_attn=True, ...): (attn_dim, context_dim)
+        if self.vattn:
+            for name, on in (("autograd", self.autograd), ("channel_grad", self.channel_grad), ("input_grad", self.input_grad),
+                             ("message flips (flipout_sen / flipout_rec)", self.flipout),
+                             ("a sender variant (sender_mix / ignore_code / ignore_receiver)", self.sender_variant),
+                             ("description attention (Receiver(desc_attn=True))", self.attn_dim)):
+                if on:
+                    raise NotImplementedError("visual attention with %s is not available" % name)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
         self.engines = {}
@@ -326,7 +342,49 @@ class Game(object):
         each step with the parameters of the single-process step on the whole batch."""
         if self.attn_dim and int(world) > 1:
             raise NotImplementedError("desc_attn with world > 1 is not available: an attention receiver trains on one GPU")
+        if self.vattn and int(world) > 1:
+            raise NotImplementedError("visual attention with world > 1 is not available: an attention sender runs on one GPU")
         self.rank, self.world, self.group = int(rank), int(world), group
+
+    def check_map(self, data, n=1):
+        """The feature map of an attention sender: [B, feat_dim, h, w] (model.py:169; [n * B, ...]: n batches of eval_steps).
+        Returns h * w.  Raises ValueError / NotImplementedError (outside the supported range)."""
+        if data.dim() != 4:
+            raise ValueError("visual attention needs data [B, %d, h, w], got %s" % (self.cfg["feat_dim"], tuple(data.shape)))
+        if data.size(1) != self.cfg["feat_dim"]:
+            raise ValueError("visual attention: data has %d channels, the sender's feat_dim is %d" % (data.size(1), self.cfg["feat_dim"]))
+        if data.size(1) > _lib.VATTN_MAX_CHANNELS:
+            raise NotImplementedError("visual attention: at most %d channels (got %d)" % (_lib.VATTN_MAX_CHANNELS, data.size(1)))
+        B, N = data.size(0) // n, data.size(2) * data.size(3)
+        if not 1 <= N <= _lib.VATTN_MAX_FEATS or B > _lib.VATTN_MAX_BATCH or B * N * self.vattn[0] > _lib.VATTN_MAX_HX:
+            raise NotImplementedError("visual attention: h * w must be 1..%d, batch <= %d and batch * h * w * attn_dim <= %d (got "
+                                      "h * w = %d, batch %d, attn_dim %d)" % (_lib.VATTN_MAX_FEATS, _lib.VATTN_MAX_BATCH,
+                                                                              _lib.VATTN_MAX_HX, N, B, self.vattn[0]))
+        return N
+
+    def check_context(self, context, rows):
+        """The context of an attention sender: [rows, attn_context_dim], required iff it has attn_W_g; a sender without it
+        ignores what it is given (model.py:127-138) -- None is returned then."""
+        if not self.vattn[1]:
+            return None
+        if context is None:
+            raise ValueError("this sender has attn_W_g (attn_extra_context): data_context [B, %d] is required" % self.vattn[1])
+        if context.dim() != 2 or tuple(context.shape) != (rows, self.vattn[1]):
+            raise ValueError("data_context must be [%d, %d], got %s" % (rows, self.vattn[1], tuple(context.shape)))
+        return context
+
+    def vattn_engine_for(self, data, n_classes=None, n=1):
+        """The engine of an attention sender for the map `data` ([n * B, C, h, w])."""
+        N = self.check_map(data, n)
+        return self.engine_for(data.size(0) // n, n_classes, n_feats=N)
+
+    def _vattn_train_engine(self, data, desc, data_context, n=1):
+        """The training engine of an attention sender for the maps `data` ([n * B, C, h, w]) with their context stated."""
+        n_feats = self.check_map(data, n)
+        context = self.check_context(data_context, data.size(0))
+        eng = self.engine_for(data.size(0) // n, desc.size(0), n_feats=n_feats)
+        eng.set_data_context(context, n=n)
+        return eng
 
     def set_desc_set(self, desc_set, desc_set_lens):
         """The description set of an attention receiver (model.py:1081-1084; misc.desc_set_of builds it from misc.cbow's output):
@@ -356,7 +414,7 @@ class Game(object):
                 view.copy_(p.data.to(eng.device))
                 p.data = view
 
-    def engine_for(self, batch, n_classes=None, global_batch=None, batch_offset=0):
+    def engine_for(self, batch, n_classes=None, global_batch=None, batch_offset=0, n_feats=None):
         given = n_classes
         n_classes = n_classes or getattr(self, "_last_classes", None) or 1
         attn = {}
@@ -369,8 +427,15 @@ class Game(object):
                 raise ValueError("desc has %d classes, desc_set_lens %d" % (given, len(self._desc_set[1])))
             n_classes = len(self._desc_set[1])
             attn = dict(attn_dim=self.attn_dim, n_words=int(self._desc_set[0].size(0)))
+        if self.vattn:
+            n_feats = n_feats or getattr(self, "_last_feats", None)
+            if not n_feats:
+                raise ValueError("visual attention: the engine depends on h * w of the feature map (call with the 4-D data first)")
+            self._last_feats = n_feats
+            attn = dict(vattn=(self.vattn[0], int(n_feats), self.vattn[1]))
         self._last_classes = n_classes
-        key = (batch, n_classes, global_batch or batch, batch_offset) + ((attn["n_words"],) if attn else ())
+        key = ((batch, n_classes, global_batch or batch, batch_offset) + ((attn["n_words"],) if "n_words" in attn else ())
+               + ((int(n_feats),) if self.vattn else ()))
         if key not in self.engines:
             eng = Engine(device=self.device, share=self.engine, batch=batch, n_classes=n_classes,
                          global_batch=global_batch, batch_offset=batch_offset, **attn, **self.cfg)
@@ -382,7 +447,7 @@ class Game(object):
                 self.engine = eng
                 self._adopt(eng)
             self.engines[key] = eng
-        if attn:
+        if "n_words" in attn:
             self.engines[key].set_desc_set(*self._desc_set)              # (an unchanged pair is not uploaded again)
         return self.engines[key]
 
@@ -436,8 +501,14 @@ class Game(object):
             if train:
                 raise NotImplementedError("message corruption of training conversations is outside the accelerated hot path")
             corrupt_mask = misc.build_mask(exchange_args.get("corrupt_region"), self.cfg["w_dim"])
-        if exchange_args.get("data_context") is not None:
-            raise NotImplementedError("attention context is outside the accelerated hot path")
+        context = exchange_args.get("data_context")
+        if context is not None and not self.vattn:
+            raise NotImplementedError("data_context needs a Sender built with use_attn=True (visual attention)")
+        if self.vattn:
+            if autograd:
+                raise NotImplementedError("visual attention with autograd is not available")
+            n_feats = self.check_map(data)
+            context = self.check_context(context, data.size(0))
         if self.attn_dim:
             if autograd:
                 raise NotImplementedError("desc_attn with autograd is not available: Game.train_step trains an attention receiver")
@@ -447,11 +518,13 @@ class Game(object):
             if m is not None and (train or k in ("sender", "receiver")):
                 m.train(train)
         B = data.size(0)
-        eng = self.engine_for(B, desc.size(0))
+        eng = self.engine_for(B, desc.size(0), **(dict(n_feats=n_feats) if self.vattn else {}))
         dev = eng.device
-        data = data.detach().to(dev, torch.float32).contiguous().view(B, -1)
+        data = data.detach().to(dev, torch.float32).contiguous().view(B, -1)         # (a map stays [B, C, h * w] in memory: read in place)
         desc = desc.detach().to(dev, torch.float32).contiguous()
         target = None if target is None else target.to(dev, torch.int64).contiguous()
+        if self.vattn:
+            eng.set_data_context(context)
         self._call += 1
         # exchange_args["uniforms"] (training): (u_z [T, B, W], u_s [T, B], u_w [T, B, W]) in place of the Philox stream -- the
         # reference's numpy draws (model.py:227, 420, 460), for tests that replay one conversation on two paths
@@ -472,6 +545,9 @@ class Game(object):
         masks = [tp["mask"][t].clone() for t in range(n + 1)]
         masks[-1].zero_()                                                 # model.py:870
         self.modules["sender"].h_x = tp["hx"]
+        if self.vattn:                                                    # model.py:189, 195: the last executed step's h_x, every step's weights
+            self.modules["sender"].h_x = tp["vattn_hx"][n - 1].clone()
+            self.modules["sender"].attn_scores = [tp["vattn_alpha"][t].clone() for t in range(n)]
         self.modules["receiver"].h_z = tp["h"][n]
         self.modules["receiver"].h_w = tp["g"][n - 1]
         if autograd:
@@ -520,7 +596,7 @@ class Game(object):
             bs, br = [], []
         return s, sen_w, rec_w, y, bs, br
 
-    def eval_forward(self, data, target, desc, corrupt_mask=None):
+    def eval_forward(self, data, target, desc, corrupt_mask=None, data_context=None):
         """The eval-mode conversation of exchange() (rounded messages, cumulative-product stop bit, every sample runs all
         max_exchange steps) WITHOUT slicing / cloning the tape into the reference's per-step lists and without any host
         synchronisation: returns the engine, whose tape views (mask, s, ps, z, pz, w, pw, y, ...) stay valid until its next
@@ -531,7 +607,14 @@ class Game(object):
                 self.modules[k].train(False)
         n, acc = getattr(self, "_eval_into", None) or (1, None)       # (eval_steps: n conversations, each reduced into acc)
         B = data.size(0) // n
-        eng = self.engine_for(B, desc.size(0))
+        if data_context is not None and not self.vattn:
+            raise NotImplementedError("data_context needs a Sender built with use_attn=True (visual attention)")
+        if self.vattn:                                                # data: the maps [n * B, C, h, w]; the context [n * B, G]
+            eng = self.vattn_engine_for(data, desc.size(0), n=n)
+            eng.set_data_context(self.check_context(data_context, data.size(0)), n=n)
+            self.modules["sender"].reset_state()
+        else:
+            eng = self.engine_for(B, desc.size(0))
         dev = eng.device
         data = data.to(dev, torch.float32).contiguous().view(n * B, -1)
         desc = desc.to(dev, torch.float32).contiguous()
@@ -547,7 +630,7 @@ class Game(object):
     def eval_accumulator(self, n_classes, top_k):
         return EvalAccumulator(n_classes, top_k)
 
-    def eval_steps(self, data, target, desc, n, acc, corrupt_mask=None):
+    def eval_steps(self, data, target, desc, n, acc, corrupt_mask=None, data_context=None):
         """n consecutive dev batches (data [n * B, F], target [n * B], as train_steps lays them out) evaluated by ONE library
         call (include/mmg.h: mmg_eval_steps): each conversation of eval_forward() is followed by the library's reduction launch,
         which adds the batch's top-k hits, confusion counts and classes seen to `acc` (eval_accumulator(); the calls of one
@@ -561,12 +644,13 @@ class Game(object):
             raise ValueError("eval_steps: the reductions need the targets")
         self._eval_into = (int(n), acc)
         try:
-            return self.eval_forward(data, target, desc, corrupt_mask=corrupt_mask)
+            return self.eval_forward(data, target, desc, corrupt_mask=corrupt_mask,
+                                     **({} if data_context is None else dict(data_context=data_context)))
         finally:
             self._eval_into = None
 
     # ------------------------------------------------------------------ model.py:1240-1339
-    def train_step(self, data, target, desc, uniforms=None, full_tape=False):
+    def train_step(self, data, target, desc, uniforms=None, full_tape=False, data_context=None):
         """exchange + masks + losses + four backward/clip/optimizer blocks, fused on the device.
         Nothing is copied to the host; read ``losses()`` when a log line needs them.
         The step keeps only what training reads (include/mmg.h: run_all_steps == 2): per-(step, sample) tape arrays are valid on
@@ -581,7 +665,11 @@ class Game(object):
         batch at every executed step, model.py:880-886) and every row of the sample dump.  Early exit == run-all and
         fused == phased are parity-tested (tests/test_hip_parity.py); the extra launches cost ~30 us once per log_interval."""
         B = data.size(0)
-        eng = self.train_engine_for(B, desc.size(0))
+        if self.vattn:                                # data: the map [B, C, h, w], read in place; data_context: [B, G]
+            eng = self._vattn_train_engine(data, desc, data_context)
+            data = data.detach().to(eng.device, torch.float32).contiguous().view(B, data.size(1), -1)
+        else:
+            eng = self.train_engine_for(B, desc.size(0))
         u = uniforms or (None, None, None)
         # the Philox minibatch counter and the optimizer step (Adam bias correction) live in each engine's workspace: hand
         # them over when the batch size / class count -- hence the engine -- changes between steps
@@ -604,11 +692,15 @@ class Game(object):
             eng.train_step(data, target, desc, u[0], u[1], u[2], seed=self.seed)
         return eng
 
-    def train_steps(self, data, target, desc, n):
+    def train_steps(self, data, target, desc, n, data_context=None):
         """n consecutive plain minibatches (no log block) enqueued by ONE library call: data [n * B, F] / target [n * B] in batch
         order (misc.Epoch).  Same updates, same sampling streams as n train_step() calls (tests/test_cli_gpu.py)."""
         B = data.size(0) // n
-        eng = self.train_engine_for(B, desc.size(0))
+        if self.vattn:
+            eng = self._vattn_train_engine(data, desc, data_context, n=n)
+            data = data.detach().to(eng.device, torch.float32).contiguous().view(n * B, data.size(1), -1)
+        else:
+            eng = self.train_engine_for(B, desc.size(0))
         last = getattr(self, "_train_engine", None)
         if last is not None and last is not eng:
             eng.tape["counter"][:3].copy_(last.tape["counter"][:3])
