@@ -223,6 +223,39 @@ int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, int has_rec
 enum { MMG_MIX_SUM = 0, MMG_MIX_PROD = 1 };
 int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_receiver);
 
+/* Relaxed messages: the Gumbel-sigmoid (binary concrete) channel with exact gradients, the differentiable-channel baseline next to
+ * REINFORCE and to the plain straight-through estimator of mmg_exchange_vjp_channel.  Binary messages only; the reference has no
+ * such option.  Per message element of a TRAINING conversation, with lz the logit, p = sigmoid(lz) and u the uniform draw the
+ * Bernoulli sample of that element uses today (same Philox key, index, counter and stream, or the injected u_z / u_w):
+ *   u'   = min(max(u, 2^-24), 1 - 2^-24)
+ *   soft = sigmoid((lz + log(1 - u') - log(u')) / tau)      tau = tau_sen for the sender's z, tau_rec for the receiver's w
+ *   bit  = (u < p) ? 1 : 0                                  exactly the unrelaxed compare (model.py:227 / 460)
+ *   hard == 0:  message = soft
+ *   hard == 1:  message = bit;  backward: message = soft + stopgrad(bit - soft)
+ * The sign of the noise makes soft > 0.5 exactly when u < p, up to rounding: a hard relaxed conversation draws the very bits an
+ * unrelaxed one draws from the same uniforms.  Everything downstream reads the message: the other agent, both baselines, the tape
+ * arrays "z" / "w" / "zr".  "lp_z" / "lp_w" keep their formula applied to the message value -- with hard == 0 they are NO
+ * log-likelihoods.  "pz", "pw", the entropy terms, the stop bit and the masks are unchanged, and so is every evaluation conversation
+ * (train == 0 rounds the probabilities: a relaxed pair is deployed discrete).  The soft values go to two tape arrays of their own,
+ * "zs" and "ws" [T, B, W], the last entries of mmg_tape_table; only a relaxed handle writes them.
+ * Backward: mmg_exchange_vjp_channel only.  The gradient arriving at a message crosses into the logits as soft (1 - soft) / tau --
+ * the exact derivative of what the forward pass computed --, upstream gradients on the probabilities keep p (1 - p):
+ *   dlz_t = dz_up[t] pz (1 - pz) + (W_ih^T dgi_t)     zs (1 - zs) / tau_sen
+ *   dlw_t = dw_up[t] pw (1 - pw) + (W_c^T dpre_{t+1}) ws (1 - ws) / tau_rec
+ * with zs / ws read from the tape (never drawn again: injected uniform buffers may be gone).  The stop bits, softmax(y) inside dbar,
+ * the baselines' inputs, data and desc stay constants; mmg_vjp_input_grads right behind it works unchanged.
+ * While it is set: mmg_exchange_forward(train = 1), mmg_sender_forward and mmg_receiver_forward form relaxed messages;
+ * mmg_exchange_forward(train = 0), mmg_eval_steps and mmg_loss_stats run as before; mmg_train_step[s], mmg_dp_train_step[s],
+ * mmg_backward, mmg_exchange_vjp and the three per-call VJPs return negative with this entry's name in the message (REINFORCE seeds
+ * and detached graphs are not what such a handle trains with).
+ * Kernels: a relaxed handle runs the generic per-sample conversation in an instantiation of its own (k_conversation<NT, .., RELAX>;
+ * the register-resident, many-class, sample-tile and wide-receiver conversations do not relax) and k_vjp_channel_relax.  Host only: the
+ * kernel selection is re-run only when the relaxed STATE changes, so the call may precede every minibatch to anneal the temperatures.
+ * tau_sen == 0 && tau_rec == 0 clears the setting and restores the original selection.
+ * Returns 0, or negative (the setting before stays): a tau that is negative or NaN; exactly one tau being zero; use_binary == 0; a
+ * handle with message flips or a sender variant (their setters refuse a relaxed handle likewise); an attention handle. */
+int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float tau_rec, int hard);
+
 /* Description attention, the reference's -desc_attn (model.py:267-271, 344-410, 444-445): the receiver's class description is no
  * fixed bag-of-words mean but, per sample and step, an attention over the WORDS of each description with the GRU state as the query.
  * With set [n_words, V] = the word vectors of all classes concatenated (a word without a vector is a row of zeros and is still
@@ -420,7 +453,7 @@ int mmg_degraded(const mmg_handle* h);
  *                  then one line with the caps it probed, in MMG_CAP_* order.
  *   mmg_plan_for:  the same text for a config and caller-supplied caps (n_caps == MMG_PLAN_CAPS), under the environment of the
  *                  call: no handle, no buffers, no GPU.  flags: bit 0 = no in-launch waits (what MMG_NO_ROLES=1 or a recovery
- *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
+ *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set, bit 3 = messages are relaxed.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
  * Both return 0, or negative (out too small: about 2 KB are needed; a config the library refuses). */
 enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP_RC_PERSIST, MMG_CAP_MC, MMG_CAP_MC3, MMG_CAP_MC3P,
        MMG_CAP_GAME, MMG_CAP_WGRAD_OPT, MMG_CAP_WGRAD, MMG_PLAN_CAPS };

@@ -98,6 +98,9 @@ class _Agent(nn.Module):
         """True when this call records an autograd node (opt-in, training mode, grad mode on)."""
         if not (getattr(game, "autograd", False) and self.training and torch.is_grad_enabled()):
             return False
+        if getattr(game, "relax", None):
+            raise NotImplementedError("autograd through the agent modules is not available on a game with relaxed messages (the "
+                                      "per-call VJPs detach the messages): Game.exchange() carries the gradient through them")
         if game.world > 1:
             raise NotImplementedError("autograd through the agent modules runs on one GPU only (data-parallel training: "
                                       "Game.train_step)")

@@ -1,5 +1,5 @@
 // conversation_body.h -- the text of k_conversation.  NOT a header of its own: kernels_fwd.h includes it twice, with MMG_CONV_ATTN 0 for
-// k_conversation<NT, FLIP, VAR> -- token for token the kernel every plain handle has always run, so its instantiations keep their symbols,
+// k_conversation<NT, FLIP, VAR, RELAX> -- token for token the kernel every plain handle has always run, so its instantiations keep their symbols,
 // arguments and code -- and with MMG_CONV_ATTN 1 for k_conversation_attn<NT>, the instantiation of an attention handle (mmg_attn_create;
 // model.py:344-410, 444-445): the receiver attends over the words of every description with its GRU state as the query.  `at` carries the
 // extra parameters, the description set and the per-word tables k_attn_prep formed (DD, E).  Per step, behind the GRU update:
@@ -16,13 +16,13 @@
 #if MMG_CONV_VATTN
 template <int NT>
 __global__ __launch_bounds__(NT) void k_conversation_vattn(Dims dm, Params P, Tape tp, ConvArgs ar, VattnArgs va) {
-    constexpr bool FLIP = false, VAR = false;
+    constexpr bool FLIP = false, VAR = false, RELAX = false;
 #elif MMG_CONV_ATTN
 template <int NT>
 __global__ __launch_bounds__(NT) void k_conversation_attn(Dims dm, Params P, Tape tp, ConvArgs ar, AttnArgs at) {
-    constexpr bool FLIP = false, VAR = false;
+    constexpr bool FLIP = false, VAR = false, RELAX = false;
 #else
-template <int NT, bool FLIP = false, bool VAR = false>
+template <int NT, bool FLIP = false, bool VAR = false, bool RELAX = false>
 __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp, ConvArgs ar) {
 #endif
     constexpr int GU = NT == 512 ? 8 : 4;               // row passes per load batch of gemv_rows
@@ -189,6 +189,11 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                         if (train) {
                             const float u = uz ? uz[n] : philox_uniform(ar.seed, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, 0u);
                             zz = (u < p) ? 1.f : 0.f;              // model.py:227
+                            if (RELAX) {                           // mmg_set_message_relaxation: the same draw as logistic noise
+                                const float soft = relax_soft(lz, u, ar.relax_tau_z);
+                                tp.zs[row * W + n] = soft;
+                                if (!ar.relax_hard) zz = soft;
+                            }
                         } else {
                             zz = rintf(p);                         // model.py:229 (torch.round = half-to-even)
                         }
@@ -433,6 +438,11 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                     if (train) {
                         const float u = uw ? uw[n] : philox_uniform(ar.seed, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, 2u);
                         wv = (u < p) ? 1.f : 0.f;                  // model.py:460
+                        if (RELAX) {
+                            const float soft = relax_soft(lw, u, ar.relax_tau_w);
+                            tp.ws[row * W + n] = soft;
+                            if (!ar.relax_hard) wv = soft;
+                        }
                     } else {
                         wv = rintf(p);                             // model.py:462
                     }

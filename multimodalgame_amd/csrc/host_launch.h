@@ -68,7 +68,7 @@ struct LaunchPlan {
 // What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes, the co-residency budgets, the
 // family and the launch plan.  Filled in three steps -- shape_pass (pure: everything up to the candidates that wait for a budget, and `ask`),
 // probe_device (`caps`), decide (pure: the rest) -- and printed by plan_text.  Constant until the next selection (mmg_create; error_gate after a
-// timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant when the routing changes).
+// timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation when the routing changes).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
     int vattn_bwd_smem = 0;      // dynamic LDS of k_vattn_bwd (a visual-attention handle)
@@ -82,6 +82,8 @@ struct Selection {
     bool flip = false;           // message flips are set on a binary handle (mmg_set_message_flipout): k_conversation_fast3<FLIP> / k_conversation<FLIP> serve it, nothing else
     bool attn = false;           // an attention handle (mmg_attn_create): the generic per-sample family with k_conversation_attn / k_bwd_conv_attn serves it, nothing else
     bool vattn = false;          // a visual-attention handle (mmg_vattn_create): the generic per-sample family with k_conversation_vattn serves it, nothing else
+    bool relax = false;          // relaxed messages are set (mmg_set_message_relaxation): the generic per-sample family with k_conversation<NT, false, false, RELAX>
+                                 // serves the handle, nothing else; its backward pass is mmg_exchange_vjp_channel (k_vjp_channel_relax) only
     int variant = 0;             // the sender variant in effect (mmg_set_sender_variant; SV_* bits, SV_IGNORE_REC on a binary handle only): != 0: the generic
                                  // per-sample family with k_conversation<NT, false, VAR> / k_bwd_conv<MANY, VAR> serves the handle, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
@@ -171,6 +173,10 @@ struct mmg_handle {
     // mmg_set_sender_variant: SV_* bits as the caller set them (layout.h).  Host state; what is in effect on this handle is sel.variant, which the
     // forward entries copy into ConvArgs::sender_var and the backward / sender-VJP launches pass as sv
     int sender_var = 0;
+    // mmg_set_message_relaxation: the temperatures of the sender's / the receiver's relaxed message (both 0: not set) and the rounding.  Host
+    // state; the forward entries copy it into ConvArgs, mmg_exchange_vjp_channel into VjpIn
+    float relax_tau_sen = 0.f, relax_tau_rec = 0.f;
+    bool relax_hard = false;
     // mmg_attn_create: desc_attn_dim (0: a plain handle) and the words of the description set; `at` is what the ATTN instantiations get
     // on top of the plain kernels' arguments (the six tensors inside the flat buffer, the attention arrays behind the plain tape), AG
     // the six gradient tensors; set_ready: mmg_set_desc_set has uploaded a set

@@ -138,6 +138,10 @@ static void plan_launches(mmg_handle* h) {
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, true> : k_conversation<256, false, true>;
         p.agent_fn = k_conversation<256, false, true>;
     }
+    if (s.relax) {                               // relaxed messages: the RELAX instantiations (shape_pass has cleared every other conversation kernel)
+        p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, false, true> : k_conversation<256, false, false, true>;
+        p.agent_fn = k_conversation<256, false, false, true>;
+    }
     p.conv_name = s.vattn ? "k_conversation_vattn" : wide ? "k_conversation_wv" : "k_conversation";     // (the profiling scope says which sender ran)
     p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
     // ---- baselines (training minibatch that did not run all rows) ----
@@ -207,7 +211,7 @@ static void plan_launches(mmg_handle* h) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout / mmg_set_sender_variant change the
+// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation change the
 // routing, and again when the library falls back to launches WITHOUT in-launch waits (h->no_roles: after a timed-out dependency, for a CU
 // budget / CU mask that cannot hold the role launches, or MMG_NO_ROLES=1).  Four steps, in this order:
 //   read_switches   the environment, once per selection -- never on the per-minibatch path, and nowhere else in the library
@@ -237,11 +241,11 @@ static Switches read_switches() {
 }
 
 // Pure.  Everything Dims, the switches and the handle's flags (no_roles; flips: message flips are set; variant: the SV_* bits of
-// mmg_set_sender_variant; err_word: the pinned error word exists)
+// mmg_set_sender_variant; relax: relaxed messages are set; err_word: the pinned error word exists)
 // settle alone.  A capability that also needs a co-residency budget (tile_split, tile_persist, mc_ok) leaves here as a CANDIDATE: its
 // preconditions hold and s.ask names the occupancy it waits for; decide() confirms or clears it.
-static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool err_word, Selection& s,
-                      int attn_dim = 0, int n_words = 0, VattnDims vd = VattnDims()) {
+static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool relax, bool err_word,
+                      Selection& s, int attn_dim = 0, int n_words = 0, VattnDims vd = VattnDims()) {
     s = Selection();
     // visual attention: the generic per-sample family with the sender's VATTN instantiation; every other family is cleared below
     s.vattn = vd.A > 0;
@@ -255,7 +259,11 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // family with the one-launch step, the many-class kernels, the sample tiles and the wide receiver do not, so all of them are cleared here
     s.variant = variant & (d.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
     if (s.variant && s.flip) return fail("message flips and a sender variant on one handle");
-    s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.attn && !s.vattn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
+    // relaxed messages (binary only): the generic per-sample kernels form them, so like a variant the setting clears the register-resident,
+    // many-class, sample-tile and wide-receiver conversations
+    s.relax = relax && d.use_binary;
+    if (s.relax && (s.flip || s.variant || s.attn || s.vattn)) return fail("relaxed messages with message flips, a sender variant or attention");
+    s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.relax && !s.attn && !s.vattn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
     s.sw_merge_prep = !w[SW_NO_MERGE_PREP] && !no_roles;
     s.sw_merge_bas = s.merge_roles;
     s.persist_ll = !w[SW_NO_PERSIST_LL] && persist_ll_shape(cfg.batch, cfg.h_dim, cfg.w_dim, cfg.rec_hidden, cfg.wv_dim, cfg.n_classes, cfg.max_exchange);
@@ -304,7 +312,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
     //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
     // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
-    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.attn && !s.vattn;
+    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.relax && !s.attn && !s.vattn;
     s.tile_force = w[SW_TILE];
     // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
     // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -405,6 +413,7 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     if (s.conv_smem > 48 * 1024) raise_lds(s.conv_smem, k_conversation<256>, k_conversation<512>);
     if (s.conv_smem > 48 * 1024 && s.flip) raise_lds(s.conv_smem, k_conversation<256, true>, k_conversation<512, true>);
     if (s.conv_smem > 48 * 1024 && s.variant) raise_lds(s.conv_smem, k_conversation<256, false, true>, k_conversation<512, false, true>);
+    if (s.conv_smem > 48 * 1024 && s.relax) raise_lds(s.conv_smem, k_conversation<256, false, false, true>, k_conversation<512, false, false, true>);
     if (s.conv_smem > 48 * 1024 && s.attn) raise_lds(s.conv_smem, k_conversation_attn<256>, k_conversation_attn<512>);
     if (s.bwd_smem > 48 * 1024 && s.attn) raise_lds(s.bwd_smem, k_bwd_conv_attn);
     if (s.conv_smem > 48 * 1024 && s.vattn) raise_lds(s.conv_smem, k_conversation_vattn<256>, k_conversation_vattn<512>);
@@ -503,7 +512,7 @@ static int decide(mmg_handle* h, const Switches& w) {
 
 static int shape_pass(mmg_handle* h, const Switches& w) {
     h->no_roles = h->no_roles || w.roles_off();
-    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words, h->vd);
+    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->relax_tau_sen > 0.f, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words, h->vd);
 }
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();

@@ -385,7 +385,19 @@ struct ConvArgs {
     float flip_pz, flip_pw;    // flip probabilities of the sender's / the receiver's message bits
     uint32_t flip_c1;          // evaluation: conversations enqueued on the handle since the setter call
     uint64_t flip_key;         // Philox key of the flip draws: the call's seed (training) / the setter's eval_seed
+    // mmg_set_message_relaxation: read by the RELAX instantiations only, in training conversations only.  The temperatures of the sender's
+    // z and of the receiver's w; relax_hard: the message is the bit (straight-through), else the soft value
+    float relax_tau_z, relax_tau_w;
+    int relax_hard;
 };
+
+// The relaxed (Gumbel-sigmoid / binary concrete) sample of a message element from the uniform draw u its Bernoulli sample uses:
+// sigmoid((logit + log(1 - u') - log(u')) / tau), u' = u clamped into [2^-24, 1 - 2^-24].  The sign of the logistic noise makes
+// soft > 0.5 exactly when u < sigmoid(logit), up to rounding: the rounded relaxed message is the Bernoulli bit of the same draw.
+__device__ __forceinline__ float relax_soft(float logit, float u, float tau) {
+    const float uc = fminf(fmaxf(u, 0x1p-24f), 1.f - 0x1p-24f);
+    return sigmoidf_((logit + logf(1.f - uc) - logf(uc)) / tau);
+}
 
 // the reference's corruption of message entry j, literally |z - m_j| in fp32 (model.py:818): exact XOR for z in {0, 1}, and in
 // continuous mode the abs of every entry, masked or not.  Call it where the sender's step-t message is formed, before anything
@@ -431,7 +443,8 @@ __global__ __launch_bounds__(64) void k_xcc_probe(uint32_t* __restrict__ out) {
 
 // FLIP: the instantiations a handle with message flips runs (flip_msg at both message sites); a compile-time switch, so that
 // the kernels of every other handle stay what they were.  VAR: likewise for a handle with a sender variant (ar.sender_var: SV_* bits); a
-// handle has flips or a variant, never both, so FLIP && VAR is not instantiated
+// handle has flips or a variant, never both, so FLIP && VAR is not instantiated.  RELAX: likewise for a handle with relaxed messages
+// (mmg_set_message_relaxation; relax_soft at both message sites, the soft values to tape.zs / tape.ws); never with FLIP or VAR
 #define MMG_CONV_ATTN 0
 #include "conversation_body.h"
 #undef MMG_CONV_ATTN

@@ -38,6 +38,7 @@ struct VjpIn {
     const float* dbr;    // [n, B]      d loss / d br_t
     int n;               // executed steps: upstream gradients exist for t < n only
     int sv;              // k_vjp_sen: the handle's sender variant (SV_* bits, layout.h; 0: the plain sender); sits in what was padding
+    float tau_z, tau_w;  // k_vjp_channel_relax: the temperatures of the relaxed messages (mmg_set_message_relaxation); nothing else reads them
 };
 
 __device__ __forceinline__ float vjp_block_reduce(float v, float* s_red, bool is_max) {
@@ -77,11 +78,18 @@ struct RecRow {
     const float *h0, *h1, *z, *y, *pw, *ps;    // GRU state before (NULL = zero state) / after the step, message in, y, w / s probs
     const float *dy, *dw, *dps, *dhw;          // d y, d w_probs | d w logits, d s_prob, d h_w
     size_t row;
+    // RELAX only (k_vjp_channel_relax): the gradient arriving at the relaxed message w_t, its soft value of the forward pass, tau_rec
+    const float *dwm, *wsoft;
+    float tau;
 };
 
 // The receiver's step backward (model.py:340-474), shared by the exchange and the per-call VJP.  On entry s_car (LDS, R floats)
 // holds d h_{t+1} from later uses of the state; on exit it holds d h_t.  Writes the row's deltas the weight-gradient jobs reduce
 // (vdgi, vdgh, vdgpre, vdlw, vdls, vdA, vdys) and the recomputed operands (vA, vg, vdbar, the softmax statistics vsm).
+// RELAX (relaxed messages, k_vjp_channel_relax): the message gradient io.dwm crosses into the logits with the relaxed sample's own
+// derivative ws (1 - ws) / tau, beside the upstream gradient on the probabilities with pw (1 - pw).  A compile-time switch: every
+// other caller keeps the code it had.
+template <bool RELAX = false>
 __device__ __forceinline__ void vjp_rec_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const RecRow& io) {
     const int D = dm.D, W = dm.W, R = dm.R, V = dm.V;
     const int tid = threadIdx.x;
@@ -168,6 +176,7 @@ __device__ __forceinline__ void vjp_rec_step(const Dims& dm, const Params& P, co
             const float gw = io.dw[j];
             dl = bin ? gw * s_pw[j] * (1.f - s_pw[j]) : gw;
         }
+        if (RELAX) { const float sw = io.wsoft[j]; dl += io.dwm[j] * (sw * (1.f - sw) / io.tau); }
         s_dlw[j] = dl;
         tp.vdlw[row * W + j] = dl;
     }
@@ -302,9 +311,12 @@ __host__ __device__ inline int vjp_sen_smem_floats(const Dims& d) { return 4 * d
 // d h_x = dpre * h_w to s_dhx and leaves d h_w = dpre * h_x in s_dpre / vdpre -- the operand of code_layer's jobs and of W_c^T .
 // (code_bias, d w) --; with a = tanh(h_x) (SV_IGNORE_CODE, model.py:208-210) d h_x = dpre and d h_w = 0 exactly.  A compile-time
 // switch: the callers without a variant (k_vjp_channel among them) keep the code they had.
-template <bool VAR = false>
+// RELAX (relaxed messages, k_vjp_channel_relax): dzm is the gradient arriving at the relaxed message z_t and zsoft its soft value of the
+// forward pass; it crosses into the logits as zs (1 - zs) / tau, beside dz pz (1 - pz).  Likewise a compile-time switch.
+template <bool VAR = false, bool RELAX = false>
 __device__ __forceinline__ void vjp_sen_step(const Dims& dm, const Params& P, const Tape& tp, float* smem, const float* c,
-                                             const float* pz, const float* dz, size_t row, int sv = 0) {
+                                             const float* pz, const float* dz, size_t row, int sv = 0, const float* dzm = nullptr,
+                                             const float* zsoft = nullptr, float tau = 1.f) {
     const int H = dm.H, W = dm.W, tid = threadIdx.x;
     float* s_hx = smem;  float* s_a = s_hx + H;  float* s_dpre = s_a + H;  float* s_dhx = s_dpre + H;
     float* s_c = s_dhx + H;  float* s_dlz = s_c + W;
@@ -320,6 +332,7 @@ __device__ __forceinline__ void vjp_sen_step(const Dims& dm, const Params& P, co
             const float g = dz[j];
             if (bin) { const float p = pz[j]; dl = g * p * (1.f - p); } else dl = g;
         }
+        if (RELAX) { const float sz = zsoft[j]; dl += dzm[j] * (sz * (1.f - sz) / tau); }
         s_dlz[j] = dl;
         tp.vdlz[row * W + j] = dl;
     }
@@ -394,8 +407,12 @@ __host__ __device__ inline int vjp_channel_smem_floats(const Dims& d) {
 // Rows of steps t >= n get zero deltas: both carries start at zero and the cross terms are linear in the upstream gradients.
 // Writes the rows the receiver's and the sender's job tables reduce; the stop bit, softmax(y) inside dbar, data and desc stay
 // constants.
-__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel(Dims dm, Params P, Tape tp, VjpIn in) {
-    extern __shared__ float smem[];
+// RELAX (a handle with relaxed messages, mmg_set_message_relaxation): the messages are the relaxed samples (or their bits, hard), whose
+// soft values the forward pass left in tape.zs / tape.ws.  The cross terms and the upstream gradients no longer share one factor:
+//   dlz_t = dz_up[t] pz (1 - pz) + (W_ih^T dgi_t) zs (1 - zs) / tau_sen;   dlw_t = dw_up[t] pw (1 - pw) + q_{t+1} ws (1 - ws) / tau_rec
+// so s_dw / s_dz carry the cross terms alone and the steps read the upstream rows themselves.
+template <bool RELAX>
+__device__ __forceinline__ void vjp_channel_body(const Dims& dm, const Params& P, const Tape& tp, const VjpIn& in, float* smem) {
     const int b = blockIdx.x, B = dm.B, D = dm.D, H = dm.H, W = dm.W, R = dm.R, T = dm.T, tid = threadIdx.x;
     float* rsm = smem;                                        // vjp_rec_step's area
     float* ssm = rsm + vjp_rec_smem_floats(dm);               // vjp_sen_step's area
@@ -409,7 +426,7 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel(Dims dm, Params P, Ta
     for (int i = tid; i < R; i += MMG_BLOCK) s_car[i] = 0.f;
     for (int h = tid; h < H; h += MMG_BLOCK) { s_hx[h] = tp.hx[(size_t)b * H + h]; s_dhx[h] = 0.f; }
     for (int j = tid; j < W; j += MMG_BLOCK)
-        s_dw[j] = (T - 1 < in.n && in.dw) ? in.dw[((size_t)(T - 1) * B + b) * W + j] : 0.f;
+        s_dw[j] = (!RELAX && T - 1 < in.n && in.dw) ? in.dw[((size_t)(T - 1) * B + b) * W + j] : 0.f;
     for (int t = T - 1; t >= 0; --t) {
         const size_t row = (size_t)t * B + b;
         const bool live = t < in.n;
@@ -418,28 +435,42 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel(Dims dm, Params P, Ta
         io.pw = tp.pw + row * W; io.ps = tp.ps + row;
         io.dy = (live && in.dy) ? in.dy + row * D : nullptr;
         io.dw = s_dw;
+        if (RELAX) { io.dw = (live && in.dw) ? in.dw + row * W : nullptr; io.dwm = s_dw; io.wsoft = tp.ws + row * W; io.tau = in.tau_w; }
         io.dps = (live && in.dps) ? in.dps + row : nullptr;
         io.dhw = nullptr;
         io.row = row;
-        vjp_rec_step(dm, P, tp, rsm, io);
+        vjp_rec_step<RELAX>(dm, P, tp, rsm, io);
         __syncthreads();                                      // this row of vdgi complete
         const float* dgi = tp.vdgi + row * 3 * R;
         for (int k = tid; k < W; k += MMG_BLOCK) {            // d z_t = W_ih^T dgi_t
             float acc = 0.f;
             for (int i = 0; i < 3 * R; ++i) acc = fmaf(Wih[(size_t)i * W + k], dgi[i], acc);
-            s_dz[k] = acc + ((live && in.dz) ? in.dz[row * W + k] : 0.f);
+            s_dz[k] = acc + ((!RELAX && live && in.dz) ? in.dz[row * W + k] : 0.f);
         }
-        vjp_sen_step(dm, P, tp, ssm, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W, s_dz, row);
+        if (RELAX) vjp_sen_step<false, true>(dm, P, tp, ssm, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W,
+                                             (live && in.dz) ? in.dz + row * W : nullptr, row, 0, s_dz, tp.zs + row * W, in.tau_z);
+        else vjp_sen_step(dm, P, tp, ssm, t == 0 ? nullptr : tp.w + (row - B) * W, tp.pz + row * W, s_dz, row);
         __syncthreads();                                      // s_dpre complete
         for (int j = tid; j < W; j += MMG_BLOCK) {            // d w_{t-1} = W_c^T dpre_t (t = 0: the code_bias path)
             float acc = 0.f;
             for (int h = 0; h < H; ++h) acc = fmaf(Wc[(size_t)h * W + j], s_dpre[h], acc);
             if (t == 0) tp.vdc0[(size_t)b * W + j] = acc;
-            else s_dw[j] = acc + ((t - 1 < in.n && in.dw) ? in.dw[(row - B) * W + j] : 0.f);
+            else s_dw[j] = acc + ((!RELAX && t - 1 < in.n && in.dw) ? in.dw[(row - B) * W + j] : 0.f);
         }
     }
     __syncthreads();
     for (int h = tid; h < H; h += MMG_BLOCK) tp.vdhx[(size_t)b * H + h] = s_dhx[h];
+}
+
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel(Dims dm, Params P, Tape tp, VjpIn in) {
+    extern __shared__ float smem[];
+    vjp_channel_body<false>(dm, P, tp, in, smem);
+}
+
+// ... of a handle with relaxed messages (mmg_set_message_relaxation): the two-factor rule above
+__global__ __launch_bounds__(MMG_BLOCK) void k_vjp_channel_relax(Dims dm, Params P, Tape tp, VjpIn in) {
+    extern __shared__ float smem[];
+    vjp_channel_body<true>(dm, P, tp, in, smem);
 }
 
 // The caller-side buffers of one sender call (mmg_sender_vjp), [B, .] each.  w: the code input (t > 0).

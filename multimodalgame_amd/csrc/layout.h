@@ -309,7 +309,10 @@ inline VattnParams resolve_vattn_params(const ParamLayout& L, float* base) {
     X(vchx, float, 0, 2, B, H, 1)        /* baseline_sen: x (= sender.h_x)                                 */ \
     X(vcdh, float, 0, 2, B, K, 1)        /* baselines: d hidden = dscore w2 1[hidden > 0] (A of k_vjp_nn)  */ \
     X(tables, uint8_t, 1, 1, 98304, 1, 1) /* GEMM / column-sum job descriptors      */ \
-    X(vtables, uint8_t, 1, 1, 8 * MMG_VJP_TABLE_BYTES, 1, 1) /* VJP job tables: the exchange's four (one per agent), then the per-call four, uploaded at mmg_create */
+    X(vtables, uint8_t, 1, 1, 8 * MMG_VJP_TABLE_BYTES, 1, 1) /* VJP job tables: the exchange's four (one per agent), then the per-call four, uploaded at mmg_create */ \
+    /* ---- relaxed messages (mmg_set_message_relaxation): written by the RELAX instantiations only, read by k_vjp_channel_relax ---- */ \
+    X(zs, float, 0, 3, T, B, W)          /* soft sender message sigmoid((lz + logistic noise) / tau_sen) of a training conversation */ \
+    X(ws, float, 0, 3, T, B, W)          /* soft receiver message, likewise with tau_rec */
 
 // statistics vector (f64).  Per stream (0 = stop bits, 1 = receiver msgs, 2 = sender msgs) and
 // step: n, sum w, sum w^2, sum w*logp, sum negent; per baseline (0 = rec, 1 = sen) and step:

@@ -423,6 +423,7 @@ extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_ca
     mmg_handle* h = owner.get();
     h->d_err = reinterpret_cast<uint32_t*>(base);           // (as a created handle has one; h_err stays NULL: nothing to release)
     h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0; h->sender_var = (flags & 4) ? SV_PROD : 0;
+    if (flags & 8) h->relax_tau_sen = h->relax_tau_rec = 1.f;
     const Switches w = read_switches();
     if (shape_pass(h, w)) return -1;
     memcpy(h->sel.caps, caps, sizeof(h->sel.caps));
@@ -504,6 +505,19 @@ static void flip_args(mmg_handle* h, ConvArgs& ar, uint64_t seed, int train, boo
     ar.flip_pz = h->flip_p_sen; ar.flip_pw = h->flip_p_rec;
     ar.flip_key = train ? seed : h->flip_eval_seed;
     if (!train) ar.flip_c1 = new_conv ? h->flip_evals++ : (h->flip_evals ? h->flip_evals - 1u : 0u);
+}
+
+// Relaxed messages of this call (mmg_set_message_relaxation), by value; only the RELAX instantiations read them, in training conversations
+static void relax_args(const mmg_handle* h, ConvArgs& ar) {
+    if (!h->sel.relax) return;
+    ar.relax_tau_z = h->relax_tau_sen; ar.relax_tau_w = h->relax_tau_rec; ar.relax_hard = h->relax_hard ? 1 : 0;
+}
+// ... and what such a handle does not train with: REINFORCE seeds and detached graphs
+static int refuse_relax(const mmg_handle* h, const char* who) {
+    if (h && h->sel.relax)
+        return fail("%s is not available while messages are relaxed (mmg_set_message_relaxation): such a handle trains through "
+                    "mmg_exchange_vjp_channel; mmg_set_message_relaxation(h, 0, 0, 0) clears the setting", who);
+    return 0;
 }
 
 // FAM_TILE: one of the plan's seven outcomes (host_select.h: plan_launches).  The outcome is known BEFORE a timing scope opens.
@@ -646,6 +660,7 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
     if (h->corrupt_on) { ar.corrupt_on = 1; memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt)); }
     flip_args(h, ar, seed, train, true);
     ar.sender_var = s.variant;
+    relax_args(h, ar);
     h->fwd = ForwardState();
     const bool base_ready = p.fwd_basehx && bas && !all_rows;
     switch (s.family) {
@@ -731,6 +746,8 @@ extern "C" int mmg_set_message_flipout(mmg_handle* h, int has_sen, float p_sen, 
     };
     if ((has_sen || has_rec) && h->sender_var)
         return fail("mmg_set_message_flipout: the handle has a sender variant (mmg_set_sender_variant); flips and a variant do not combine");
+    if ((has_sen || has_rec) && h->relax_tau_sen > 0.f)
+        return fail("mmg_set_message_flipout: the handle has relaxed messages (mmg_set_message_relaxation); a flip of a relaxed message is not defined");
     set(has_sen != 0, p_sen, has_rec != 0, p_rec, flipout_dev != 0, eval_seed, 0u);
     if (((h->flip_sen || h->flip_rec) && h->dm.use_binary) == h->sel.flip) return 0;        // same routing: nothing to select
     const JobTable old = h->jt;
@@ -757,6 +774,8 @@ extern "C" int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, i
     if (want && refuse_attn(h, "mmg_set_sender_variant")) return -1;
     if (want && (h->flip_sen || h->flip_rec))
         return fail("mmg_set_sender_variant: the handle has message flips (mmg_set_message_flipout); flips and a variant do not combine");
+    if (want && h->relax_tau_sen > 0.f)
+        return fail("mmg_set_sender_variant: the handle has relaxed messages (mmg_set_message_relaxation); the joint VJP does not form the variants");
     const int old_var = h->sender_var;
     h->sender_var = want;
     const int eff = want & (h->dm.use_binary ? (SV_PROD | SV_IGNORE_CODE | SV_IGNORE_REC) : (SV_PROD | SV_IGNORE_CODE));
@@ -767,6 +786,38 @@ extern "C" int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, i
         h->sender_var = old_var;
         select_paths(h);
         return fail("mmg_set_sender_variant: %s", why.c_str());
+    }
+    if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
+        HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
+        HIP_OK(hipMemcpy(h->d_jt, &h->jt, sizeof(JobTable), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// Relaxed messages (include/mmg.h): host state; re-runs the selection only when the relaxed state itself changes, since a relaxed handle is served
+// by the generic per-sample family only (host_select.h) -- a call that only moves the temperatures selects nothing.
+extern "C" int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float tau_rec, int hard) {
+    if (!h) return fail("NULL handle");
+    if (!(tau_sen >= 0.f) || !(tau_rec >= 0.f))          // (NaN fails both compares)
+        return fail("mmg_set_message_relaxation: tau_sen = %g, tau_rec = %g: temperatures must be positive (both 0 clears the setting)", (double)tau_sen, (double)tau_rec);
+    if ((tau_sen == 0.f) != (tau_rec == 0.f))
+        return fail("mmg_set_message_relaxation: tau_sen = %g, tau_rec = %g: both positive, or both 0 to clear the setting", (double)tau_sen, (double)tau_rec);
+    const bool on = tau_sen > 0.f;
+    if (on) {
+        if (!h->dm.use_binary) return fail("mmg_set_message_relaxation: binary messages only (use_binary = 0: the messages are the logits, already differentiable)");
+        if (h->flip_sen || h->flip_rec) return fail("mmg_set_message_relaxation: the handle has message flips (mmg_set_message_flipout)");
+        if (h->sender_var) return fail("mmg_set_message_relaxation: the handle has a sender variant (mmg_set_sender_variant)");
+        if (refuse_attn(h, "mmg_set_message_relaxation")) return -1;
+    }
+    const float o_sen = h->relax_tau_sen, o_rec = h->relax_tau_rec; const bool o_hard = h->relax_hard;
+    h->relax_tau_sen = tau_sen; h->relax_tau_rec = tau_rec; h->relax_hard = on && hard != 0;
+    if (on == h->sel.relax) return 0;                    // same routing: nothing to select
+    const JobTable old = h->jt;
+    if (select_paths(h)) {
+        const std::string why = g_err;
+        h->relax_tau_sen = o_sen; h->relax_tau_rec = o_rec; h->relax_hard = o_hard;
+        select_paths(h);
+        return fail("mmg_set_message_relaxation: %s", why.c_str());
     }
     if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
         HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
@@ -895,6 +946,7 @@ static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_targe
 extern "C" int mmg_backward(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, void* stream) {
     if (!h) return fail("NULL handle");
     if (!d_x || !d_target || !d_desc) return fail("x / target / desc must not be NULL");
+    if (refuse_relax(h, "mmg_backward")) return -1;
     if (h->fwd.bas_pending) return fail("mmg_loss_stats must run between mmg_exchange_forward(train) and mmg_backward (it carries the baselines' forward pass)");
     // continuous messages: the statistics are this rank's sum of rewards and hit count only, nothing a gradient depends on
     // (model.py:1297-1305) -- the call forms them itself (as a workgroup of the backward launch where the path has one, else as
@@ -972,7 +1024,7 @@ static int train_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
 
 extern "C" int mmg_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                               const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, void* stream) {
-    if (begin_minibatch(h, "mmg_train_step")) return -1;
+    if (begin_minibatch(h, "mmg_train_step") || refuse_relax(h, "mmg_train_step")) return -1;
     if (h->cfg.global_batch != h->cfg.batch) return fail("mmg_train_step is single-GPU; with several ranks: mmg_dp_train_step, or all-reduce between the phases");
     if (!d_target) return fail("target must not be NULL");
     return run_minibatches(h, 1, stream, [&](int64_t) { return train_step_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, stream); });
@@ -983,7 +1035,7 @@ extern "C" int mmg_train_step(mmg_handle* h, const float* d_x, const int64_t* d_
 // sampling streams advance with the device-side minibatch counter exactly as under n mmg_train_step calls.
 extern "C" int mmg_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc,
                                uint64_t seed, void* stream) {
-    if (begin_minibatch(h, "mmg_train_steps")) return -1;
+    if (begin_minibatch(h, "mmg_train_steps") || refuse_relax(h, "mmg_train_steps")) return -1;
     if (h->cfg.global_batch != h->cfg.batch) return fail("mmg_train_steps is single-GPU; with several ranks: mmg_dp_train_steps");
     if (!d_x || !d_target || !d_desc || n < 0) return fail("x / target / desc must not be NULL, n >= 0");
     return run_minibatches(h, n, stream, [&](int64_t i) {
@@ -1027,13 +1079,13 @@ static int dp_step_impl(mmg_handle* h, const float* d_x, const int64_t* d_target
 }
 extern "C" int mmg_dp_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                                  const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed, int full_tape, int reduce, void* stream) {
-    if (begin_minibatch(h, "mmg_dp_train_step")) return -1;
+    if (begin_minibatch(h, "mmg_dp_train_step") || refuse_relax(h, "mmg_dp_train_step")) return -1;
     if (!d_x || !d_target || !d_desc) return fail("x / target / desc must not be NULL");
     return run_minibatches(h, 1, stream, [&](int64_t) { return dp_step_impl(h, d_x, d_target, d_desc, d_u_z, d_u_s, d_u_w, seed, full_tape, reduce, stream); });
 }
 extern "C" int mmg_dp_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc,
                                   uint64_t seed, int reduce, void* stream) {
-    if (begin_minibatch(h, "mmg_dp_train_steps")) return -1;
+    if (begin_minibatch(h, "mmg_dp_train_steps") || refuse_relax(h, "mmg_dp_train_steps")) return -1;
     if (!d_x || !d_target || !d_desc || n < 0) return fail("x / target / desc must not be NULL, n >= 0");
     return run_minibatches(h, n, stream, [&](int64_t i) {
         return dp_step_impl(h, d_x + (size_t)i * h->dm.B * h->dm.F, d_target + (size_t)i * h->dm.B, d_desc, nullptr, nullptr, nullptr, seed, 0, reduce, stream);
@@ -1112,6 +1164,7 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 1; ar.w_in = d_w;
     flip_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
+    relax_args(h, ar);
     if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
     if (h->sel.vattn) hipLaunchKernelGGL(h->sel.plan.agent_vattn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->va);
     else hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
@@ -1145,6 +1198,7 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 2; ar.h_state = d_h_z; ar.sprod_state = d_s_prob_prod; ar.sprod_first = first;
     flip_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
+    relax_args(h, ar);
     if (h->sel.attn) hipLaunchKernelGGL(h->sel.plan.agent_attn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->at);
     else hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(receiver)")) return -1;
@@ -1190,7 +1244,7 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
                                 const float* d_dz, const float* d_dw, const float* d_dps, const float* d_dbs, const float* d_dbr,
                                 void* stream) {
     if (!h) return fail("NULL handle");
-    if (refuse_attn(h, "mmg_exchange_vjp")) return -1;
+    if (refuse_attn(h, "mmg_exchange_vjp") || refuse_relax(h, "mmg_exchange_vjp")) return -1;
     const Dims& d = h->dm;
     if (agent < 0 || agent > 3) return fail("unknown agent %d", agent);
     if (n_steps < 1 || n_steps > d.T) return fail("n_steps must be in [1, %d] (got %d)", d.T, n_steps);
@@ -1198,6 +1252,7 @@ extern "C" int mmg_exchange_vjp(mmg_handle* h, int agent, int n_steps, const flo
     hipStream_t st = (hipStream_t)stream;
     VjpIn in;
     in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = d_dbs; in.dbr = d_dbr; in.n = n_steps; in.sv = h->sel.variant;
+    in.tau_z = in.tau_w = 0.f;
     if (agent == MMG_AGENT_RECEIVER) {
         if (!d_desc) return fail("desc must not be NULL");
         const size_t smem = sizeof(float) * (size_t)vjp_rec_smem_floats(d);
@@ -1238,11 +1293,12 @@ extern "C" int mmg_exchange_vjp_channel(mmg_handle* h, int n_steps, const float*
     hipStream_t st = (hipStream_t)stream;
     VjpIn in;
     in.dy = d_dy; in.dz = d_dz; in.dw = d_dw; in.dps = d_dps; in.dbs = nullptr; in.dbr = nullptr; in.n = n_steps; in.sv = 0;
+    in.tau_z = h->relax_tau_sen; in.tau_w = h->relax_tau_rec;
     const size_t smem = sizeof(float) * (size_t)vjp_channel_smem_floats(d);
     if (vjp_lds_ok(smem, "channel", " (too many classes or h_dim too large)") || launch_vjp_cd(h, st, d_desc)) return -1;
     {
         Scope sc(h, st, "k_vjp_channel");
-        hipLaunchKernelGGL(k_vjp_channel, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in);
+        hipLaunchKernelGGL(h->sel.relax ? k_vjp_channel_relax : k_vjp_channel, dim3(d.B), dim3(MMG_BLOCK), smem, st, d, h->P, h->tp, in);
         if (launch_check("k_vjp_channel")) return -1;
     }
     if (launch_vjp_class(h, st, in)) return -1;
@@ -1322,7 +1378,7 @@ extern "C" int mmg_vjp_input_grads(mmg_handle* h, int per_call, int n_steps, con
 extern "C" int mmg_sender_vjp(mmg_handle* h, const float* d_x, const float* d_w, int t, const float* d_h_x, const float* d_probs,
                               const float* d_dout, const float* d_dh_x, float* d_dx, float* d_dw, void* stream) {
     if (!h) return fail("NULL handle");
-    if (refuse_attn(h, "mmg_sender_vjp")) return -1;
+    if (refuse_attn(h, "mmg_sender_vjp") || refuse_relax(h, "mmg_sender_vjp")) return -1;
     const Dims& d = h->dm;
     if (!d_x || !d_h_x) return fail("x / h_x must not be NULL");
     if (t < 0 || t >= d.T) return fail("t out of range");
@@ -1358,7 +1414,7 @@ extern "C" int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_
                                 const float* d_dw, const float* d_dps, const float* d_dh_w, const float* d_dh_new,
                                 float* d_dz, float* d_dh_prev, void* stream) {
     if (!h) return fail("NULL handle");
-    if (refuse_attn(h, "mmg_receiver_vjp")) return -1;
+    if (refuse_attn(h, "mmg_receiver_vjp") || refuse_relax(h, "mmg_receiver_vjp")) return -1;
     const Dims& d = h->dm;
     if (!d_z || !d_desc || !d_h_new || !d_y) return fail("z / desc / h_new / y must not be NULL");
     if (d.use_binary && d_dw && !d_w_probs) return fail("w_probs must not be NULL when d w_probs is given (binary messages)");
@@ -1388,7 +1444,7 @@ extern "C" int mmg_receiver_vjp(mmg_handle* h, const float* d_z, const float* d_
 extern "C" int mmg_baseline_vjp(mmg_handle* h, int which, const float* d_x, const float* d_binary, const float* d_inp, int rows,
                                 const float* d_dscore, float* d_dx, float* d_dbinary, float* d_dinp, void* stream) {
     if (!h) return fail("NULL handle");
-    if (refuse_attn(h, "mmg_baseline_vjp")) return -1;
+    if (refuse_attn(h, "mmg_baseline_vjp") || refuse_relax(h, "mmg_baseline_vjp")) return -1;
     const Dims& d = h->dm;
     if (which != MMG_AGENT_BASELINE_REC && which != MMG_AGENT_BASELINE_SEN)
         return fail("which must be MMG_AGENT_BASELINE_REC or MMG_AGENT_BASELINE_SEN");

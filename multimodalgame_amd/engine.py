@@ -219,6 +219,28 @@ class Engine(object):
         variant = (mix, bool(ignore_code), bool(ignore_receiver))
         self.sender_variant = None if variant == ("sum", False, False) else variant
 
+    relaxation = None              # (tau_sen, tau_rec, hard) while set_message_relaxation holds
+
+    def set_message_relaxation(self, tau_sen=None, tau_rec=None, hard=False):
+        """Relaxed messages, the Gumbel-sigmoid channel (include/mmg.h: mmg_set_message_relaxation): every message element of a
+        training conversation is sigmoid((logit + logistic noise) / tau), the noise formed from the very uniform its Bernoulli
+        sample draws -- tau_sen for the sender's message, tau_rec for the receiver's; hard: the message is the bit and the soft
+        value carries the gradient (straight-through).  The soft values land in tape["zs"] / tape["ws"].  vjp_channel is the
+        backward pass of such an engine; the REINFORCE entries and the detached VJPs raise.  None, None clears the setting.
+        Host only; the library re-selects its kernels only when the relaxed state changes, so a training loop may call this
+        before every minibatch to anneal the temperatures."""
+        if (tau_sen is None) != (tau_rec is None):
+            raise ValueError("tau_sen and tau_rec: both temperatures, or None, None to clear the setting")
+        if tau_sen is None:
+            _lib.check(self.lib.mmg_set_message_relaxation(self.handle, 0.0, 0.0, 0))
+            self.relaxation = None
+            return
+        tau_sen, tau_rec = float(tau_sen), float(tau_rec)
+        if not (tau_sen > 0.0 and tau_rec > 0.0):                         # (NaN fails the compare)
+            raise ValueError("tau_sen = %r, tau_rec = %r: temperatures must be positive" % (tau_sen, tau_rec))
+        _lib.check(self.lib.mmg_set_message_relaxation(self.handle, tau_sen, tau_rec, int(bool(hard))))
+        self.relaxation = (tau_sen, tau_rec, bool(hard))
+
     def set_desc_set(self, desc_set, lens):
         """The description set of an attention engine (include/mmg.h: mmg_set_desc_set): desc_set [n_words, V], the word vectors of
         all classes concatenated; lens: n_classes positive lengths that sum to n_words.  Copied into the workspace (a blocking

@@ -15,6 +15,25 @@ def _input_grad(g, like):
     return None if g is None else g.to(device=like.device, dtype=like.dtype).reshape(like.shape)
 
 
+def relax_setting(relax):
+    """dict(tau_sen=..., tau_rec=..., hard=False) (or a (tau_sen, tau_rec, hard) tuple) -> (tau_sen, tau_rec, hard); None stays.
+    Raises ValueError for anything but two positive temperatures."""
+    if relax is None:
+        return None
+    if isinstance(relax, dict):
+        unknown = sorted(set(relax) - {"tau_sen", "tau_rec", "hard"})
+        if unknown or "tau_sen" not in relax or "tau_rec" not in relax:
+            raise ValueError("relax = dict(tau_sen=..., tau_rec=..., hard=False) expected, got keys %s" % sorted(relax))
+        relax = (relax["tau_sen"], relax["tau_rec"], relax.get("hard", False))
+    tau_sen, tau_rec, hard = relax
+    if tau_sen is None or tau_rec is None:
+        raise ValueError("relax: both temperatures, tau_sen and tau_rec, are needed")
+    tau_sen, tau_rec = float(tau_sen), float(tau_rec)
+    if not (tau_sen > 0.0 and tau_rec > 0.0):                             # (NaN fails the compare)
+        raise ValueError("relax: tau_sen = %r and tau_rec = %r must be positive" % (tau_sen, tau_rec))
+    return tau_sen, tau_rec, bool(hard)
+
+
 class _AgentVJP(torch.autograd.Function):
     """One agent's graph of a training exchange() as ONE autograd node (the reference's four graphs are disjoint: every input
     crossing between agents is detached, model.py:807-811, 826-829, 835-843).  Inputs: a spec (engine, tape generation, steps,
@@ -97,7 +116,9 @@ class _ChannelVJP(_AgentVJP):
     two agents are not detached (``channel_grad``; the reference detaches them, model.py:807-811, 826-829).  Inputs: a spec as
     _AgentVJP's and the sender's, then the receiver's parameters; outputs: what _SenderVJP and _ReceiverVJP hand out together
     (pz | z logits, y, ps, pw | w logits, stacked over the executed steps).  backward runs Engine.vjp_channel ONCE and returns
-    copies of both agents' gradient slices; under ``input_grad`` d data and d desc too, with the channel's cross terms."""
+    copies of both agents' gradient slices; under ``input_grad`` d data and d desc too, with the channel's cross terms.
+    spec["relax"]: the relaxation the forward ran with (None: the straight-through channel) -- backward runs under the same one,
+    whatever the engine has been set to since (an annealing step between exchange() and backward())."""
     KEYS = ("dz", "dy", "dps", "dw")
 
     @staticmethod
@@ -109,8 +130,16 @@ class _ChannelVJP(_AgentVJP):
         if eng.generation != spec["gen"]:
             raise RuntimeError("the exchange tape this sender-receiver node was recorded on has been overwritten by a later "
                                "engine call (exchange / train_step / forward): call backward() before the next one")
-        eng.vjp_channel(spec["n"], spec["x"], spec["desc"], **{k: g for k, g in zip(_ChannelVJP.KEYS, grads) if g is not None})
-        return (None,) + _AgentVJP._input_grads(ctx, saved) + tuple(eng.grads[agent][name].clone() for agent, name in spec["names"])
+        relax, now = spec.get("relax"), eng.relaxation
+        if relax != now:
+            eng.set_message_relaxation(*(relax or (None, None)))
+        try:
+            eng.vjp_channel(spec["n"], spec["x"], spec["desc"], **{k: g for k, g in zip(_ChannelVJP.KEYS, grads) if g is not None})
+            return ((None,) + _AgentVJP._input_grads(ctx, saved)
+                    + tuple(eng.grads[agent][name].clone() for agent, name in spec["names"]))
+        finally:
+            if relax != now:
+                eng.set_message_relaxation(*(now or (None, None)))
 
 
 class FlatOptimizer(object):
@@ -240,6 +269,15 @@ class Game(object):
     message is replaced by zeros after it was sampled or rounded (Engine.set_sender_variant).  They hold for every entry of every
     engine the game creates, on every rank; plain autograd works with them, channel_grad, input_grad and message flips do not.
     Separate from `flags` as well: -sender_mix, -ignore_code and -ignore_receiver stay refused there.
+    relax = dict(tau_sen=..., tau_rec=..., hard=False): relaxed messages, the Gumbel-sigmoid channel with exact gradients
+    (Engine.set_message_relaxation) -- the differentiable-channel baseline next to REINFORCE and to the plain straight-through
+    estimator of channel_grad.  Training exchange() calls then form every message element as sigmoid((logit + logistic noise) / tau)
+    from the uniform its Bernoulli sample draws (hard: the bit forward, the soft value's gradient backward), and the joint
+    sender-receiver node differentiates exactly that.  Needs autograd=True, channel_grad=True, binary messages and world == 1;
+    set_relaxation() anneals the temperatures between minibatches; exchange_args["relax"] overrides the setting for one call.
+    Evaluation conversations stay discrete.  Message flips, sender variants, attention, train_step(s) and the agent modules' own
+    autograd nodes are not available with it and raise; bs / br of a relaxed exchange are plain tensors (the baselines are
+    REINFORCE machinery: mmg_exchange_vjp refuses a relaxed handle).
     Description attention (model.py:267-271, 344-410) is read from the module: Receiver(..., desc_attn=True, desc_attn_dim=A).  The
     receiver then attends over the words of every description: exchange() takes exchange_args["desc_set"] / ["desc_set_lens"] as
     the reference does, Receiver.forward its desc_set / desc_set_lens arguments, and set_desc_set() states the pair for the entries
@@ -257,7 +295,7 @@ class Game(object):
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
                  channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False,
-                 sender_mix="sum", ignore_code=False, ignore_receiver=False):
+                 sender_mix="sum", ignore_code=False, ignore_receiver=False, relax=None):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -311,6 +349,9 @@ class Game(object):
                     raise NotImplementedError("visual attention with %s is not available" % name)
         self._call = 0
         self.rank, self.world, self.group, self._dp = 0, 1, None, {}
+        self.relax = relax_setting(relax)
+        if self.relax:
+            self._check_relax(self.autograd, self.channel_grad)
         self.engines = {}
         self.engine = None            # the first engine owns the flat buffers
         self.optimizers = None
@@ -336,6 +377,38 @@ class Game(object):
             raise NotImplementedError("%s with a sender variant (sender_mix / ignore_code / ignore_receiver) is not available: "
                                       "plain autograd is" % ("channel_grad" if channel_grad else "input_grad"))
 
+    def _check_relax(self, autograd, channel_grad):
+        """What relaxed messages need of the game and of the call."""
+        if not (autograd and channel_grad):
+            raise ValueError("relaxed messages need autograd=True and channel_grad=True: their gradient crosses the channel "
+                             "inside the joint sender-receiver node")
+        if not self.cfg["use_binary"]:
+            raise ValueError("relaxed messages are for binary messages: continuous ones are the logits, already differentiable")
+        if self.world > 1:
+            raise NotImplementedError("relaxed messages with world > 1 are not available: autograd through exchange() runs on one GPU")
+        for name, on in (("message flips (flipout_sen / flipout_rec)", self.flipout),
+                         ("a sender variant (sender_mix / ignore_code / ignore_receiver)", self.sender_variant),
+                         ("description attention (Receiver(desc_attn=True))", self.attn_dim),
+                         ("visual attention (Sender(use_attn=True))", self.vattn)):
+            if on:
+                raise NotImplementedError("relaxed messages with %s are not available" % name)
+
+    def _refuse_relaxed_step(self, who):
+        if self.relax:
+            raise NotImplementedError("%s is the REINFORCE step: a game with relaxed messages trains through exchange() and "
+                                      "backward() (set_relaxation(None, None) clears the setting)" % who)
+
+    def set_relaxation(self, tau_sen=None, tau_rec=None, hard=False):
+        """The temperatures of the relaxed messages from now on -- what a training loop calls between minibatches to anneal them
+        -- for every engine of the game (Engine.set_message_relaxation: host only, no kernel is re-selected while the game
+        stays relaxed).  None, None: back to the unrelaxed channel."""
+        relax = None if tau_sen is None and tau_rec is None else relax_setting((tau_sen, tau_rec, hard))
+        if relax:
+            self._check_relax(self.autograd, self.channel_grad)
+        self.relax = relax
+        for eng in self.engines.values():
+            eng.set_message_relaxation(*(relax or (None, None)))
+
     def set_parallel(self, rank, world, group=None):
         """Data-parallel training (dist.DataParallel): train_step() then takes THIS rank's rows of the global minibatch --
         [rank * B / world, (rank + 1) * B / world) of the reference's batch (misc.py:257-302 order) -- and every rank ends
@@ -344,6 +417,8 @@ class Game(object):
             raise NotImplementedError("desc_attn with world > 1 is not available: an attention receiver trains on one GPU")
         if self.vattn and int(world) > 1:
             raise NotImplementedError("visual attention with world > 1 is not available: an attention sender runs on one GPU")
+        if self.relax and int(world) > 1:
+            raise NotImplementedError("relaxed messages with world > 1 are not available: autograd through exchange() runs on one GPU")
         self.rank, self.world, self.group = int(rank), int(world), group
 
     def check_map(self, data, n=1):
@@ -443,6 +518,8 @@ class Game(object):
                 eng.set_message_flipout(self.flipout[0], self.flipout[1], dev=self.flipout[2], eval_seed=self.seed)
             if self.sender_variant:
                 eng.set_sender_variant(*self.sender_variant)
+            if self.relax:
+                eng.set_message_relaxation(*self.relax)
             if self.engine is None:
                 self.engine = eng
                 self._adopt(eng)
@@ -483,9 +560,19 @@ class Game(object):
         from the joint node under channel_grad) in their own shape, dtype and device (include/mmg.h: mmg_vjp_input_grads), so
         that an encoder in front of ``data`` or an embedding table behind ``desc`` trains with the agents.  softmax(y) inside dbar
         stays a constant (model.py:441); baseline_sen reads h_x detached (model.py:835).  Without the option, or without autograd
-        being active, both stay constants and nothing changes."""
+        being active, both stay constants and nothing changes.
+
+        Relaxed messages (``Game(..., relax=dict(tau_sen=..., tau_rec=..., hard=...))``, ``set_relaxation()``, or
+        ``exchange_args["relax"]`` for this call; on top of autograd and channel_grad, binary messages): a training conversation
+        forms its messages as sigmoid((logit + logistic noise) / tau) from the uniforms the Bernoulli samples draw, and the joint
+        node's backward is the exact gradient of that forward (include/mmg.h: mmg_set_message_relaxation).  Same return structure:
+        the message lists hold the relaxed (soft) or rounded (hard) values, detached -- the gradient through them is inside the
+        node --, the probabilities, y and s_probs are the node's outputs; bs / br are plain tensors."""
         data, target, desc = exchange_args["data"], exchange_args.get("target"), exchange_args["desc"]
         train = exchange_args["train"]
+        relax = (relax_setting(exchange_args["relax"]) if "relax" in exchange_args else self.relax) if train else None
+        if relax:
+            self._check_relax(bool(exchange_args.get("autograd", self.autograd)), bool(exchange_args.get("channel_grad", self.channel_grad)))
         break_early = exchange_args.get("break_early", False)
         autograd = bool(exchange_args.get("autograd", self.autograd)) and bool(train) and torch.is_grad_enabled()
         inputs = (data, desc) if autograd and bool(exchange_args.get("input_grad", self.input_grad)) else (None, None)
@@ -530,8 +617,15 @@ class Game(object):
         # reference's numpy draws (model.py:227, 420, 460), for tests that replay one conversation on two paths
         u = exchange_args.get("uniforms") if train else None
         u = [None if v is None else torch.as_tensor(v).to(dev, torch.float32).contiguous() for v in (u or (None, None, None))]
-        eng.forward(data, target, desc, u[0], u[1], u[2], seed=self.seed, train=train, run_all=True,
-                    **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
+        held = getattr(eng, "relaxation", None)
+        if train and relax != held:                                     # (this call's own setting: restored behind the forward)
+            eng.set_message_relaxation(*(relax or (None, None)))
+        try:
+            eng.forward(data, target, desc, u[0], u[1], u[2], seed=self.seed, train=train, run_all=True,
+                        **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
+        finally:
+            if train and relax != held:
+                eng.set_message_relaxation(*(held or (None, None)))
         tp = eng.tape
         T = self.max_exchange
         n = T
@@ -551,7 +645,8 @@ class Game(object):
         self.modules["receiver"].h_z = tp["h"][n]
         self.modules["receiver"].h_w = tp["g"][n - 1]
         if autograd:
-            return self._exchange_graph(eng, data, desc, n, masks, bool(exchange_args.get("channel_grad", self.channel_grad)), inputs)
+            return self._exchange_graph(eng, data, desc, n, masks, bool(exchange_args.get("channel_grad", self.channel_grad)), inputs,
+                                        relax=relax)
         s = (masks, [tp["s"][t].clone() for t in range(n)], [tp["ps"][t].clone() for t in range(n)])
         sen_w = ([tp["z"][t].clone() for t in range(n)], [tp["pz"][t].clone() if binary else None for t in range(n)])
         rec_w = ([tp["w"][t].clone() for t in range(n)], [tp["pw"][t].clone() if binary else None for t in range(n)])
@@ -560,7 +655,7 @@ class Game(object):
         br = [tp["br"][t].clone() for t in range(n)] if train and binary else []
         return s, sen_w, rec_w, y, bs, br
 
-    def _exchange_graph(self, eng, data, desc, n, masks, channel=False, inputs=(None, None)):
+    def _exchange_graph(self, eng, data, desc, n, masks, channel=False, inputs=(None, None), relax=None):
         """exchange()'s return structure with the four agents' autograd nodes (training, run-all tape of this call).
         channel: the sender and the receiver share one node (_ChannelVJP).  inputs: the caller's (data, desc) tensors under
         input_grad -- tensor inputs of the sender's / the receiver's / the joint node."""
@@ -575,7 +670,7 @@ class Game(object):
 
         if channel:
             named = [(a, name, p) for a in ("sender", "receiver") for name, p in self.modules[a].named_parameters()]
-            spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=[(a, name) for a, name, _ in named],
+            spec = dict(eng=eng, gen=eng.generation, n=n, x=data, desc=desc, names=[(a, name) for a, name, _ in named], relax=relax,
                         outs=[tp["pz" if binary else "z"][:n], tp["y"][:n], tp["ps"][:n], tp["pw" if binary else "w"][:n]])
             sen_st, y_st, ps_st, w_st = _ChannelVJP.apply(spec, data_in, desc_in, *[p for _, _, p in named])
             sen = sen_st.unbind(0)
@@ -588,8 +683,11 @@ class Game(object):
         if binary:
             sen_w = ([tp["z"][t].clone() for t in range(n)], list(sen))
             rec_w = ([tp["w"][t].clone() for t in range(n)], list(rw))
-            bs = list(node(_BaselineSenVJP, "baseline_sen", [tp["bs"][:n]])[0].unbind(0))
-            br = list(node(_BaselineRecVJP, "baseline_rec", [tp["br"][:n]])[0].unbind(0))
+            if relax:                             # (the baselines are REINFORCE machinery: no VJP on a relaxed handle)
+                bs, br = [tp["bs"][t].clone() for t in range(n)], [tp["br"][t].clone() for t in range(n)]
+            else:
+                bs = list(node(_BaselineSenVJP, "baseline_sen", [tp["bs"][:n]])[0].unbind(0))
+                br = list(node(_BaselineRecVJP, "baseline_rec", [tp["br"][:n]])[0].unbind(0))
         else:
             sen_w = (list(sen), [None] * n)
             rec_w = (list(rw), [None] * n)
@@ -665,6 +763,7 @@ class Game(object):
         batch at every executed step, model.py:880-886) and every row of the sample dump.  Early exit == run-all and
         fused == phased are parity-tested (tests/test_hip_parity.py); the extra launches cost ~30 us once per log_interval."""
         B = data.size(0)
+        self._refuse_relaxed_step("train_step")
         if self.vattn:                                # data: the map [B, C, h, w], read in place; data_context: [B, G]
             eng = self._vattn_train_engine(data, desc, data_context)
             data = data.detach().to(eng.device, torch.float32).contiguous().view(B, data.size(1), -1)
@@ -696,6 +795,7 @@ class Game(object):
         """n consecutive plain minibatches (no log block) enqueued by ONE library call: data [n * B, F] / target [n * B] in batch
         order (misc.Epoch).  Same updates, same sampling streams as n train_step() calls (tests/test_cli_gpu.py)."""
         B = data.size(0) // n
+        self._refuse_relaxed_step("train_steps")
         if self.vattn:
             eng = self._vattn_train_engine(data, desc, data_context, n=n)
             data = data.detach().to(eng.device, torch.float32).contiguous().view(n * B, data.size(1), -1)
