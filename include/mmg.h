@@ -422,7 +422,10 @@ int mmg_train_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, in
  * called through the ADDRESS the caller registers (libmmg does not link RCCL) on the caller's communicator, in place, on
  * `stream`.  reduce == 0 skips both (a one-rank job).  full_tape != 0: every sample runs all steps (run_all_steps = 3: the
  * minibatches whose log block reads the whole tape; baseline scores on the live rows only), same update.  mmg_dp_train_steps: n minibatches laid out as for
- * mmg_train_steps (this rank's B rows of each). */
+ * mmg_train_steps (this rank's B rows of each).
+ * Continuous messages with Adaptive stopping: losses[6] (executed steps) and the running totals are formed from THIS rank's samples
+ * -- max_b t* + 1 steps, sum_b (t* + 1) sample-steps -- because only sums travel to the other ranks; on one GPU they are the
+ * reference's (model.py:866).  Continuous messages with Fixed exchange: max_exchange steps and max_exchange * global_batch sample-steps on every rank. */
 int mmg_dp_set_allreduce(mmg_handle* h, void* nccl_all_reduce, void* comm);
 int mmg_dp_train_step(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc,
                       const float* d_u_z, const float* d_u_s, const float* d_u_w, uint64_t seed,

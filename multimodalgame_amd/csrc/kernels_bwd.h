@@ -105,6 +105,16 @@ __device__ __forceinline__ void stats_pairs(const Dims& dm, const Params& P, con
             for (int b = lane; b < B; b += 64) a0 += which == 0 ? (double)ldf(&tp.logs[b]) : (double)(LLIN ? __hip_atomic_load(&tp.hit[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tp.hit[b]);
             a0 = dpp_wave_sum_d(a0);
             if (lane == 0) put_d(&tp.stats[stat_glob(T, which)], a0);
+            // continuous messages with Adaptive stopping: no (stream, step) pair is enabled, so the steps the reference executes
+            // before every sample has stopped (model.py:866) and the sample-steps come from t*: max_b t* + 1 and sum_b (t* + 1) of
+            // THIS rank's samples (the only instantiation continuous mode runs: k_stats and k_bwd_mc2's statistics workgroup)
+            if (!WT && !CC && !PLL && !LLIN && !dm.use_binary && !dm.fixed) {
+                double sum = 0.0;
+                float most = 0.f;
+                for (int b = lane; b < B; b += 64) { const int n = tp.tstar[b] + 1; sum += (double)n; most = fmaxf(most, (float)n); }
+                if (which == 0) { sum = dpp_wave_sum_d(sum); if (lane == 0) put_d(&tp.stats[stat_glob(T, 3)], sum); }
+                else { most = dpp_wave_max(most); if (lane == 0) put_d(&tp.stats[stat_glob(T, 2)], (double)most); }
+            }
             continue;
         }
         const int kind = p / T, t = p - kind * T;
@@ -230,7 +240,8 @@ __device__ __forceinline__ void loss_coefficients(const Dims& dm, const double* 
             for (int k = 0; k < 5; ++k) acc[k] += (t < 64) ? s_part[k][t] : 0.0;
             nsteps += (st[stat_stream(T, 2, t, 0)] > 0) ? 1 : 0;
         }
-        if (!dm.use_binary) nsteps = T;
+        // continuous messages: no stream counts; Fixed runs all T steps, Adaptive until every sample has stopped (stats_pairs)
+        if (!dm.use_binary) nsteps = dm.fixed ? T : (int)st[stat_glob(T, 2)];
         if (write_nll) losses_out[0] = (float)(-st[stat_glob(T, 0)] / (double)dm.Bg);   // NLL (model.py:1271); k_wgrad<OPT>: written by the norm role
         losses_out[1] = (float)acc[0];                                   // loss_binary_s
         losses_out[2] = (float)acc[1];                                   // loss_binary_rec
@@ -242,7 +253,7 @@ __device__ __forceinline__ void loss_coefficients(const Dims& dm, const double* 
         if (totals) {
             double live = 0.0;                                           // sum_t |{b: step t is live}| = sample-steps
             for (int t = 0; t < T; ++t) live += st[stat_stream(T, 2, t, 0)];
-            if (!dm.use_binary) live = (double)T * (double)dm.Bg;
+            if (!dm.use_binary) live = dm.fixed ? (double)T * (double)dm.Bg : st[stat_glob(T, 3)];
             totals[0] += (double)nsteps; totals[1] += st[stat_glob(T, 1)]; totals[2] += 1.0; totals[3] += live;
         }
     }

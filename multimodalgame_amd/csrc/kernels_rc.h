@@ -592,7 +592,8 @@ __device__ __forceinline__ void rc_tail_body(const Dims& dm, const Tape& tp, con
         const int b = b0 + m;
         const float v = (lane < D) ? rc_ld<PS>(&tp.outp[(size_t)b * D + lane]) : -3.0e38f;
         const float mx = dpp_wave_max(v);
-        const float se = dpp_wave_sum((lane < D) ? __expf(v - mx) : 0.f);
+        const float ev = (lane < D) ? __expf(v - mx) : 0.f;
+        const float se = dpp_wave_sum(ev);
         const float lse = mx + flog(se);
         const int tgt = ar.target ? (int)ar.target[b] : -1;
         const float dt = (tgt >= 0) ? (rc_ld<PS>(&tp.outp[(size_t)b * D + max(tgt, 0)]) - lse) : 0.f;
@@ -600,7 +601,10 @@ __device__ __forceinline__ void rc_tail_body(const Dims& dm, const Tape& tp, con
         float above = 0.f;
         if (lane < D) {
             tp.dist[(size_t)b * D + lane] = ld;
-            tp.sm[(size_t)b * D + lane] = __expf(ld);
+            // the probabilities the backward pass reads: normalised by their OWN sum, so that a row sums to 1 to fp32 rounding.  The
+            // gradient of a y-head unit that is on for every class of every sample is w2 sum_b sum_d (sm - onehot) = 0 exactly;
+            // exp(v - lse) carries the fast logarithm's error into every row sum (~1e-6), which RMSprop turns into O(lr) steps
+            tp.sm[(size_t)b * D + lane] = ev / se;
             if (tgt >= 0 && ld > dt) above = 1.f;
         }
         above = dpp_wave_sum(above);

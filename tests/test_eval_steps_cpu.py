@@ -23,7 +23,9 @@ C1 = dict(use_binary=True, fixed_exchange=False, max_exchange=10, batch_size=64,
 # The shapes of tests/test_eval_steps_gpu.py that no fixture covers: flags, classes, batch, top_k, receiver s.bias (None: the
 # filled one), seeds.  Smallest shapes at which k_eval_reduce can still go wrong: a ragged batch below one wave's worth of
 # sample workgroups, everyone stopping at step 1 (n = 1), nobody stopping (n = T, tsel = T - 1), T = 1, Fixed mode, top_k >= D,
-# more classes than a wave has lanes (130, and 1000 on k_conversation_mc), continuous messages, config 1's shape at B = 64.
+# more classes than a wave has lanes (130, and 1000 on k_conversation_mc), continuous messages, config 1's shape at B = 64, and
+# continuous messages with Adaptive stopping on the register-resident kernels (c1_cont_B64) and on k_conversation_mc3 with
+# train = False (D130_cont_B17): s.bias 1.2 spreads their output steps over 7 and 4 values.
 # (The stop bit s = 1 KEEPS a sample talking -- the mask is the running minimum of s, model.py:852 -- so the strongly negative
 # s.bias is the one that ends every conversation at step 1 and the strongly positive one never stops.)
 CASES = {
@@ -37,6 +39,8 @@ CASES = {
     "c1_B64": dict(flags=C1, n_classes=30, batch=64, top_k=6, s_bias=1.2, seed_weights=5, seed_data=6),
     "D130_B17": dict(flags=C1, n_classes=130, batch=17, top_k=6, s_bias=1.2, seed_weights=5, seed_data=6),
     "D1000_B16": dict(flags=C1, n_classes=1000, batch=16, top_k=6, s_bias=1.2, seed_weights=5, seed_data=6),
+    "c1_cont_B64": dict(flags=dict(C1, use_binary=False), n_classes=30, batch=64, top_k=6, s_bias=1.2, seed_weights=5, seed_data=6),
+    "D130_cont_B17": dict(flags=dict(C1, use_binary=False), n_classes=130, batch=17, top_k=6, s_bias=1.2, seed_weights=5, seed_data=6),
 }
 MIN_GAP = 1e-4
 
@@ -204,3 +208,6 @@ def test_gpu_cases_have_clear_gaps(name):
         assert 1 < r["n"] <= T and len(set(r["tsel"].tolist())) > 1, "the ragged case should select different output steps"
     if name == "tiny_topk_ge_D":
         assert r["hits"] == c["batch"]
+    if name in ("c1_cont_B64", "D130_cont_B17"):
+        assert not meta["use_binary"] and not meta["fixed_exchange"]
+        assert 2 < r["n"] <= T and len(set(r["tsel"].tolist())) >= 3, "continuous + Adaptive: the output steps should spread over three values and more"
