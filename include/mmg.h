@@ -256,6 +256,40 @@ int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_r
  * handle with message flips or a sender variant (their setters refuse a relaxed handle likewise); an attention handle. */
 int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float tau_rec, int hard);
 
+/* Training controls of a live handle: which agents the REINFORCE step updates, and the values of the learning rate and of the entropy
+ * weights (model.py:1307-1330 with optimizer.step() of a frozen agent not called; the reference has no such switches).  The calls
+ * enqueue nothing and synchronise nothing, and the kernel family of the handle stays.  mmg_set_learning_rate and mmg_set_entropy change
+ * host state alone.  mmg_set_trainable also re-plans k_wgrad for the new set of frozen agents (below): its job table, row splits, its
+ * walk over the tiles, and whether the clip + optimizer step fits inside its launch (k_wgrad<true>) or runs as k_opt behind it -- the first
+ * call for a set allocates pinned host memory for its table.  Each call takes effect at the next minibatch that is enqueued -- of
+ * mmg_train_step[s], mmg_dp_train_step[s] and of the phased mmg_backward / mmg_clip_step, on plain, attention and visual-attention
+ * handles alike -- and may come between the minibatches of a run.
+ *   mmg_set_trainable: bit MMG_AGENT_* of mask set = that agent is updated; the default is all four.  Bits of agents the mode never
+ *     trains (continuous messages: the sender and both baselines) are accepted and ignored; a mask without any trained agent is allowed
+ *     (the step changes no parameter); bits outside the four are an error.  A frozen agent:
+ *       - its parameters and its optimizer state (square_avg | exp_avg, exp_avg_sq) stay bit-identical, and the update neither reads nor
+ *         writes them;
+ *       - its slice of d_grads holds ZEROS behind mmg_backward and behind every training step (mmg_dp_train_step all-reduces the
+ *         whole buffer): its weight-gradient jobs are not in the table k_wgrad runs -- one table per set of frozen agents, built at
+ *         this call, kept, and uploaded on the stream of the next minibatch --, the launches that only feed them are not made, and
+ *         the slice is cleared once;
+ *       - the forward pass, the losses, the statistics, the logged values and the other agents' gradients and updates are what they
+ *         are without the mask: a frozen baseline still scores, a frozen sender still speaks; the minibatch counter and the Philox
+ *         stream advance as ever;
+ *       - Adam's bias correction counts an agent's OWN updates, as four torch.optim.Adam objects would: tape "counter"[4 + a] holds the
+ *         committed steps agent a sat out frozen, its step count is counter[1] - counter[4 + a].  With nothing ever frozen the four
+ *         words stay zero and every count is the global one.
+ *   mmg_set_learning_rate: finite lr >= 0, an error otherwise.
+ *   mmg_set_entropy: new values for the weights the handle was created with (has_entropy_*).  A weight that was absent at mmg_create
+ *     stays absent and its argument is ignored (the has_* flags never change); a non-finite value is an error.
+ *   mmg_get_training_controls: the mask as set, the current learning rate and entropy3 = {entropy_s, entropy_sen, entropy_rec}; each
+ *     pointer may be NULL.
+ * Each returns 0, or negative (the settings before stay). */
+int mmg_set_trainable(mmg_handle* h, int mask);
+int mmg_set_learning_rate(mmg_handle* h, float lr);
+int mmg_set_entropy(mmg_handle* h, float entropy_s, float entropy_sen, float entropy_rec);
+int mmg_get_training_controls(const mmg_handle* h, int* mask, float* lr, float* entropy3);
+
 /* Description attention, the reference's -desc_attn (model.py:267-271, 344-410, 444-445): the receiver's class description is no
  * fixed bag-of-words mean but, per sample and step, an attention over the WORDS of each description with the GRU state as the query.
  * With set [n_words, V] = the word vectors of all classes concatenated (a word without a vector is a row of zeros and is still
@@ -456,7 +490,7 @@ int mmg_degraded(const mmg_handle* h);
  *                  then one line with the caps it probed, in MMG_CAP_* order.
  *   mmg_plan_for:  the same text for a config and caller-supplied caps (n_caps == MMG_PLAN_CAPS), under the environment of the
  *                  call: no handle, no buffers, no GPU.  flags: bit 0 = no in-launch waits (what MMG_NO_ROLES=1 or a recovery
- *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set, bit 3 = messages are relaxed.  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
+ *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set, bit 3 = messages are relaxed, bits 4-7 = bit 4 + MMG_AGENT_* set: that agent is frozen (mmg_set_trainable; its jobs leave k_wgrad's table: "gemm tiles", "blocks").  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
  * Both return 0, or negative (out too small: about 2 KB are needed; a config the library refuses). */
 enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP_RC_PERSIST, MMG_CAP_MC, MMG_CAP_MC3, MMG_CAP_MC3P,
        MMG_CAP_GAME, MMG_CAP_WGRAD_OPT, MMG_CAP_WGRAD, MMG_PLAN_CAPS };

@@ -53,7 +53,8 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_plan_text", "mmg_plan_for", "mmg_set_sender_variant", "mmg_attn_param_count", "mmg_attn_grad_floats",
            "mmg_attn_param_table", "mmg_attn_workspace_bytes", "mmg_attn_tape_table", "mmg_attn_create", "mmg_set_desc_set",
            "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
-           "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation"]
+           "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation",
+           "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
@@ -64,6 +65,7 @@ VATTN_MAX_CHANNELS = 4096      # feat_dim of the map
 # the caps of mmg_plan_for / the last line of mmg_plan_text (include/mmg.h: MMG_CAP_*): the CU count, then one occupancy per role kernel
 PLAN_CAPS = ("n_cu", "split", "persist", "rc_bwd", "rc_persist", "mc", "mc3", "mc3p", "game", "wgrad_opt", "wgrad")
 PLAN_NO_ROLES, PLAN_FLIPS, PLAN_VARIANT, PLAN_RELAX = 1, 2, 4, 8        # flags of mmg_plan_for
+PLAN_FROZEN_SHIFT = 4                   # ... and agent_mask(frozen agents) << PLAN_FROZEN_SHIFT: the plan with those agents frozen
 MIX = {"sum": 0, "prod": 1}             # mmg_set_sender_variant's mix (include/mmg.h: MMG_MIX_SUM, MMG_MIX_PROD)
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
@@ -118,6 +120,11 @@ def load():
     lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
     lib.mmg_set_sender_variant.restype = i32; lib.mmg_set_sender_variant.argtypes = [vp, i32, i32, i32]
     lib.mmg_set_message_relaxation.restype = i32; lib.mmg_set_message_relaxation.argtypes = [vp, C.c_float, C.c_float, i32]
+    lib.mmg_set_trainable.restype = i32; lib.mmg_set_trainable.argtypes = [vp, i32]
+    lib.mmg_set_learning_rate.restype = i32; lib.mmg_set_learning_rate.argtypes = [vp, C.c_float]
+    lib.mmg_set_entropy.restype = i32; lib.mmg_set_entropy.argtypes = [vp, C.c_float, C.c_float, C.c_float]
+    lib.mmg_get_training_controls.restype = i32
+    lib.mmg_get_training_controls.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mmg_exchange_vjp.restype = i32; lib.mmg_exchange_vjp.argtypes = [vp, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_exchange_vjp_channel.restype = i32; lib.mmg_exchange_vjp_channel.argtypes = [vp, i32, fp, fp, fp, fp, fp, fp, vp]
     lib.mmg_vjp_input_grads.restype = i32; lib.mmg_vjp_input_grads.argtypes = [vp, i32, i32, fp, fp, fp, vp]
@@ -210,6 +217,16 @@ def tape_table(cfg, attn_dim=0, n_words=0, vattn=None):
     check(0 if fn(C.byref(cfg), *dims, arr, n) == n else -1)
     return [dict(name=e.name.decode(), dtype=e.dtype, dims=[int(e.dims[i]) for i in range(e.ndim)], offset=e.offset)
             for e in arr]
+
+
+def agent_mask(agents):
+    """MMG_AGENT_* bits of a collection of agent names (mmg_set_trainable's mask); raises ValueError for a name that is no agent."""
+    mask = 0
+    for a in agents:
+        if a not in AGENTS:
+            raise ValueError("%r is no agent: one of %s" % (a, ", ".join(AGENTS)))
+        mask |= 1 << AGENTS.index(a)
+    return mask
 
 
 def plan_for(cfg, caps, flags=0):

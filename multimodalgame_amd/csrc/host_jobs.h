@@ -13,18 +13,34 @@ struct JobBuilder {
     bool small_split, bias_as_gemm;
     const float* ones;
     int tiles = 0, ng = 0, cblocks = 0, nc = 0;
+    // frozen agents (mmg_set_trainable): a job whose destination lies in a frozen agent's slice of the gradient buffer is not entered --
+    // the caller still gets a record to fill in (off_g / off_c), which no table holds
+    int frozen = 0;
+    const float* grads = nullptr;
+    const int64_t* agent_begin = nullptr;
+    GemmJob off_g;
+    ColJob off_c;
     JobBuilder(JobTable& jt_, int split_rows_, long long ptotal_, bool small_split_, bool bias_as_gemm_, const float* ones_)
         : jt(jt_), split_rows(split_rows_), ptotal(ptotal_), small_split(small_split_), bias_as_gemm(bias_as_gemm_), ones(ones_) {
         memset(&jt, 0, sizeof(jt));
     }
+    void freeze(int frozen_, const float* grads_, const int64_t* agent_begin_) { frozen = frozen_; grads = grads_; agent_begin = agent_begin_; }
+    bool off(const float* dst) const {
+        if (!frozen) return false;
+        const int64_t at = dst - grads;
+        int a = 0;
+        for (int k = 1; k < 4; ++k) if (at >= agent_begin[k]) a = k;
+        return (frozen >> a) & 1;
+    }
     GemmJob& gemm(const float* A, int lda, const float* Bm, int ldb, int bmod, int bsrc, float* C, int ldc, int rows, int N, int Kk) {
-        GemmJob& g = jt.g[ng++];
+        const bool skip = off(C);
+        GemmJob& g = skip ? off_g : jt.g[ng++];
         g.A = A; g.Bm = Bm; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.rows = rows; g.N = N; g.K = Kk;
         g.bmod = bmod; g.bsrc = bsrc; g.tile_begin = tiles; g.tiles_k = (Kk + 31) / 32;     // 16 x 32 outputs per block
         g.vhid = nullptr; g.vw2 = nullptr; g.compact = (rows == split_rows) ? 1 : 0;
         g.nsplit = (rows != split_rows) ? 1 : small_split ? wgrad_job_nsplit(rows, ptotal, ((N + 15) / 16) * ((Kk + 31) / 32))
                                                           : wgrad_nsplit(rows, ptotal);
-        tiles += ((N + 15) / 16) * g.tiles_k * g.nsplit;
+        if (!skip) tiles += ((N + 15) / 16) * g.tiles_k * g.nsplit;
         return g;
     }
     // a job whose rows are NOT (step, sample) rows whatever their count (the words of a description set): never compact, never split
@@ -42,10 +58,11 @@ struct JobBuilder {
         g.vhid = hid; g.vw2 = w2;
     }
     ColJob& col(const float* src, int ld, int rows, int cols, float* dst, const float* scale) {
-        ColJob& c = jt.c[nc++];
+        const bool skip = off(dst);
+        ColJob& c = skip ? off_c : jt.c[nc++];
         c.src = src; c.dst = dst; c.scale = scale; c.ld = ld; c.rows = rows; c.cols = cols; c.blk_begin = cblocks;
         c.vbeta = nullptr; c.vw2 = nullptr; c.wrow = nullptr; c.compact = (rows == split_rows) ? 1 : 0; c.special = 0;
-        cblocks += (cols + 15) / 16;
+        if (!skip) cblocks += (cols + 15) / 16;
         return c;
     }
     // bias gradient = column sums of a (step, sample)-row tape.  With thousands of rows the 16-column blocks of a column job
@@ -85,6 +102,7 @@ static int build_jobs(mmg_handle* h, CodeBiasJob code_bias, bool small_split) {
     const int B = d.B, T = d.T, H = d.H, W = d.W, R = d.R, V = d.V, K = d.K, D = d.D, F = d.F;
     const int TB = T * B;
     JobBuilder jb(jt, TB, h->pl.total, small_split, wgrad_nsplit(TB, h->pl.total) > 1 || (small_split && TB > 2048), tp.ones);
+    jb.freeze(frozen_agents(h), h->grads, h->pl.agent_begin);
     const Params& P = h->P;
     const bool bin = d.use_binary;
     // ---- receiver ----

@@ -134,6 +134,10 @@ struct ForwardState {
     bool basehx_ready = false;      // this forward pass formed tape.basehx inside the conversation launch
 };
 
+// What mmg_set_trainable decided for one set of frozen agents: the selection (k_wgrad's plan follows the job table) and the job table in
+// pinned host memory, uploaded on the stream of the next minibatch.  valid: built since the last full selection (select_paths)
+struct MaskPlan { bool valid = false; Selection sel; JobTable* pinned = nullptr; };
+
 struct mmg_handle {
     mmg_config cfg = {};
     Dims dm = {};
@@ -177,6 +181,17 @@ struct mmg_handle {
     // state; the forward entries copy it into ConvArgs, mmg_exchange_vjp_channel into VjpIn
     float relax_tau_sen = 0.f, relax_tau_rec = 0.f;
     bool relax_hard = false;
+    // mmg_set_trainable: MMG_AGENT_* bits of the agents the training entries update (the others are frozen).  Host state; the optimizer
+    // launches get it as OptArgs::trainable (mmg.hip: opt_trainable).  The learning rate and the entropy weights of mmg_set_learning_rate /
+    // mmg_set_entropy live where mmg_create put them: cfg.learning_rate, cfg.entropy_* and their copies in dm
+    int train_mask = 15;
+    // ... and its job tables: k_wgrad's table holds the jobs of the agents in training only (host_jobs.h), one per set of frozen agents,
+    // built at mmg_set_trainable and kept.  jt_src != NULL: the table in use is not on the device yet (apply_pending uploads it on the
+    // stream of the next minibatch); zero_pending: agents whose gradient slice has to be cleared once -- nothing writes it while they are frozen
+    MaskPlan mask_plans[16];
+    std::vector<JobTable*> retired_tables;   // pinned tables a later selection replaced: never rewritten (an upload may still read them), freed with the handle
+    const JobTable* jt_src = nullptr;
+    int zero_pending = 0;
     // mmg_attn_create: desc_attn_dim (0: a plain handle) and the words of the description set; `at` is what the ATTN instantiations get
     // on top of the plain kernels' arguments (the six tensors inside the flat buffer, the attention arrays behind the plain tape), AG
     // the six gradient tensors; set_ready: mmg_set_desc_set has uploaded a set
@@ -197,8 +212,30 @@ struct mmg_handle {
     ~mmg_handle() {
         for (auto& t : timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }
         if (h_err) hipHostFree(h_err);
+        for (auto& mp : mask_plans) if (mp.pinned) hipHostFree(mp.pinned);
+        for (JobTable* t : retired_tables) hipHostFree(t);
     }
 };
+
+// mmg_set_trainable on the device side.  OptArgs::trainable: bits 0-3 = the agents this step updates -- the caller's mask inside what the
+// mode trains (continuous messages: the receiver alone, model.py:1313) --, bits 4-7 = the agents the mode trains and the caller froze.
+static int opt_trainable(const mmg_handle* h) {
+    const int mode = h->cfg.use_binary ? 15 : 1;
+    return (mode & h->train_mask) | ((mode & ~h->train_mask) << 4);
+}
+static int frozen_agents(const mmg_handle* h) { return opt_trainable(h) >> 4; }
+// The table in use into pinned memory of its own, kept with the selection it belongs to.  A buffer that held another table is retired, not
+// rewritten: an upload enqueued from it may not have run yet.
+static int keep_mask_plan(mmg_handle* h) {
+    MaskPlan& mp = h->mask_plans[frozen_agents(h)];
+    if (mp.pinned) h->retired_tables.push_back(mp.pinned);
+    mp.pinned = nullptr; mp.valid = false;
+    if (hipHostMalloc(reinterpret_cast<void**>(&mp.pinned), sizeof(JobTable), hipHostMallocDefault) != hipSuccess) { mp.pinned = nullptr; return fail("no pinned host memory for a job table"); }
+    memcpy(mp.pinned, &h->jt, sizeof(JobTable));
+    mp.sel = h->sel; mp.valid = true;
+    return 0;
+}
+static bool is_frozen(const mmg_handle* h, int agent) { return (frozen_agents(h) >> agent) & 1; }
 
 // ---------------------------------------------------------------------------------------------
 // launch helper with optional HIP-event timing on the launch stream
@@ -265,6 +302,7 @@ static int launch_wgrad(mmg_handle* h, hipStream_t st, const JobTable* djt, cons
 // its tiles and column blocks only (no spare block: the logged losses, running totals and gradient tail stay untouched), no
 // live-row list.  Writes only the agent's slice of the gradient buffer.
 static int launch_vjp_wgrad(mmg_handle* h, hipStream_t st, int slot, const float* d_x, const float* d_desc) {
+    h->zero_pending |= frozen_agents(h);                 // (a VJP writes its agent's slice whatever the mask: cleared before the next training step)
     const JobTable* djt = reinterpret_cast<const JobTable*>(h->tp.vtables + (size_t)slot * MMG_VJP_TABLE_BYTES);
     return launch_wgrad(h, st, djt, h->vjp_hd[slot], d_x, d_desc, false, 0, false, nullptr);
 }

@@ -495,7 +495,7 @@ static int decide(mmg_handle* h, const Switches& w) {
         // (measured, round 5: 1 336 tiles on 856 slots 289 -> 281 us per minibatch, 3 848 on 672 219 -> 217; 5 120 on 552 388 -> 396 --
         //  beyond ~6 tiles per workgroup the static split loses more to its ragged last round than the walk saves;
         //  a balanced stride (tiles / rounds) gave the gain away again: as many workgroups as are resident)
-        if (h->jt.gemm_tiles > slots && slots >= 64 && h->jt.gemm_tiles <= 6 * slots) s.wgrad_stride = slots;
+        s.wgrad_stride = (h->jt.gemm_tiles > slots && slots >= 64 && h->jt.gemm_tiles <= 6 * slots) ? slots : 0;
     }
     plan_launches(h);
     if (no_roles) {
@@ -517,6 +517,23 @@ static int shape_pass(mmg_handle* h, const Switches& w) {
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();
     if (shape_pass(h, w) || probe_device(h->cfg, h->dm, h->sel)) return -1;
+    // (the tables mmg_set_trainable kept belong to the selection before; the callers upload h->jt themselves, after draining the device)
+    for (auto& mp : h->mask_plans) mp.valid = false;
+    if (decide(h, w)) return -1;
+    if (h->jt_src) {                                      // a table that still waits for its upload: the one just decided takes its place
+        if (keep_mask_plan(h)) return -1;
+        h->jt_src = h->mask_plans[frozen_agents(h)].pinned;
+    }
+    return 0;
+}
+// The selection again for another set of frozen agents (mmg_set_trainable), from the caps the device gave at the last select_paths: exactly
+// what mmg_plan_for does -- shape_pass starts from an empty Selection, so nothing of the plan before survives --, and no HIP call.
+static int reselect_from_caps(mmg_handle* h) {
+    const Switches w = read_switches();
+    int32_t caps[MMG_PLAN_CAPS];
+    memcpy(caps, h->sel.caps, sizeof(caps));
+    if (shape_pass(h, w)) return -1;
+    memcpy(h->sel.caps, caps, sizeof(caps));
     return decide(h, w);
 }
 

@@ -570,8 +570,11 @@ __device__ __forceinline__ float4 load4_guard(const float* __restrict__ base_, s
 // of config 4 8 us, 35 -> 43: reverted.)
 struct WgHead { int gemm_tiles, n_wblocks, special_block, special_job; };
 
+// trainable: bits 0-3 = MMG_AGENT_* whose elements this step updates (continuous messages: the receiver at most, model.py:1313);
+// bits 4-7 = agents the CALLER froze (mmg_set_trainable) among those the mode trains: a committed step adds one to their
+// counter[4 + a], the steps they sat out -- an agent's own step count, Adam's bias correction, is counter[1] - counter[4 + a]
 struct OptArgs {
-    int optim_type, only_receiver, from_wgrad, bump_step, bump_mb;
+    int optim_type, trainable, from_wgrad, bump_step, bump_mb;
     float lr;
     int64_t agent_begin[5];
     int64_t total;
@@ -593,8 +596,9 @@ struct WgOpt {
 };
 #define MMG_COEF_REPL 64
 // one gradient element's update (k_opt's arithmetic); w, s1, s2 were requested before the wait for the coefficient
+// bc1, bc2s: Adam's bias corrections of the element's agent (opt_wait_bc), unused otherwise
 __device__ __forceinline__ void opt_update_one(const OptArgs& oa, float* params, float* state, int64_t idx, float g, float coef,
-                                               float w, float s1, float s2, uint32_t step) {
+                                               float w, float s1, float s2, float bc1, float bc2s) {
     const float gv = g * coef;
     if (oa.optim_type == MMG_OPT_RMSPROP) {
         const float sv = 0.99f * s1 + (1.f - 0.99f) * gv * gv;
@@ -602,7 +606,6 @@ __device__ __forceinline__ void opt_update_one(const OptArgs& oa, float* params,
         state[idx] = sv;
     } else if (oa.optim_type == MMG_OPT_ADAM) {
         const float b1 = 0.9f, b2 = 0.999f;
-        const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
         const float mv = s1 + (gv - s1) * (1.f - b1), vv = b2 * s2 + (1.f - b2) * gv * gv;
         w -= (oa.lr / bc1) * mv / (sqrtf(vv) / bc2s + 1e-8f);
         state[idx] = mv; state[oa.total + idx] = vv;
@@ -612,6 +615,25 @@ __device__ __forceinline__ void opt_update_one(const OptArgs& oa, float* params,
     params[idx] = w;
 }
 // the wave's clip coefficient of `agent`: spins on this block's replica of the norm role's pairs; < 0: the update is skipped
+__device__ __forceinline__ bool opt_trains(const OptArgs& oa, int agent) { return (oa.trainable >> agent) & 1; }
+// Adam's bias corrections of `agent`, 1 - 0.9^n and sqrt(1 - 0.999^n) with n the agent's OWN step count: its norm role forms them once
+// (the blocks formed them per element from the one global count) and publishes them as pairs, replicated like the coefficient, ahead of
+// it -- behind a fresh coefficient they have landed, or land within the trip.  false: the wait expired, the update is skipped
+#define MMG_COEF_BC (4 * MMG_COEF_REPL + 4)
+__device__ __forceinline__ bool opt_wait_bc(const WgOpt& wo, int agent, uint32_t epoch, const uint32_t* sync, float& bc1, float& bc2s) {
+    bc1 = 1.f; bc2s = 1.f;
+    if (wo.oa.optim_type != MMG_OPT_ADAM) return true;
+    const size_t at = MMG_COEF_BC + (size_t)(2 * agent) * MMG_COEF_REPL + (blockIdx.x & (MMG_COEF_REPL - 1));
+    unsigned long long u1, u2;
+    for (int spins = 0;; ) {
+        u1 = ld_ll(wo.coefll, at); u2 = ld_ll(wo.coefll, at + MMG_COEF_REPL);
+        if (ll_fresh(u1, epoch) && ll_fresh(u2, epoch)) break;
+        __builtin_amdgcn_s_sleep(2);
+        if (++spins > (1 << 20)) { __hip_atomic_store(const_cast<uint32_t*>(sync) + MMG_SYNC_ERR, 10u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+    }
+    bc1 = ll_value(u1); bc2s = ll_value(u2);
+    return true;
+}
 __device__ __forceinline__ float opt_wait_coef(const WgOpt& wo, int agent, uint32_t epoch, const uint32_t* sync) {
     unsigned long long u;
     for (int spins = 0;; ) {
@@ -681,6 +703,13 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
         // an in-launch dependency wait of this minibatch timed out (sync[MMG_SYNC_ERR]): parameters and optimizer state stay
         // untouched (coefficient -1) -- exactly k_opt's contract; the closing role posts the word to the host
         const uint32_t err = __hip_atomic_load(sync + MMG_SYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // Adam's bias corrections count the agent's OWN updates, as four torch.optim.Adam objects would: the steps it sat out frozen
+        // (counter[4 + agent]) do not count.  A frozen agent's role publishes none: nobody reads them, and its word is the closing role's
+        if (wo.oa.optim_type == MMG_OPT_ADAM && opt_trains(wo.oa, agent) && threadIdx.x < MMG_COEF_REPL) {
+            const float astep = (float)(ostep - wo.counter[4 + agent]);
+            st_ll(wo.coefll, MMG_COEF_BC + (size_t)(2 * agent) * MMG_COEF_REPL + threadIdx.x, 1.f - powf(0.9f, astep), oepoch);
+            st_ll(wo.coefll, MMG_COEF_BC + (size_t)(2 * agent + 1) * MMG_COEF_REPL + threadIdx.x, sqrtf(1.f - powf(0.999f, astep)), oepoch);
+        }
         if (threadIdx.x < MMG_COEF_REPL + 1) {
             const float tot = (s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]);
             const float coef = 1.0f / (sqrtf(tot) + 1e-6f);               // max_norm = 1 (model.py:1310)
@@ -766,14 +795,17 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
 #ifdef MMG_TIMING
             if (threadIdx.x == 0 && bid < 2000) dbg2[8192 + 4 * bid + 2] = (long long)wall_clock64();
 #endif
-            const float coef = opt_wait_coef(wo, jt->wblock_agent[bid], oepoch, sync);
+            // (the table holds the jobs of the agents in training alone, host_jobs.h: every block of this launch updates)
+            const int ag = jt->wblock_agent[bid];
+            float coef = opt_wait_coef(wo, ag, oepoch, sync), bc1, bc2s;
+            if (coef >= 0.f && !opt_wait_bc(wo, ag, oepoch, sync, bc1, bc2s)) coef = -1.f;
             // (one workgroup, <= 32 elements: read back what it stored -- same thread, same address)
             for (int j0 = 0; j0 < Wc && coef >= 0.f; j0 += MMG_BLOCK / 8) {
                 const int j = j0 + jj;
                 if (j < Wc && p8 == 0) {
                     const int64_t idx = (C.dst - wo.grads) + j;
                     opt_update_one(wo.oa, wo.params, wo.state, idx, C.dst[j], coef, wo.params[idx], wo.state[idx],
-                                   wo.oa.optim_type == MMG_OPT_ADAM ? wo.state[wo.oa.total + idx] : 0.f, ostep);
+                                   wo.oa.optim_type == MMG_OPT_ADAM ? wo.state[wo.oa.total + idx] : 0.f, bc1, bc2s);
                 }
             }
         }
@@ -826,7 +858,12 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
                 losses[0] = bad ? __builtin_nanf("") : (float)(-stats[stat_glob(dm.T, 0)] / (double)dm.Bg);     // NLL (model.py:1271)
                 const uint32_t err = __hip_atomic_load(sync + MMG_SYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (wo.err_host && (err != 0u || *wo.err_host == 0u)) *wo.err_host = err;
-                if (err == 0u) wo.counter[2] = ostep;                           // committed to counter[1] by the next k_prep
+                if (err == 0u) {
+                    wo.counter[2] = ostep;                                      // committed to counter[1] by the next k_prep
+                    // (only the norm role of an agent in training reads its word, and the closing role moves the frozen agents' alone)
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) if ((wo.oa.trainable >> (4 + a)) & 1) wo.counter[4 + a] += 1u;
+                }
                 if (wo.oa.bump_mb) { wo.counter[0] += 1u; wo.counter[3] += 1u; }
             }
         }
@@ -1151,6 +1188,7 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
         }
         if (OPT) {
             if (threadIdx.x == 0) st_ll(wo.gnll, tile, sq, oepoch);
+            const int tile_agent = jt->wblock_agent[tile];
             // parameter / state elements of this thread: requested now, they arrive while the norm role adds up
             float w[2], s1[2], s2[2];
 #pragma unroll
@@ -1162,14 +1200,15 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
 #ifdef MMG_TIMING
             if (threadIdx.x == 0 && tile < 2000) dbg2[8192 + 4 * tile + 2] = (long long)wall_clock64();
 #endif
-            const float coef = opt_wait_coef(wo, jt->wblock_agent[tile], oepoch, sync);
+            float coef = opt_wait_coef(wo, tile_agent, oepoch, sync), bc1, bc2s;
+            if (coef >= 0.f && !opt_wait_bc(wo, tile_agent, oepoch, sync, bc1, bc2s)) coef = -1.f;
 #ifdef MMG_TIMING
             if (threadIdx.x == 0 && tile < 2000) dbg2[8192 + 4 * tile + 3] = (long long)wall_clock64();
 #endif
             if (coef >= 0.f) {
 #pragma unroll
                 for (int h2 = 0; h2 < 2; ++h2)
-                    if (gi2[h2] >= 0) opt_update_one(wo.oa, wo.params, wo.state, gi2[h2], gv2[h2], coef, w[h2], s1[h2], s2[h2], ostep);
+                    if (gi2[h2] >= 0) opt_update_one(wo.oa, wo.params, wo.state, gi2[h2], gv2[h2], coef, w[h2], s1[h2], s2[h2], bc1, bc2s);
             }
         }
         // (the prefetches beyond a tile's last chunk are never consumed: across the back edge their registers count as outstanding
@@ -1288,11 +1327,13 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
     if (threadIdx.x == 0) part[bid] = sq;
     if (OPT) {
         if (threadIdx.x == 0) st_ll(wo.gnll, bid, sq, oepoch);
+        const int ag = jt->wblock_agent[bid];
         const bool mine = threadIdx.x < 16 && (c0 + (int)threadIdx.x) < C.cols;
         const int64_t idx = mine ? (C.dst - wo.grads) + c0 + threadIdx.x : 0;
         const float w = wo.params[idx], s1 = wo.state[idx], s2 = (wo.oa.optim_type == MMG_OPT_ADAM) ? wo.state[wo.oa.total + idx] : 0.f;
-        const float coef = opt_wait_coef(wo, jt->wblock_agent[bid], oepoch, sync);
-        if (coef >= 0.f && mine) opt_update_one(wo.oa, wo.params, wo.state, idx, v, coef, w, s1, s2, ostep);
+        float coef = opt_wait_coef(wo, ag, oepoch, sync), bc1, bc2s;
+        if (coef >= 0.f && !opt_wait_bc(wo, ag, oepoch, sync, bc1, bc2s)) coef = -1.f;
+        if (coef >= 0.f && mine) opt_update_one(wo.oa, wo.params, wo.state, idx, v, coef, w, s1, s2, bc1, bc2s);
     }
     MMG_WG_END();
 }
@@ -1346,19 +1387,35 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_opt(const JobTable* __restrict__ 
     // without any stream operation or synchronisation; it is sticky, every later training call fails (mmg.hip: sticky_error)
     if (err_host && blockIdx.x == 0 && threadIdx.x == 0 && (err != 0u || *err_host == 0u)) *err_host = err;
     if (err != 0u) return;
+    // this step commits: it is one more that the agents the caller froze sat out (no thread of the launch reads a frozen agent's word)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) if ((oa.trainable >> (4 + a)) & 1) const_cast<uint32_t*>(counter)[4 + a] += 1u;
+    }
     // oa.from_wgrad: the squared-norm partials are the ones k_wgrad left per block (single GPU);
     // otherwise the MMG_GN_BLOCKS partials of k_gradnorm over the all-reduced gradient (data parallel).
     __shared__ float s_coef[4];
+    __shared__ float s_bc1[4], s_bc2s[4];
     __shared__ float s_ss[4][4];
-    // this thread's element quad: issue its loads first so they share one memory round trip with the partials
+    auto agent_of = [&](int64_t i) {
+        int a = 0;
+        if (i >= oa.agent_begin[1]) a = 1;
+        if (i >= oa.agent_begin[2]) a = 2;
+        if (i >= oa.agent_begin[3]) a = 3;
+        return a;
+    };
+    // this thread's element quad: issue its loads first so they share one memory round trip with the partials (a frozen agent's
+    // quad is not loaded at all)
     float* st1 = state; float* st2 = state + oa.total;
     const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const bool have = i0 < oa.total;
-    const int64_t il = have ? i0 : 0;
-    const float4 g0 = *reinterpret_cast<const float4*>(grads + il);
-    const float4 w0 = *reinterpret_cast<const float4*>(params + il);
-    const float4 s0 = *reinterpret_cast<const float4*>(st1 + il);
-    const float4 v0 = (oa.optim_type == MMG_OPT_ADAM) ? *reinterpret_cast<const float4*>(st2 + il) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool have = i0 < oa.total && opt_trains(oa, agent_of(i0));
+    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), w0 = g0, s0 = g0, v0 = g0;
+    if (have) {
+        g0 = *reinterpret_cast<const float4*>(grads + i0);
+        w0 = *reinterpret_cast<const float4*>(params + i0);
+        s0 = *reinterpret_cast<const float4*>(st1 + i0);
+        if (oa.optim_type == MMG_OPT_ADAM) v0 = *reinterpret_cast<const float4*>(st2 + i0);
+    }
     const uint32_t step = counter[1] + (oa.bump_step ? 1u : 0u);      // k_gradnorm bumps it in the DP path
     {
         const int n = oa.from_wgrad ? jt->n_wblocks : MMG_GN_BLOCKS;
@@ -1392,22 +1449,22 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_opt(const JobTable* __restrict__ 
             s_coef[threadIdx.x] = coef < 1.f ? coef : 1.f;
             // non-finite guard (k_wgrad<OPT>'s norm role): a non-finite gradient norm of any agent makes the logged NLL NaN
             if (losses && blockIdx.x == 0 && (!(tot == tot) || tot > 3.0e38f)) losses[0] = __builtin_nanf("");
+            // Adam's bias correction counts the agent's OWN updates, as four torch.optim.Adam objects would
+            float bc1 = 1.f, bc2s = 1.f;
+            if (oa.optim_type == MMG_OPT_ADAM && opt_trains(oa, (int)threadIdx.x)) {
+                const float astep = (float)(step - counter[4 + threadIdx.x]);
+                bc1 = 1.f - powf(0.9f, astep);
+                bc2s = sqrtf(1.f - powf(0.999f, astep));
+            }
+            s_bc1[threadIdx.x] = bc1; s_bc2s[threadIdx.x] = bc2s;
         }
     }
     __syncthreads();
     const float b1 = 0.9f, b2 = 0.999f;
-    float bc1 = 1.f, bc2s = 1.f;
-    if (oa.optim_type == MMG_OPT_ADAM) {
-        bc1 = 1.f - powf(b1, (float)step);
-        bc2s = sqrtf(1.f - powf(b2, (float)step));
-    }
     for (int64_t i = i0; i < oa.total; i += (int64_t)gridDim.x * blockDim.x * 4) {
-        int a = 0;
-        if (i >= oa.agent_begin[1]) a = 1;
-        if (i >= oa.agent_begin[2]) a = 2;
-        if (i >= oa.agent_begin[3]) a = 3;
-        if (oa.only_receiver && a != 0) continue;                     // model.py:1313
-        const float coef = s_coef[a];
+        const int a = agent_of(i);
+        if (!opt_trains(oa, a)) continue;                             // model.py:1313; a frozen agent (mmg_set_trainable)
+        const float coef = s_coef[a], bc1 = s_bc1[a], bc2s = s_bc2s[a];
         const bool first = (i == i0);
         float4 g = first ? g0 : *reinterpret_cast<const float4*>(grads + i);
         float4 w = first ? w0 : *reinterpret_cast<float4*>(params + i);

@@ -236,7 +236,7 @@ inline VattnParams resolve_vattn_params(const ParamLayout& L, float* base) {
     X(statll, float, 0, 1, 2 * (27 * T + 2 * T * B), 1, 1) /* (value, epoch) pairs of the stream statistics (per (stream, step): n | four f64 sums as 2 halves each) and of bs | br: hand-off from the statistics roles to the sample roles of the backward launch (kernels_fast.h) */ \
     X(stats, double, 3, 1, NSTAT, 1, 1)  /* batch statistics (all-reduced in DP)   */ \
     X(losses, float, 0, 1, 8, 1, 1)      /* nll, bin_s, bin_rec, bin_sen, bas_rec, bas_sen, n_steps, hits */ \
-    X(counter, uint32_t, 2, 1, 4, 1, 1)  /* [0] minibatch counter (Philox), [1] optimizer step, [3] launch epoch of the (value, epoch) pair hand-offs: bumped with [0], never copied between engines (game.py), never reset */ \
+    X(counter, uint32_t, 2, 1, 8, 1, 1)  /* [0] minibatch counter (Philox), [1] optimizer step, [3] launch epoch of the (value, epoch) pair hand-offs: bumped with [0], never copied between engines (game.py), never reset; [4 + a] optimizer steps agent a sat out frozen (mmg_set_trainable): its own step count, Adam's bias correction, is [1] - [4 + a] */ \
     X(rmap, int32_t, 2, 1, T * B, 1, 1)  /* compacted list of the (step, sample) rows with t <= t*(b), in (t, b) order   */ \
     X(rcount, int32_t, 2, 1, 4, 1, 1)    /* [0] its length (k_wgrad reduces over these rows only)                          */ \
     X(sync, uint32_t, 2, 1, 512, 1, 1)    /* in-launch dependency counters between workgroup roles (device_utils.h: role_signal) */ \
@@ -268,7 +268,7 @@ inline VattnParams resolve_vattn_params(const ParamLayout& L, float* base) {
     X(dbr, float, 0, 2, T, B, 1)                                                   \
     X(gnpart, float, 0, 1, 16384 + NPART, 1, 1)  /* squared grad-norm partials (k_wgrad blocks | k_gradnorm) */ \
     X(gnll, float, 0, 1, 2 * 16384, 1, 1) /* k_wgrad<OPT>: (value, epoch) pairs of the blocks' sums of squares (hand-off to the norm role of the same launch) */ \
-    X(coefll, float, 0, 1, 2 * (4 * 64 + 4), 1, 1) /* k_wgrad<OPT>: (value, epoch) pairs of the four clip coefficients, 64 replicas each, then the four agents' squared norms */ \
+    X(coefll, float, 0, 1, 2 * (4 * 64 + 4 + 8 * 64), 1, 1) /* k_wgrad<OPT>: (value, epoch) pairs of the four clip coefficients, 64 replicas each, then the four agents' squared norms, then each agent's two Adam bias corrections, 64 replicas each */ \
     X(ones, float, 0, 1, 256, 1, 1)      /* 1.0f: B operand of bias gradients run as K = 1 GEMM jobs (many (step, sample) rows) */ \
     X(wcnt, int32_t, 2, 1, 16384, 1, 1)  /* k_wgrad: slices of an output tile that have written their partial tile (the last one adds them up and zeroes the count) */ \
     X(wpart, float, 0, 1, NWP, 1, 1)     /* raw partial tiles of weight gradients whose rows are split over workgroups (k_wgrad) */ \

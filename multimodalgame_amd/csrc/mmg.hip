@@ -424,6 +424,7 @@ extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_ca
     h->d_err = reinterpret_cast<uint32_t*>(base);           // (as a created handle has one; h_err stays NULL: nothing to release)
     h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0; h->sender_var = (flags & 4) ? SV_PROD : 0;
     if (flags & 8) h->relax_tau_sen = h->relax_tau_rec = 1.f;
+    h->train_mask = 15 & ~(flags >> 4);                     // bits 4-7: frozen agents (mmg_set_trainable's mask, inverted)
     const Switches w = read_switches();
     if (shape_pass(h, w)) return -1;
     memcpy(h->sel.caps, caps, sizeof(h->sel.caps));
@@ -826,6 +827,59 @@ extern "C" int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float ta
     return 0;
 }
 
+// Training controls (include/mmg.h): host state, read where the next minibatch's launches are enqueued -- the mask, the learning rate and
+// the entropy weights travel as kernel arguments (OptArgs, Dims).  No kernel is re-selected and nothing synchronises.  (The values are
+// checked before the handle: a bad value reads the same with or without one.)
+extern "C" int mmg_set_trainable(mmg_handle* h, int mask) {
+    if (mask & ~15) return fail("mmg_set_trainable: mask 0x%x has bits outside the four agents (MMG_AGENT_RECEIVER .. MMG_AGENT_BASELINE_SEN: 0x0 .. 0xf)", (unsigned)mask);
+    if (!h) return fail("NULL handle");
+    const int old_mask = h->train_mask, old_frozen = frozen_agents(h);
+    h->train_mask = mask;
+    const int frozen = frozen_agents(h);
+    if (frozen == old_frozen) return 0;
+    // the job table of this set of frozen agents and what follows it -- row splits, k_wgrad's walk, whether the optimizer fits inside
+    // its launch --: decided once (host_select.h: reselect_from_caps, pure), kept, and uploaded on the stream of the next minibatch
+    MaskPlan& mp = h->mask_plans[frozen];
+    if (mp.valid) {
+        h->sel = mp.sel;
+        memcpy(&h->jt, mp.pinned, sizeof(JobTable));
+    } else if (reselect_from_caps(h) || keep_mask_plan(h)) {
+        const std::string why = g_err;
+        h->train_mask = old_mask;
+        reselect_from_caps(h);
+        return fail("mmg_set_trainable: %s", why.c_str());
+    }
+    h->jt_src = mp.pinned;
+    h->zero_pending |= frozen & ~old_frozen;
+    return 0;
+}
+extern "C" int mmg_set_learning_rate(mmg_handle* h, float lr) {
+    if (!(lr >= 0.f) || !(lr <= 3.4028235e38f))          // (NaN fails both compares)
+        return fail("mmg_set_learning_rate: lr = %g: the learning rate must be finite and >= 0", (double)lr);
+    if (!h) return fail("NULL handle");
+    h->cfg.learning_rate = lr;
+    return 0;
+}
+extern "C" int mmg_set_entropy(mmg_handle* h, float entropy_s, float entropy_sen, float entropy_rec) {
+    const float v[3] = {entropy_s, entropy_sen, entropy_rec};
+    for (int k = 0; k < 3; ++k)
+        if (!(v[k] >= -3.4028235e38f && v[k] <= 3.4028235e38f))
+            return fail("mmg_set_entropy: entropy_s = %g, entropy_sen = %g, entropy_rec = %g: the weights must be finite", (double)entropy_s, (double)entropy_sen, (double)entropy_rec);
+    if (!h) return fail("NULL handle");
+    // a weight that was None at mmg_create stays absent (has_entropy_* selected the kernels' terms): its argument is ignored
+    if (h->cfg.has_entropy_s) h->cfg.entropy_s = h->dm.es = entropy_s;
+    if (h->cfg.has_entropy_sen) h->cfg.entropy_sen = h->dm.esen = entropy_sen;
+    if (h->cfg.has_entropy_rec) h->cfg.entropy_rec = h->dm.erec = entropy_rec;
+    return 0;
+}
+extern "C" int mmg_get_training_controls(const mmg_handle* h, int* mask, float* lr, float* entropy3) {
+    if (!h) return fail("NULL handle");
+    if (mask) *mask = h->train_mask;
+    if (lr) *lr = h->cfg.learning_rate;
+    if (entropy3) { entropy3[0] = h->cfg.entropy_s; entropy3[1] = h->cfg.entropy_sen; entropy3[2] = h->cfg.entropy_rec; }
+    return 0;
+}
+
 extern "C" int mmg_loss_stats(mmg_handle* h, void* stream) {
     if (!h) return fail("NULL handle");
     hipStream_t st = (hipStream_t)stream;
@@ -863,7 +917,7 @@ static int launch_bwd_tile(mmg_handle* h, hipStream_t st, const int64_t* d_targe
         }
         if (launch_check("k_bwd_tile")) return -1;
     }
-    if (d.use_binary) {
+    if (d.use_binary && !is_frozen(h, MMG_AGENT_SENDER)) {                  // (the sender's reverse pass feeds the sender's jobs alone)
         Scope sc(h, st, "k_send_bwd");
         if (p.send_own)
             hipLaunchKernelGGL(k_send_bwd, dim3(p.n_rowblk, p.n_hbands), dim3(MMG_BLOCK), s.send_bwd_smem, st, h->dm, h->P, h->tp, (const int*)(p.row_map ? h->tp.rmap : nullptr), (const int*)(p.row_map ? h->tp.rcount : nullptr));
@@ -888,6 +942,7 @@ static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_tar
     if (s.attn) {
         // the reverse pass, then the two reductions that are no GEMM over (step, sample) rows: dE | Py2 per class, dDD per word
         { Scope sc(h, st, "k_bwd_conv"); hipLaunchKernelGGL(k_bwd_conv_attn, dim3(d.B), dim3(MMG_BLOCK), s.bwd_smem, st, h->dm, h->P, h->tp, d_target, h->at); }
+        if (is_frozen(h, MMG_AGENT_RECEIVER)) return launch_check("k_bwd_conv_attn");      // (both feed the receiver's jobs alone)
         { Scope sc(h, st, "k_attn_dE"); hipLaunchKernelGGL(k_attn_dE, dim3(d.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, h->at); }
         { Scope sc(h, st, "k_attn_dDD"); hipLaunchKernelGGL(k_attn_dDD, dim3(h->n_words), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, h->at); }
         return launch_check("k_bwd_conv_attn");
@@ -897,7 +952,7 @@ static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_tar
         // output tile of attn_W_x.weight.  Continuous messages train the receiver alone: nothing more
         { Scope sc(h, st, "k_bwd_conv"); hipLaunchKernelGGL(p.bwd_conv_fn, dim3(d.B), dim3(MMG_BLOCK), s.bwd_smem, st, h->dm, h->P, h->tp, d_target); }
         if (launch_check("k_bwd_conv")) return -1;
-        if (!d.use_binary) return 0;
+        if (!d.use_binary || is_frozen(h, MMG_AGENT_SENDER)) return 0;      // (the attention's reverse pass: the sender's tensors alone)
         VattnArgs va = h->va; va.ctx = h->ctx_cur;
         const size_t smem = (size_t)s.vattn_bwd_smem;           // (sized by shape_pass, its limit raised by probe_device)
         { Scope sc(h, st, "k_vattn_bwd"); hipLaunchKernelGGL(k_vattn_bwd, dim3(d.B), dim3(MMG_BLOCK), smem, st, h->dm, h->P, h->tp, h->bwd_x, va); }
@@ -913,16 +968,33 @@ static int launch_bwd_sample(mmg_handle* h, hipStream_t st, const int64_t* d_tar
     return launch_check("k_bwd_conv");
 }
 
+// What mmg_set_trainable left for the stream of the next minibatch: the job table of the agents in training goes to the device, and the
+// gradient slice of a newly frozen agent is cleared ONCE -- no job, and none of the launches below, writes it while the agent stays frozen
+// (a data-parallel caller all-reduces the whole buffer).  Stream-ordered behind the minibatch before, which read the table before.
+static int apply_pending(mmg_handle* h, hipStream_t st) {
+    if (h->jt_src) {
+        HIP_OK(hipMemcpyAsync(h->d_jt, h->jt_src, sizeof(JobTable), hipMemcpyHostToDevice, st));
+        h->jt_src = nullptr;
+    }
+    const int zero = h->zero_pending & frozen_agents(h);
+    h->zero_pending = 0;
+    for (int a = 0; a < 4; ++a)
+        if ((zero >> a) & 1)
+            HIP_OK(hipMemsetAsync(h->grads + h->pl.agent_begin[a], 0, sizeof(float) * (size_t)(h->pl.agent_begin[a + 1] - h->pl.agent_begin[a]), st));
+    return 0;
+}
+
 // with_opt: this step's k_wgrad carries the optimizer (no k_opt launch).  conv_done: the fused step -- k_game_fast ran the forward and the
 // reverse pass (its first class role listed the live rows), so no k_prep committed the minibatch counter / launch epoch: the optimizer does
 static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, const float* d_desc, hipStream_t st, bool with_stats,
                          bool with_opt = false, bool conv_done = false) {
     const LaunchPlan& p = h->sel.plan;
     h->bwd_x = d_x;
+    if (apply_pending(h, st)) return -1;
     if (!conv_done) {
         if (h->sel.family == FAM_TILE ? launch_bwd_tile(h, st, d_target) : mc_bwd(h) ? launch_bwd_mc(h, st, d_target, with_stats)
                                                                                      : launch_bwd_sample(h, st, d_target, with_stats)) return -1;
-        if (p.dc != DC_NONE) {
+        if (p.dc != DC_NONE && !is_frozen(h, MMG_AGENT_RECEIVER)) {         // (dC feeds the receiver's y1 jobs alone)
             Scope sc(h, st, "k_dC");
             if (p.dc == DC_PLAIN) hipLaunchKernelGGL(k_dC, dim3(h->dm.D), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp);
             else hipLaunchKernelGGL(k_dC_tile, dim3(p.dc_grid, p.dc_slices), dim3(MMG_BLOCK), 0, st, h->dm, h->P, h->tp, p.dc_slices, 0);
@@ -934,7 +1006,7 @@ static int backward_impl(mmg_handle* h, const float* d_x, const int64_t* d_targe
     hd.gemm_tiles = h->jt.gemm_tiles; hd.n_wblocks = h->jt.n_wblocks; hd.special_block = h->jt.special_block; hd.special_job = h->jt.special_job;
     WgOpt wo = {};
     if (with_opt) {
-        wo.oa.optim_type = h->cfg.optim_type; wo.oa.only_receiver = 0; wo.oa.lr = h->cfg.learning_rate;
+        wo.oa.optim_type = h->cfg.optim_type; wo.oa.trainable = opt_trainable(h); wo.oa.lr = h->cfg.learning_rate;
         wo.oa.from_wgrad = 1; wo.oa.bump_step = 1; wo.oa.bump_mb = conv_done ? 1 : 0;
         for (int a = 0; a < 5; ++a) wo.oa.agent_begin[a] = h->pl.agent_begin[a];
         wo.oa.total = h->pl.total; wo.params = h->params; wo.state = h->opt_state; wo.grads = h->grads; wo.gnll = h->tp.gnll; wo.coefll = h->tp.coefll;
@@ -961,6 +1033,7 @@ static int clip_step_impl(mmg_handle* h, hipStream_t st, bool from_wgrad, bool g
     // from_wgrad: use the squared-norm partials k_wgrad left behind (valid only if d_grads has not been
     // modified since mmg_backward, i.e. single GPU); otherwise recompute them from d_grads.
     float* part = h->tp.gnpart + (from_wgrad ? 0 : MMG_MAX_WBLOCKS);
+    if (apply_pending(h, st)) return -1;
     if (!from_wgrad) {
         Scope sc(h, st, "k_gradnorm");
         hipLaunchKernelGGL(k_gradnorm, dim3(MMG_GN_BLOCKS), dim3(MMG_BLOCK), 0, st, (const JobTable*)h->d_jt,
@@ -969,7 +1042,7 @@ static int clip_step_impl(mmg_handle* h, hipStream_t st, bool from_wgrad, bool g
         if (launch_check("k_gradnorm")) return -1;
     }
     OptArgs oa;
-    oa.optim_type = h->cfg.optim_type; oa.only_receiver = h->cfg.use_binary ? 0 : 1; oa.lr = h->cfg.learning_rate;
+    oa.optim_type = h->cfg.optim_type; oa.trainable = opt_trainable(h); oa.lr = h->cfg.learning_rate;
     oa.from_wgrad = from_wgrad ? 1 : 0; oa.bump_step = from_wgrad ? 1 : 0; oa.bump_mb = game_step ? 1 : 0;
     for (int a = 0; a < 5; ++a) oa.agent_begin[a] = h->pl.agent_begin[a];
     oa.total = h->pl.total;

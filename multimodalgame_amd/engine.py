@@ -28,6 +28,14 @@ def check_desc_set(desc_set, lens, n_classes, wv_dim):
         raise ValueError("desc_set_lens sum to %d, desc_set has %d words" % (sum(lens), desc_set.size(0)))
 
 
+def steps_from_counter(counter):
+    """{agent: optimizer steps that updated it} of a tape "counter" tensor (Engine.agent_steps; Game reads the counter of whichever
+    engine trained last through this).  Words the tensor does not hold read zero: a 4-word counter carries the global count alone."""
+    c = counter.cpu().tolist()
+    step, sat_out = int(max(c[1], c[2])), c[4:8] + [0] * 4
+    return {a: step - int(sat_out[i]) for i, a in enumerate(_lib.AGENTS)}
+
+
 class Engine(object):
     def __init__(self, device="cuda:0", share=None, attn_dim=0, n_words=0, vattn=None, **cfg_kwargs):
         """share: another Engine whose flat parameter / gradient / optimizer-state buffers this one
@@ -240,6 +248,41 @@ class Engine(object):
             raise ValueError("tau_sen = %r, tau_rec = %r: temperatures must be positive" % (tau_sen, tau_rec))
         _lib.check(self.lib.mmg_set_message_relaxation(self.handle, tau_sen, tau_rec, int(bool(hard))))
         self.relaxation = (tau_sen, tau_rec, bool(hard))
+
+    # ------------------------------------------------------------------ training controls
+    def set_trainable(self, agents):
+        """The agents the REINFORCE step updates from the next minibatch on (include/mmg.h: mmg_set_trainable): a collection of agent
+        names (_lib.AGENTS) or the mask itself; the others are frozen -- parameters and optimizer state bit-identical, their slice of
+        the gradient buffer zero, the forward pass and the other agents' updates unchanged.  Host only, no synchronisation."""
+        mask = int(agents) if isinstance(agents, int) else _lib.agent_mask([agents] if isinstance(agents, str) else agents)
+        _lib.check(self.lib.mmg_set_trainable(self.handle, mask))
+
+    def set_learning_rate(self, lr):
+        """The learning rate of every later minibatch (include/mmg.h: mmg_set_learning_rate): finite, >= 0.  Host only."""
+        _lib.check(self.lib.mmg_set_learning_rate(self.handle, float(lr)))
+
+    def set_entropy(self, entropy_s=None, entropy_sen=None, entropy_rec=None):
+        """New values of the entropy weights of every later minibatch (include/mmg.h: mmg_set_entropy); None keeps a weight's current
+        value.  A weight that was None when the engine was created stays absent, whatever is passed.  Host only."""
+        cur = self.training_controls()
+        vals = [float((cur[k] or 0.0) if v is None else v) for k, v in (("entropy_s", entropy_s), ("entropy_sen", entropy_sen), ("entropy_rec", entropy_rec))]
+        _lib.check(self.lib.mmg_set_entropy(self.handle, *vals))
+
+    def training_controls(self):
+        """dict(trainable = tuple of agent names, mask, learning_rate, entropy_s, entropy_sen, entropy_rec): what the next minibatch
+        trains with (include/mmg.h: mmg_get_training_controls).  An entropy weight the engine was created without reads None."""
+        mask, lr, ent = C.c_int(0), C.c_float(0.0), (C.c_float * 3)()
+        _lib.check(self.lib.mmg_get_training_controls(self.handle, C.byref(mask), C.byref(lr), ent))
+        has = (self.cfg.has_entropy_s, self.cfg.has_entropy_sen, self.cfg.has_entropy_rec)
+        out = dict(mask=mask.value, trainable=tuple(a for i, a in enumerate(_lib.AGENTS) if (mask.value >> i) & 1), learning_rate=float(lr.value))
+        for k, h, v in zip(("entropy_s", "entropy_sen", "entropy_rec"), has, ent):
+            out[k] = float(v) if h else None
+        return out
+
+    def agent_steps(self):
+        """{agent: optimizer steps that updated it}: the global step count (tape "counter"[1], [2] while a step is not committed yet)
+        minus the steps the agent sat out frozen ("counter"[4 + a]).  One device->host copy."""
+        return steps_from_counter(self.tape["counter"])
 
     def set_desc_set(self, desc_set, lens):
         """The description set of an attention engine (include/mmg.h: mmg_set_desc_set): desc_set [n_words, V], the word vectors of

@@ -7,7 +7,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import flags as _flags
 from . import misc
-from .engine import Engine
+from .engine import Engine, steps_from_counter
 
 
 def _input_grad(g, like):
@@ -156,20 +156,26 @@ class FlatOptimizer(object):
         """(name, view into the flat buffer) in torch.optim's numbering: the order of module.parameters(), i.e. of
         named_parameters() -- direct nn.Parameters first (Sender: code_bias is index 0), then the sub-modules in
         registration order -- NOT the engine's flat-buffer order."""
-        views = self.game.engine.params[self.agent]
         mod = self.game.modules.get(self.agent)
+        if self.game.engine is None:                  # (no engine yet: nothing was trained, the modules still own their parameters)
+            return [(name, p.data) for name, p in mod.named_parameters()] if mod is not None else []
+        views = self.game.engine.params[self.agent]
         if mod is None:
             return list(views.items())
         return [(name, views[name]) for name, _ in mod.named_parameters()]
 
     def state_dict(self):
+        """torch.optim's layout; "step" is the agent's OWN count of updates (a frozen agent's stands still) and
+        param_groups[0]["lr"] the current learning rate.  One more top-level key, "training_controls" -- whether the agent is trainable,
+        the learning rate, the entropy weights, the agent's step --, carries Game.freeze / set_hyper through a checkpoint;
+        torch.optim ignores it."""
         eng, kind = self.game.engine, self.game.cfg["optim_type"]
-        step = self.game.counters()[1]
-        n = eng.n_params
+        step = self.game.agent_steps()[self.agent]
+        n = eng.n_params if eng is not None else 0
         state = {}
         for i, (name, view) in enumerate(self._params()):
             off = view.storage_offset()
-            if step == 0 or kind == "SGD":
+            if eng is None or step == 0 or kind == "SGD":
                 continue
             if kind == "RMSprop":
                 state[i] = {"step": torch.tensor(float(step)),
@@ -183,10 +189,17 @@ class FlatOptimizer(object):
             group.update(alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False)
         elif kind == "Adam":
             group.update(betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False)
-        return {"state": state, "param_groups": [group]}
+        return {"state": state, "param_groups": [group], "training_controls": self.game.controls_state(self.agent, step)}
 
     def load_state_dict(self, sd):
         eng, kind = self.game.engine, self.game.cfg["optim_type"]
+        # "training_controls" (state_dict): a checkpoint of this package restores the mask bit, the learning rate and the entropy weights;
+        # a torch optimizer's state dict, or a checkpoint from before the controls existed, has no such key and sets nothing new
+        controls = sd.get("training_controls")
+        if controls is not None:
+            self.game.load_controls(self.agent, controls)
+        if eng is None:
+            return
         # The parameters themselves do not change here, but a pending node of an agent module's forward() was recorded before
         # the optimizer state it is meant to be stepped with: it raises, as for the other library-side updates (Engine.param_version).
         eng.bump_param_version()
@@ -204,8 +217,7 @@ class FlatOptimizer(object):
                 eng.opt_state[off:off + view.numel()].copy_(st["exp_avg"].reshape(-1).to(eng.device))
                 eng.opt_state[n + off:n + off + view.numel()].copy_(st["exp_avg_sq"].reshape(-1).to(eng.device))
         if step:
-            for e in self.game.engines.values():
-                e.tape["counter"][1:3] = step
+            self.game.set_agent_step(self.agent, step)
 
 
 class EvalAccumulator(object):
@@ -352,6 +364,8 @@ class Game(object):
         self.relax = relax_setting(relax)
         if self.relax:
             self._check_relax(self.autograd, self.channel_grad)
+        self.trainable = tuple(_lib.AGENTS)           # freeze() / unfreeze(): the agents train_step(s) updates
+        self._agent_steps = None      # per-agent optimizer steps restored before any engine exists (load_controls)
         self.engines = {}
         self.engine = None            # the first engine owns the flat buffers
         self.optimizers = None
@@ -408,6 +422,114 @@ class Game(object):
         self.relax = relax
         for eng in self.engines.values():
             eng.set_message_relaxation(*(relax or (None, None)))
+
+    # ------------------------------------------------------------------ training controls (include/mmg.h: mmg_set_trainable, ...)
+    def _check_agents(self, agents):
+        self._refuse_relaxed_step("freeze / unfreeze: train_step")
+        _lib.agent_mask(agents)                       # (ValueError for a name that is no agent)
+        return set(agents)
+
+    def freeze(self, *agents):
+        """Stop updating these agents (names as in models_dict()) from the next train_step(s) on, in every engine of the game and
+        in those created later: parameters and optimizer state stay bit-identical, the agent still speaks / scores, the other
+        agents train as before, Adam's bias correction of a frozen agent stands still.  With world > 1 EVERY rank must make the same
+        calls between the same minibatches (the mask is host state of each rank's handle).  A game with relaxed messages refuses:
+        its optimizers are torch's."""
+        off = self._check_agents(agents)
+        self.trainable = tuple(a for a in _lib.AGENTS if a in self.trainable and a not in off)
+        for eng in self.engines.values():
+            eng.set_trainable(self.trainable)
+
+    def unfreeze(self, *agents):
+        """Update these agents again (all four when called without a name); see freeze(), and its note on world > 1."""
+        on = self._check_agents(agents or _lib.AGENTS)
+        self.trainable = tuple(a for a in _lib.AGENTS if a in self.trainable or a in on)
+        for eng in self.engines.values():
+            eng.set_trainable(self.trainable)
+
+    def set_hyper(self, learning_rate=None, entropy_s=None, entropy_sen=None, entropy_rec=None):
+        """New values of the learning rate and of the entropy weights for every later minibatch of train_step(s) -- what a
+        training loop calls between minibatches to anneal them; None keeps a value.  They are kept in game.cfg and hold for every
+        engine of the game and for those created later.  An entropy weight the game was created without (None in its flags) stays
+        absent: its argument is ignored.  With world > 1 EVERY rank must make the same calls between the same minibatches.  A game
+        with relaxed messages refuses: its optimizers and losses are the caller's."""
+        self._refuse_relaxed_step("set_hyper: train_step")
+        new = {}
+        if learning_rate is not None:
+            lr = float(learning_rate)
+            if not (lr >= 0.0 and lr != float("inf")):                    # (NaN fails the compare)
+                raise ValueError("learning_rate = %r: finite and >= 0 expected" % (learning_rate,))
+            new["learning_rate"] = lr
+        for k, v in (("entropy_s", entropy_s), ("entropy_sen", entropy_sen), ("entropy_rec", entropy_rec)):
+            if v is None:
+                continue
+            v = float(v)
+            if v != v or v in (float("inf"), float("-inf")):
+                raise ValueError("%s = %r: a finite weight expected" % (k, v))
+            if self.cfg[k] is not None:
+                new[k] = v
+        self.cfg.update(new)
+        for eng in self.engines.values():
+            if "learning_rate" in new:
+                eng.set_learning_rate(new["learning_rate"])
+            if any(k.startswith("entropy") for k in new):
+                eng.set_entropy(**{k: v for k, v in new.items() if k.startswith("entropy")})
+
+    def agent_steps(self):
+        """{agent: optimizer steps that updated it} of the engine that trained last (Engine.agent_steps); zeros before any engine."""
+        eng = getattr(self, "_train_engine", None) or self.engine
+        if eng is None:
+            return dict(self._agent_steps or {a: 0 for a in _lib.AGENTS})
+        return steps_from_counter(eng.tape["counter"])
+
+    @staticmethod
+    def _write_agent_steps(eng, steps):
+        """tape "counter" of one engine from {agent: steps}: the global step is the largest count, the others' difference to it the
+        steps they sat out frozen (include/mmg.h: mmg_set_trainable)."""
+        c = eng.tape["counter"]
+        step = max(int(steps[a]) for a in _lib.AGENTS)
+        c[1:3] = step
+        sat_out = torch.tensor([step - int(steps[a]) for a in _lib.AGENTS], dtype=c.dtype)
+        c[4:8] = sat_out[:c[4:8].numel()]
+
+    def set_agent_step(self, agent, step):
+        """Restore one agent's step count (FlatOptimizer.load_state_dict) in every engine; the others keep theirs.  The counts are
+        read from the device once per load, not once per optimizer (a training step drops the host copy)."""
+        steps = dict(self._agent_steps or self.agent_steps())
+        if steps[agent] == int(step) and self._agent_steps is not None:
+            return
+        steps[agent] = int(step)
+        self._agent_steps = steps
+        for eng in self.engines.values():
+            self._write_agent_steps(eng, steps)
+
+    def controls_state(self, agent, step=None):
+        """What FlatOptimizer.state_dict()["training_controls"] holds for `agent`."""
+        return dict(trainable=agent in self.trainable, learning_rate=self.cfg["learning_rate"], entropy_s=self.cfg["entropy_s"],
+                    entropy_sen=self.cfg["entropy_sen"], entropy_rec=self.cfg["entropy_rec"],
+                    step=int(self.agent_steps()[agent] if step is None else step))
+
+    def load_controls(self, agent, controls):
+        """The inverse of controls_state(): fields a checkpoint lacks keep their current values.  (A game with relaxed messages has
+        no library-side optimizer and can only have saved the defaults: nothing to restore.)"""
+        if self.relax:
+            return
+        if "trainable" in controls and bool(controls["trainable"]) != (agent in self.trainable):
+            (self.unfreeze if controls["trainable"] else self.freeze)(agent)
+        # (the four optimizers of a checkpoint carry the same game-wide values: the first one sets them, the others find them set)
+        new = {k: controls[k] for k in ("learning_rate", "entropy_s", "entropy_sen", "entropy_rec")
+               if controls.get(k) is not None and self.cfg[k] is not None and float(controls[k]) != self.cfg[k]}
+        if new:
+            self.set_hyper(**new)
+        if "step" in controls:
+            self.set_agent_step(agent, controls["step"])
+
+    def _hand_over_counters(self, eng, last):
+        """The Philox minibatch counter, the optimizer step and the agents' frozen steps live in each engine's workspace: they move
+        to the engine that trains next ([3]: the engine's own launch epoch, never handed over)."""
+        c, lc = eng.tape["counter"], last.tape["counter"]
+        c[:3].copy_(lc[:3])
+        c[4:8].copy_(lc[4:8])
 
     def set_parallel(self, rank, world, group=None):
         """Data-parallel training (dist.DataParallel): train_step() then takes THIS rank's rows of the global minibatch --
@@ -520,6 +642,10 @@ class Game(object):
                 eng.set_sender_variant(*self.sender_variant)
             if self.relax:
                 eng.set_message_relaxation(*self.relax)
+            if set(self.trainable) != set(_lib.AGENTS):
+                eng.set_trainable(self.trainable)
+            if self._agent_steps:
+                self._write_agent_steps(eng, self._agent_steps)
             if self.engine is None:
                 self.engine = eng
                 self._adopt(eng)
@@ -774,8 +900,9 @@ class Game(object):
         # them over when the batch size / class count -- hence the engine -- changes between steps
         last = getattr(self, "_train_engine", None)
         if last is not None and last is not eng:
-            eng.tape["counter"][:3].copy_(last.tape["counter"][:3])      # ([3]: the engine's own launch epoch, never handed over)
+            self._hand_over_counters(eng, last)
         self._train_engine = eng
+        self._agent_steps = None                      # (the device counts move: set_agent_step reads them again)
         if self.world > 1:
             dp = self._dp.get(id(eng))
             if dp is None:
@@ -803,8 +930,9 @@ class Game(object):
             eng = self.train_engine_for(B, desc.size(0))
         last = getattr(self, "_train_engine", None)
         if last is not None and last is not eng:
-            eng.tape["counter"][:3].copy_(last.tape["counter"][:3])
+            self._hand_over_counters(eng, last)
         self._train_engine = eng
+        self._agent_steps = None                      # (the device counts move: set_agent_step reads them again)
         if self.world > 1:
             dp = self._dp.get(id(eng))
             if dp is None:
