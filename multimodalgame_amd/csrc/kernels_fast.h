@@ -13,6 +13,7 @@
 #include "device_utils.h"
 #include "kernels_fwd.h"
 #include "layout.h"
+#include "bwd_sample_parts.h"
 
 namespace mmg {
 
@@ -26,16 +27,7 @@ struct FastDims {
 // sigmoid / tanh / log -- three orders of magnitude inside the 1e-4 parity bar.
 __device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float ftanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
-__device__ __forceinline__ float flog(float x) { return __logf(x); }
-
-// d loss / d logit of one Bernoulli unit (kernels_bwd.h: bit_seed) with hardware rcp / log
-__device__ __forceinline__ float bit_seed_fast(float q, float p, float wh, float ce) {
-    const float pe = p + MMG_EPS, qe = 1.f - p + MMG_EPS;
-    const float rp = __builtin_amdgcn_rcpf(pe), rq = __builtin_amdgcn_rcpf(qe);
-    float dLdp = -wh * (q * rp - (1.f - q) * rq);
-    if (ce != 0.f) dLdp += ce * (flog(pe) + p * rp - flog(qe) - (1.f - p) * rq);
-    return dLdp * p * (1.f - p);
-}
+// (flog and bit_seed_fast, the same for log and the Bernoulli seed: bwd_sample_parts.h)
 
 // dot product of NV float4 register quads with float4 operands read from LDS at base + stride*j,
 // as four independent FMA chains (x, y, z, w components) to keep the single wave per SIMD issuing.
@@ -69,6 +61,8 @@ namespace mmg {
 // recurrence needs resident in registers (w^T: 8, w_h^T: 16, W_hh^T: 48, binary_layer^T: 32 per lane).
 // Same math, tape contract and zero-filling as k_bwd_conv (kernels_bwd.h).  The dh-independent work of all steps runs in
 // three sweeps before the recurrence; a reverse step is two phases (cell backward | W_hh^T dgh).
+// The pass itself is bwd_sample_parts.h (shared with k_game_fast and k_bwd_sample): this kernel holds the roles, the
+// prologue's loads, the wait for the statistics and the order of the pieces.
 // ---------------------------------------------------------------------------------------------
 // MERGED: the grid starts with `n_stats` one-wave statistics roles (k_stats' pairs); the sample roles load their
 // weights and forward tape while those run and wait for them right before the loss coefficients (device_utils.h).
@@ -234,17 +228,7 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
         float4 q[MMG_REPACK_F4];
 #pragma unroll
         for (int j = 0; j < MMG_REPACK_F4; ++j) q[j] = wr[j * NT];
-        auto put = [](float* dst, const float4& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; };
-#pragma unroll
-        for (int j = 0; j < 12; ++j) put(whhT + 4 * j, q[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) put(y1T + 4 * j, q[12 + j]);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) put(wwF + 4 * j, q[16 + j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) put(whF + 4 * j, q[18 + j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) put(&wbF[j >> 1][4 * (j & 1)], q[22 + j]);
+        unpack_wrep(q, whhT, y1T, wwF, whF, wbF);
     }
     float y1r[R / K4];                             // y1[:, :R] row k4 fragment (forward product A = y1h . h*)
 #pragma unroll
@@ -305,36 +289,8 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
     const float dy_mine = (tid < Dr) ? (sm_mine - (tid == tgt ? 1.f : 0.f)) / (float)dm.Bg : 0.f;
     __syncthreads();                                    // the forward tape is staged (t_h)
     {
-        const int t = tstar;
-        if (tid < 64) {
-            if (lane < Dr) {                            // (MERGE_DC: write-through store, see the signal below)
-                if (MERGE_DC) __hip_atomic_store(&tp.dy[(size_t)b * Dr + lane], dy_mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else tp.dy[(size_t)b * Dr + lane] = dy_mine;
-            }
-            if (lane < 32) s_dy[lane] = dy_mine;
-            const float dsum = dpp_wave_sum(dy_mine);
-            if (lane == 0) tp.dysum[b] = dsum;
-        } else if (tid < 64 + R) {
-            tp.hstar[(size_t)b * R + tid - 64] = t_h[(t + 1) * R + tid - 64];
-        }
-        {
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < R / K4; ++i) acc = fmaf(y1r[i], t_h[(t + 1) * R + p4 * (R / K4) + i], acc);
-            acc = lane_group_sum<K4>(acc);
-            if (p4 == 0) s_A[k4] = acc;
-        }
-        __syncthreads();
-        if (tid < R) {
-            const float a = s_A[tid];
-            float acc = 0.f;
-#pragma unroll
-            for (int d = 0; d < D; ++d) acc += (a + cdcol[d] > 0.f) ? s_dy[d] : 0.f;
-            const float v = acc * w2_mine;
-            s_dA[tid] = v; tp.dA[(size_t)b * R + tid] = v;
-            if (MERGE_DC) __hip_atomic_store(&tp.Astar[(size_t)b * R + tid], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else tp.Astar[(size_t)b * R + tid] = a;
-        }
+        // (MERGE_DC: dy and A* as write-through stores, see the signal below)
+        output_step<R, K4, D, MERGE_DC>(dy_mine, y1r, cdcol, w2_mine, t_h, s_dy, s_A, s_dA, tp.dy, tp.dysum, tp.hstar, tp.dA, tp.Astar, Dr, b, tstar, tid, k4, p4);
         if (MERGE_DC && tid == 0) {
             // wave 0 wrote dy and A* with device-scope (write-through) stores: they need no L2 write-back, only to
             // have completed before the counter moves -- 64 sample roles each doing a full device-scope release
@@ -343,69 +299,19 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
             __hip_atomic_fetch_add(tp.sync + MMG_SYNC_ARR(1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    // ---- everything that does not depend on the carried dh, for ALL steps of the sample at once, and BEFORE the batch
-    // statistics are needed.  A Bernoulli seed is linear in its two loss coefficients (App. A.4):
-    //   seed = wh S1 + ce S2,   S1 = -(q / pe - (1 - q) / qe) p (1 - p),   S2 = (log pe + p / pe - log qe - (1 - p) / qe) p (1 - p)
-    // and so is everything downstream of it.  The sweeps below run on the two BASIS vectors of every step while the
-    // statistics roles of this launch are still reducing: dgpre = (dlw W_w)(1 - g^2), the sender's dpre = (dlz W_b)(1 - a^2)
-    // and dgpre W_h as [16 steps, K] x [K, N] products on the matrix cores.  After the wait a step's gradients are two
-    // multiply-adds of its bases with (wh_t, ce_t).
+    // ---- everything that does not depend on the carried dh, for ALL steps of the sample at once, on the two seed BASES of every
+    // step (bwd_sample_parts.h, 7.) and BEFORE the batch statistics are needed: the sweeps below run while the statistics roles
+    // of this launch are still reducing.
     MMG_BSTAMP(8);
-    auto seed_basis = [](float q, float pr, float& S1, float& S2) {
-        const float pe = pr + MMG_EPS, qe = 1.f - pr + MMG_EPS;
-        const float rp = __builtin_amdgcn_rcpf(pe), rq = __builtin_amdgcn_rcpf(qe), pq = pr * (1.f - pr);
-        S1 = -(q * rp - (1.f - q) * rq) * pq;
-        S2 = (flog(pe) + pr * rp - flog(qe) - (1.f - pr) * rq) * pq;
-    };
     constexpr int NS_ = TMAX * W / NT;
     float s1w[NS_], s2w[NS_], s1z[NS_], s2z[NS_];
-#pragma unroll
-    for (int u = 0; u < NS_; ++u) {
-        const int i = tid + NT * u, t = i / W;
-        float a1, a2, b1, b2;
-        seed_basis(t_w[i], t_pw[i], a1, a2);
-        seed_basis(t_z[i], t_pz[i], b1, b2);
-        if (!(binary && t < tstar)) { a1 = 0.f; a2 = 0.f; }                  // receiver message: active while m_{t+1} == 1
-        if (!(binary && t <= tstar)) { b1 = 0.f; b2 = 0.f; }
-        s1w[u] = a1; s2w[u] = a2; s1z[u] = b1; s2z[u] = b2;
-        const int j = i - t * W;
-        s_sbas[t * SW + j] = a1; s_sbas[(TMAX + t) * SW + j] = a2; s_sbas[(2 * TMAX + t) * SW + j] = b1; s_sbas[(3 * TMAX + t) * SW + j] = b2;
-    }
+    seed_bases<W, NT, TMAX, SW>(t_w, t_pw, t_z, t_pz, s_sbas, binary, tstar, tid, s1w, s2w, s1z, s2z);
     __syncthreads();
     MMG_BSTAMP(9);
-    // D fragments: lane holds rows t = 4 fq + r of column fi of its n-tile
-    f32x4 g1 = {0.f, 0.f, 0.f, 0.f}, g2 = {0.f, 0.f, 0.f, 0.f}, p1[4], p2[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) { p1[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; p2[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-    for (int ks = 0; ks < W / 4; ++ks) {
-        const int o = fi * SW + 4 * ks + fq;
-        const float aw1 = s_sbas[o], aw2 = s_sbas[TMAX * SW + o], az1 = s_sbas[2 * TMAX * SW + o], az2 = s_sbas[3 * TMAX * SW + o];
-        g1 = mfma16(aw1, wwF[ks], g1); g2 = mfma16(aw2, wwF[ks], g2);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { p1[nt] = mfma16(az1, wbF[nt][ks], p1[nt]); p2[nt] = mfma16(az2, wbF[nt][ks], p2[nt]); }
-    }
+    f32x4 g1, g2, p1[4], p2[4];
+    sweep_seed<W, R, H, TMAX, SW>(s_sbas, wwF, wbF, t_g, t_a, wv, fi, fq, g1, g2, p1, p2);
     const int unit = 16 * wv + fi;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float g = t_g[(4 * fq + r) * R + unit];
-        g1[r] *= (1.f - g * g); g2[r] *= (1.f - g * g);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float a = t_a[(4 * fq + r) * H + 64 * wv + 16 * nt + fi];
-            p1[nt][r] *= (1.f - a * a); p2[nt][r] *= (1.f - a * a);
-        }
-    // W_y1h^T dA enters dh at the output step only (unit k4, reduction slice p4)
-    {
-        float accy = 0.f;
-#pragma unroll
-        for (int i = 0; i < R / K4; ++i) accy = fmaf(y1T[i], s_dA[p4 * (R / K4) + i], accy);
-        accy = lane_group_sum<K4>(accy);
-        if (p4 == 0) s_dAy[k4] = accy;
-    }
+    y1hT_dA<R, K4>(y1T, s_dA, s_dAy, k4, p4);
     float* s_H2 = t_msg + 2 * TMAX * W;                 // [16][R] over t_z | t_pz (read for the last time before the barrier above)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { s_G1[(4 * fq + r) * SR + unit] = g1[r]; s_G2p[(4 * fq + r) * SR + unit] = g2[r]; }
@@ -423,16 +329,7 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
         u_bs = ld_ll(tp.statll, statll_bs(dm) + so); u_br = ld_ll(tp.statll, statll_br(dm) + so);
     };
     if (MERGED) { load_stat_pairs(); asm volatile("" ::: "memory"); }      // (the loads stay ahead of the sweep's LDS reads)
-    {
-        f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < R / 4; ++ks) {
-            h1 = mfma16(s_G1[fi * SR + 4 * ks + fq], whF[ks], h1);
-            h2 = mfma16(s_G2p[fi * SR + 4 * ks + fq], whF[ks], h2);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { s_dhin[(4 * fq + r) * R + unit] = h1[r]; s_H2[(4 * fq + r) * R + unit] = h2[r]; }
-    }
+    sweep_wh<R, SR>(s_G1, s_G2p, whF, s_dhin, s_H2, wv, fi, fq);
     MMG_BSTAMP(11);
     if (MERGED) {                                       // the statistics roles of this launch publish stats, bs, br
         const bool need_b = binary && min(tid, Tm1) <= tstar;       // (the statistics roles write the baseline scores of live rows only)
@@ -450,22 +347,7 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
         coef_compute(dm, creg, lc);
     }
     MMG_BSTAMP(2);
-    if (tid < TMAX) {
-        // per-step scalars of the three streams (model.py:908-922): wh = (L - baseline) cw, ce; stop-bit and MSE seeds
-        const int t = min(tid, Tm1);
-        const bool on = binary && tid <= tstar;
-        s_cf[tid] = on ? (L - rbr_) * lc.cw[T + t] : 0.f;          s_cf[TMAX + tid] = on ? lc.ce[T + t] : 0.f;          // receiver message
-        s_cf[2 * TMAX + tid] = on ? (L - rbs_) * lc.cw[2 * T + t] : 0.f; s_cf[3 * TMAX + tid] = on ? lc.ce[2 * T + t] : 0.f;   // sender message
-        float dls = 0.f;
-        if (on && !dm.fixed) dls = bit_seed_fast(rs_, rps_, (L - rbr_) * lc.cw[t], lc.ce[t]);
-        s_dls[tid] = dls;
-        if (tid <= tstar) {
-            const size_t row = (size_t)tid * B + b;
-            tp.dls[row] = dls;
-            tp.dbs[row] = binary ? lc.cb[t] * (rbs_ - L) : 0.f;                  // MSE seeds (model.py:971-988)
-            tp.dbr[row] = binary ? lc.cb[t] * (rbr_ - L) : 0.f;
-        }
-    }
+    step_scalars<TMAX>(lc.cw, lc.ce, lc.cb, L, rbs_, rbr_, rs_, rps_, binary, dm.fixed != 0, s_cf, s_dls, tp.dls, tp.dbs, tp.dbr, B, T, b, tstar, tid);
 
     // ---- zero the gradient tapes of steps this sample never took -- unless k_wgrad reduces over the live rows only
     // (build_row_map) and never looks at them: ~1.7 MB of stores per minibatch at config 2
@@ -480,85 +362,11 @@ __global__ __launch_bounds__(256, 1) void k_bwd_conv_fast(Dims dm, Params P, Tap
     __syncthreads();
     MMG_BSTAMP(3);
     // ---- the gradient tapes of the live steps: bases x coefficients (stores only; the recurrence below does not wait for them)
-    {
-        const float* c1r = s_cf, *c2r = s_cf + TMAX, *c1z = s_cf + 2 * TMAX, *c2z = s_cf + 3 * TMAX;
-#pragma unroll
-        for (int u = 0; u < NS_; ++u) {
-            const int i = tid + NT * u, t = i / W, j = i - t * W;
-            if (t <= tstar) {
-                const size_t row = (size_t)t * B + b;
-                tp.dlw[row * W + j] = fmaf(c1r[t], s1w[u], c2r[t] * s2w[u]);
-                tp.dlz[row * W + j] = fmaf(c1z[t], s1z[u], c2z[t] * s2z[u]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = 4 * fq + r;
-            if (t <= tstar) tp.dgpre[((size_t)t * B + b) * R + unit] = fmaf(c1r[t], g1[r], c2r[t] * g2[r]);
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            const int hcol = 64 * wv + 16 * nt + fi;
-            float part = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 4 * fq + r;
-                if (t <= tstar) {
-                    const float v = fmaf(c1z[t], p1[nt][r], c2z[t] * p2[nt][r]);
-                    tp.dpre[((size_t)t * B + b) * H + hcol] = v;
-                    part += v;
-                }
-            }
-            part += __shfl_xor(part, 16); part += __shfl_xor(part, 32);       // the four row groups of the column
-            if (fq == 0) tp.dhx[(size_t)b * H + hcol] = part;
-        }
-    }
+    store_grad_tapes<W, R, H, NT, TMAX>(s_cf, s1w, s2w, s1z, s2z, g1, g2, p1, p2, tp.dlw, tp.dlz, tp.dgpre, tp.dpre, tp.dhx, B, b, tstar, tid, wv, fi, fq);
 
-    // ---- the recurrence: two phases and ONE barrier per step.  The carried dh of unit k4 lives in a register of each of the unit's
-    // four lanes (the 4-lane sum leaves W_hh^T dgh in all of them: no LDS hop, no barrier before the next cell backward), and the gate
-    // gradients are double-buffered: a wave that runs ahead writes the OTHER buffer and stops at the next step's barrier, which the
-    // slowest wave reaches only after it has read this one.
-    auto step_in = [&](int t) {                                        // what step t adds to dh besides the recurrence
-        float v = fmaf(s_cf[t], s_dhin[t * R + k4], s_cf[TMAX + t] * s_H2[t * R + k4]) + wsk * s_dls[t];
-        if (t == tstar) v += s_dAy[k4];
-        return v;
-    };
-    float dh_c = 0.f;
-    for (int t = tstar; t >= 0; --t) {
-        const size_t row = (size_t)t * B + b;
-        float* const dgb = s_dgh[t & 1];
-        MMG_BSTAMP(16 + 2 * t);
-        // ===== (4) GRU cell backward: all K4 lanes of unit k4 form the gate gradients, lane p4 stores the p4-th of them
-        const float dh = dh_c + step_in(t);
-        const float* gr = t_gru + t * 4 * R;
-        const float rr = gr[k4], uu = gr[R + k4], nn = gr[2 * R + k4], ghn = gr[3 * R + k4];
-        {
-            const float hp = t_h[t * R + k4];
-            const float dn = dh * (1.f - uu), du = dh * (hp - nn);
-            const float dnp = dn * (1.f - nn * nn), dup = du * uu * (1.f - uu);
-            const float drp = dnp * ghn * rr * (1.f - rr);
-            float* gi = tp.dgi + row * 3 * R; float* gh = tp.dgh + row * 3 * R;
-            static_assert(K4 == 4, "four lanes per unit share the stores");
-            // (selects, then ONE predicated region: three divergent branches each with their own stores split the phase)
-            const float vi = (p4 == 0) ? drp : (p4 == 1) ? dup : dnp;
-            const float vh = (p4 == 2) ? dnp * rr : vi;
-            const int idx = p4 * R + k4;
-            if (p4 < 3) { gi[idx] = vi; gh[idx] = vh; dgb[idx] = vh; }
-        }
-        __syncthreads(); MMG_BSTAMP(16 + 2 * t + 1);
-        // ===== (5) dh_{t-1} = dh * u + W_hh^T dgh
-        {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 3 * R / K4; i += 4) {
-                const float4 dv = *reinterpret_cast<const float4*>(dgb + p4 * (3 * R / K4) + i);
-                a0 = fmaf(whhT[i], dv.x, a0); a1 = fmaf(whhT[i + 1], dv.y, a1);
-                a2 = fmaf(whhT[i + 2], dv.z, a2); a3 = fmaf(whhT[i + 3], dv.w, a3);
-            }
-            const float acc = lane_group_sum<K4>((a0 + a1) + (a2 + a3));
-            dh_c = __fmul_rn(dh, uu) + acc;
-        }
-    }
+    // ---- the recurrence: two phases (cell backward | W_hh^T dgh) and ONE barrier per step, the carried dh in a register
+    recurrence_one_barrier<R, K4, TMAX>(whhT, t_gru, t_h, s_cf, s_dhin, s_H2, s_dls, s_dAy, wsk, &s_dgh[0][0], tp.dgi, tp.dgh, B, b, tstar, k4, p4,
+                                        [&](int slot) { MMG_BSTAMP(slot); });
     MMG_BSTAMP(4);
     // (code_bias: k_wgrad's special column job forms dsig * W_c^T (sum_b dpre_0) once, instead of W_c^T dpre_0 per sample here)
 }

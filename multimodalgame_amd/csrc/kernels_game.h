@@ -692,17 +692,7 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         for (int j = 18; j < 22; ++j) q[j] = wr[j * NT];
 #pragma unroll
         for (int j = 0; j < 12; ++j) q[j] = wr[j * NT];
-        auto put = [](float* dst, const float4& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; };
-#pragma unroll
-        for (int j = 0; j < 12; ++j) put(whhT + 4 * j, q[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) put(y1T + 4 * j, q[12 + j]);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) put(wwF + 4 * j, q[16 + j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) put(whF + 4 * j, q[18 + j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) put(&wbF[j >> 1][4 * (j & 1)], q[22 + j]);
+        unpack_wrep(q, whhT, y1T, wwF, whF, wbF);
     }
     const float Lrew = s_gm[0];
     // ================================================================ epilogue 2: the bulk of the tape (a, GRU gates, class logits, masks,
@@ -747,8 +737,8 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         }
     }
     MMG_STAMP(6); if (tid == 0) { MMG_GT(2048 + 16 * b + 4); }
-    // ================================================================ reverse pass (kernels_fast.h: k_bwd_conv_fast, MERGED + MERGE_DC)
-    // on the forward's LDS slots: t_w = s_w slots 1.., t_pw = s_pw (contiguous), t_z | t_pz, t_g, t_gru, t_h, t_a
+    // ================================================================ reverse pass: the pieces of bwd_sample_parts.h in the order of
+    // k_bwd_conv_fast<MERGED, MERGE_DC> (kernels_fast.h), binary messages and Adaptive stopping assumed, on the forward's LDS slots: t_w = s_w slots 1.., t_pw = s_pw (contiguous), t_z | t_pz, t_g, t_gru, t_h, t_a
 #ifdef MMG_TIMING
 #define MMG_GSTAMP(slot) do { if (b == 0 && tid == 0) tp.dbg[128 + (slot)] = (long long)wall_clock64(); } while (0)
 #else
@@ -767,82 +757,26 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
     LossCoef lc; lc.cw = s_coef; lc.ce = s_coef + 3 * T; lc.cb = s_coef + 6 * T;
     // ---- output step t*: NLL seed dy, A* (kept by the forward pass), dA; dy / A* released to the class roles
     const float dy_mine = (tid < Dr) ? (s_sm[min(tid, 31)] - (tid == tgt ? 1.f : 0.f)) / (float)dm.Bg : 0.f;
-    {
-        const int t = tstar;
-        if (tid < 64) {
-            if (lane < Dr) __hip_atomic_store(&tp.dy[(size_t)b * Dr + lane], dy_mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (lane < 32) s_dy[lane] = dy_mine;
-            const float dsum = dpp_wave_sum(dy_mine);
-            if (lane == 0) tp.dysum[b] = dsum;
-        } else if (tid < 64 + R) {
-            tp.hstar[(size_t)b * R + tid - 64] = t_h[(t + 1) * R + tid - 64];
-        }
-        __syncthreads();
-        if (tid < R) {
-            const float a = s_Astep[t * R + tid];
-            float acc = 0.f;
+    output_seed<R, true>(dy_mine, t_h + (tstar + 1) * R, s_dy, tp.dy, tp.dysum, tp.hstar, Dr, b, tid);
+    __syncthreads();
+    if (tid < R) {
+        const float a = s_Astep[tstar * R + tid];
+        float acc = 0.f;
 #pragma unroll
-            for (int d = 0; d < D; ++d) acc += (d < Dr && a + s_cd[d * R + tid] > 0.f) ? s_dy[d] : 0.f;
-            const float v = acc * w2_mine;
-            s_dA[tid] = v; tp.dA[(size_t)b * R + tid] = v;
-            __hip_atomic_store(&tp.Astar[(size_t)b * R + tid], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (int d = 0; d < D; ++d) acc += (d < Dr && a + s_cd[d * R + tid] > 0.f) ? s_dy[d] : 0.f;
+        output_dA<R, true>(a, acc, w2_mine, s_dA, tp.dA, tp.Astar, b, tid);
     }
     // ---- everything that does not depend on the carried dh, for ALL steps at once, on the two seed BASES (kernels_fast.h)
     MMG_GSTAMP(8); if (tid == 0) { MMG_GT(2048 + 16 * b + 5); }
-    auto seed_basis = [](float q, float pr, float& S1, float& S2) {
-        const float pe = pr + MMG_EPS, qe = 1.f - pr + MMG_EPS;
-        const float rp = __builtin_amdgcn_rcpf(pe), rq = __builtin_amdgcn_rcpf(qe), pq = pr * (1.f - pr);
-        S1 = -(q * rp - (1.f - q) * rq) * pq;
-        S2 = (flog(pe) + pr * rp - flog(qe) - (1.f - pr) * rq) * pq;
-    };
     constexpr int NS_ = TMAX * W / NT;
     float s1w[NS_], s2w[NS_], s1z[NS_], s2z[NS_];
-#pragma unroll
-    for (int u = 0; u < NS_; ++u) {
-        const int i = tid + NT * u, t = i / W;
-        float a1, a2, b1, b2;
-        seed_basis(t_w[i], t_pw[i], a1, a2);
-        seed_basis(t_z[i], t_pz[i], b1, b2);
-        if (!(t < tstar)) { a1 = 0.f; a2 = 0.f; }                  // receiver message: active while m_{t+1} == 1
-        if (!(t <= tstar)) { b1 = 0.f; b2 = 0.f; }
-        s1w[u] = a1; s2w[u] = a2; s1z[u] = b1; s2z[u] = b2;
-        const int j = i - t * W;
-        s_sbas[t * G::SW + j] = a1; s_sbas[(TMAX + t) * G::SW + j] = a2; s_sbas[(2 * TMAX + t) * G::SW + j] = b1; s_sbas[(3 * TMAX + t) * G::SW + j] = b2;
-    }
+    seed_bases<W, NT, TMAX, G::SW>(t_w, t_pw, t_z, t_pz, s_sbas, true, tstar, tid, s1w, s2w, s1z, s2z);
     __syncthreads();
     MMG_GSTAMP(9);
-    f32x4 g1 = {0.f, 0.f, 0.f, 0.f}, g2 = {0.f, 0.f, 0.f, 0.f}, p1[4], p2[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) { p1[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; p2[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-    for (int ks = 0; ks < W / 4; ++ks) {
-        const int o = fi * G::SW + 4 * ks + fq;
-        const float aw1 = s_sbas[o], aw2 = s_sbas[TMAX * G::SW + o], az1 = s_sbas[2 * TMAX * G::SW + o], az2 = s_sbas[3 * TMAX * G::SW + o];
-        g1 = mfma16(aw1, wwF[ks], g1); g2 = mfma16(aw2, wwF[ks], g2);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { p1[nt] = mfma16(az1, wbF[nt][ks], p1[nt]); p2[nt] = mfma16(az2, wbF[nt][ks], p2[nt]); }
-    }
+    f32x4 g1, g2, p1[4], p2[4];
+    sweep_seed<W, R, H, TMAX, G::SW>(s_sbas, wwF, wbF, t_g, t_a, wv, fi, fq, g1, g2, p1, p2);
     const int unit = 16 * wv + fi;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float g = t_g[(4 * fq + r) * R + unit];
-        g1[r] *= (1.f - g * g); g2[r] *= (1.f - g * g);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float a = t_a[(4 * fq + r) * H + 64 * wv + 16 * nt + fi];
-            p1[nt][r] *= (1.f - a * a); p2[nt][r] *= (1.f - a * a);
-        }
-    {   // W_y1h^T dA enters dh at the output step only (unit k4, reduction slice p4)
-        float accy = 0.f;
-#pragma unroll
-        for (int i = 0; i < R / K4; ++i) accy = fmaf(y1T[i], s_dA[p4 * (R / K4) + i], accy);
-        accy = lane_group_sum<K4>(accy);
-        if (p4 == 0) s_dAy[k4] = accy;
-    }
+    y1hT_dA<R, K4>(y1T, s_dA, s_dAy, k4, p4);
     float* const s_G1 = lds + G::sg; float* const s_G2 = lds + G::sg + TMAX * G::SR;     // [16][SR] each
     float* const s_H2 = t_z;                            // [16][R] over t_z | t_pz (their contents went out in epilogue 0 / 1)
 #pragma unroll
@@ -860,16 +794,7 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         u_bs = ld_ll(tp.statll, statll_bs(dm) + so); u_br = ld_ll(tp.statll, statll_br(dm) + so);
     };
     load_stat_pairs(); asm volatile("" ::: "memory");      // (the loads stay ahead of the sweep's LDS reads)
-    {
-        f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < R / 4; ++ks) {
-            h1 = mfma16(s_G1[fi * G::SR + 4 * ks + fq], whF[ks], h1);
-            h2 = mfma16(s_G2[fi * G::SR + 4 * ks + fq], whF[ks], h2);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { s_dhin[(4 * fq + r) * R + unit] = h1[r]; s_H2[(4 * fq + r) * R + unit] = h2[r]; }
-    }
+    sweep_wh<R, G::SR>(s_G1, s_G2, whF, s_dhin, s_H2, wv, fi, fq);
     MMG_GSTAMP(11); if (tid == 0) { MMG_GT(2048 + 16 * b + 7); }
     float rbs_, rbr_;
     {                                                    // the statistics roles of this launch publish stats, bs, br
@@ -888,97 +813,14 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         coef_compute(dm, creg, lc);
     }
     MMG_GSTAMP(2); if (tid == 0) { MMG_GT(2048 + 16 * b + 9); }
-    if (tid < TMAX) {
-        // per-step scalars of the three streams (model.py:908-922): wh = (L - baseline) cw, ce; stop-bit and MSE seeds
-        const int t = min(tid, Tm1);
-        const bool on = tid <= tstar;
-        s_cf[tid] = on ? (Lrew - rbr_) * lc.cw[T + t] : 0.f;          s_cf[TMAX + tid] = on ? lc.ce[T + t] : 0.f;          // receiver message
-        s_cf[2 * TMAX + tid] = on ? (Lrew - rbs_) * lc.cw[2 * T + t] : 0.f; s_cf[3 * TMAX + tid] = on ? lc.ce[2 * T + t] : 0.f;   // sender message
-        float dls = 0.f;
-        if (on) dls = bit_seed_fast(rs_, rps_, (Lrew - rbr_) * lc.cw[t], lc.ce[t]);
-        s_dls[tid] = dls;
-        if (tid <= tstar) {
-            const size_t row = (size_t)tid * B + b;
-            tp.dls[row] = dls;
-            tp.dbs[row] = lc.cb[t] * (rbs_ - Lrew);                  // MSE seeds (model.py:971-988)
-            tp.dbr[row] = lc.cb[t] * (rbr_ - Lrew);
-        }
-    }
+    step_scalars<TMAX>(lc.cw, lc.ce, lc.cb, Lrew, rbs_, rbr_, rs_, rps_, true, false, s_cf, s_dls, tp.dls, tp.dbs, tp.dbr, B, T, b, tstar, tid);
     __syncthreads();
     MMG_GSTAMP(3); if (tid == 0) { MMG_GT(2048 + 16 * b + 10); }
     // ---- the gradient tapes of the live steps: bases x coefficients (stores only; the recurrence below does not wait for them)
-    {
-        const float* c1r = s_cf, *c2r = s_cf + TMAX, *c1z = s_cf + 2 * TMAX, *c2z = s_cf + 3 * TMAX;
-#pragma unroll
-        for (int u = 0; u < NS_; ++u) {
-            const int i = tid + NT * u, t = i / W, j = i - t * W;
-            if (t <= tstar) {
-                const size_t row = (size_t)t * B + b;
-                tp.dlw[row * W + j] = fmaf(c1r[t], s1w[u], c2r[t] * s2w[u]);
-                tp.dlz[row * W + j] = fmaf(c1z[t], s1z[u], c2z[t] * s2z[u]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = 4 * fq + r;
-            if (t <= tstar) tp.dgpre[((size_t)t * B + b) * R + unit] = fmaf(c1r[t], g1[r], c2r[t] * g2[r]);
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            const int hcol = 64 * wv + 16 * nt + fi;
-            float part = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 4 * fq + r;
-                if (t <= tstar) {
-                    const float v = fmaf(c1z[t], p1[nt][r], c2z[t] * p2[nt][r]);
-                    tp.dpre[((size_t)t * B + b) * H + hcol] = v;
-                    part += v;
-                }
-            }
-            part += __shfl_xor(part, 16); part += __shfl_xor(part, 32);       // the four row groups of the column
-            if (fq == 0) tp.dhx[(size_t)b * H + hcol] = part;
-        }
-    }
-    // ---- the recurrence: two phases and ONE barrier per step (kernels_fast.h)
-    auto step_in = [&](int t) {
-        float v = fmaf(s_cf[t], s_dhin[t * R + k4], s_cf[TMAX + t] * s_H2[t * R + k4]) + wsk * s_dls[t];
-        if (t == tstar) v += s_dAy[k4];
-        return v;
-    };
-    float dh_c = 0.f;
-    for (int t = tstar; t >= 0; --t) {
-        const size_t row = (size_t)t * B + b;
-        float* const dgb = s_dghb + (t & 1) * 3 * R;
-        MMG_GSTAMP(16 + 2 * t);
-        const float dh = dh_c + step_in(t);
-        const float* gr = t_gru + t * 4 * R;
-        const float rr = gr[k4], uu = gr[R + k4], nn = gr[2 * R + k4], ghn = gr[3 * R + k4];
-        {
-            const float hp = t_h[t * R + k4];
-            const float dn = dh * (1.f - uu), du = dh * (hp - nn);
-            const float dnp = dn * (1.f - nn * nn), dup = du * uu * (1.f - uu);
-            const float drp = dnp * ghn * rr * (1.f - rr);
-            float* gi = tp.dgi + row * 3 * R; float* gh = tp.dgh + row * 3 * R;
-            static_assert(K4 == 4, "four lanes per unit share the stores");
-            const float vi = (p4 == 0) ? drp : (p4 == 1) ? dup : dnp;
-            const float vh = (p4 == 2) ? dnp * rr : vi;
-            const int idx = p4 * R + k4;
-            if (p4 < 3) { gi[idx] = vi; gh[idx] = vh; dgb[idx] = vh; }
-        }
-        __syncthreads(); MMG_GSTAMP(16 + 2 * t + 1);
-        {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 3 * R / K4; i += 4) {
-                const float4 dv = *reinterpret_cast<const float4*>(dgb + p4 * (3 * R / K4) + i);
-                a0 = fmaf(whhT[i], dv.x, a0); a1 = fmaf(whhT[i + 1], dv.y, a1);
-                a2 = fmaf(whhT[i + 2], dv.z, a2); a3 = fmaf(whhT[i + 3], dv.w, a3);
-            }
-            const float acc = lane_group_sum<K4>((a0 + a1) + (a2 + a3));
-            dh_c = __fmul_rn(dh, uu) + acc;
-        }
-    }
+    store_grad_tapes<W, R, H, NT, TMAX>(s_cf, s1w, s2w, s1z, s2z, g1, g2, p1, p2, tp.dlw, tp.dlz, tp.dgpre, tp.dpre, tp.dhx, B, b, tstar, tid, wv, fi, fq);
+    // ---- the recurrence: two phases and ONE barrier per step
+    recurrence_one_barrier<R, K4, TMAX>(whhT, t_gru, t_h, s_cf, s_dhin, s_H2, s_dls, s_dAy, wsk, s_dghb, tp.dgi, tp.dgh, B, b, tstar, k4, p4,
+                                        [&](int slot) { MMG_GSTAMP(slot); });
     MMG_GSTAMP(4); if (tid == 0) { MMG_GT(2048 + 16 * b + 11); tp.dbg2[2048 + 16 * b + 12] = (long long)tstar; }
 }
 

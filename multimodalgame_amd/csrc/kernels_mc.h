@@ -719,7 +719,10 @@ __global__ __launch_bounds__(256, 1) void k_bwd_mc2(Dims dm, Params P, Tape tp, 
         if (tid < 3 * R) { tp.dgi[row * 3 * R + tid] = 0.f; tp.dgh[row * 3 * R + tid] = 0.f; }
     }
     __syncthreads();
-    // ---- the recurrence: [cell backward] barrier [W_hh^T dgh] barrier (k_bwd_sample)
+    // ---- the recurrence: [cell backward] barrier [W_hh^T dgh] barrier.  A deliberate COPY of bwd_sample_parts.h's
+    // recurrence_two_barrier without the dhin term (as are the fragment loads, the gru / h staging and W_y1h^T dA above: load_whhT_y1T,
+    // stage_gru_h, y1hT_dA): calling the shared pieces timed outside this copy's own run-to-run spread at config 5
+    // (profiles/bwd_parts_bench_ab.txt).  Change the two together.
     for (int t = tstar; t >= 0; --t) {
         const size_t row = (size_t)t * B + b;
         const float din = (t == tstar) ? s_dAy[k4] : 0.f;

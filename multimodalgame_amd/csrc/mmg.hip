@@ -16,6 +16,7 @@
 #include "device_utils.h"
 #include "kernels_fwd.h"
 #include "kernels_bwd.h"
+#include "bwd_sample_parts.h"
 #include "kernels_fast.h"
 #include "kernels_fast3.h"
 #include "kernels_game.h"
