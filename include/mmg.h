@@ -256,6 +256,37 @@ int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, int ignore_r
  * handle with message flips or a sender variant (their setters refuse a relaxed handle likewise); an attention handle. */
 int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float tau_rec, int hard);
 
+/* Gaussian message noise: an additive white Gaussian noise channel for CONTINUOUS messages (use_binary == 0), the continuous twin of
+ * mmg_set_message_flipout; the reference has no such option.  With lz_t / lw_t the logits the conversation forms today (in continuous
+ * mode they are the messages), the sender's message of step t becomes z_t = lz_t + sigma_sen * n_z[t, b, j] and the receiver's
+ * w_t = lw_t + sigma_rec * n_w[t, b, j], n standard normal.  The noisy value IS the message: the receiver's GRU, the sender's code
+ * input of step t + 1, the tape arrays "z" / "w" / "zr", the backward pass, every VJP and mmg_eval_steps read it.  The constant
+ * first_rec in front of step 0 is no message and takes no noise.  The noise is added where the message is formed; a mask of
+ * mmg_set_message_corruption is applied after it (|z + sigma n - m|).  Training conversations always take the noise; evaluation
+ * conversations only with noise_dev != 0.  A sigma of 0 leaves that message clean; both 0 clears the setting.
+ * Draws: one Philox4x32-10 block per element, counter (e, c1, stream, 0), 64-bit key, as the Bernoulli draws build it; its first two
+ * output words x0, x1 give u1 = ((x0 >> 8) + 1) 2^-24 in (0, 1], u2 = (x1 >> 8) 2^-24 in [0, 1) and n = sqrt(-2 ln u1) cos(2 pi u2),
+ * so |n| <= 5.77.  e = (t * B_global + batch_offset + b) * W + j is the element index of the Bernoulli draws: a data-parallel shard
+ * draws what the single-GPU batch draws.
+ *   training:   streams 7 (sender) / 8 (receiver), key = the call's seed, c1 = the minibatch counter of the Bernoulli draws -- also
+ *               when d_u_z / d_u_s / d_u_w are injected;
+ *   evaluation: streams 9 / 10, key = eval_seed, c1 = the number of evaluation conversations enqueued on this handle since this call
+ *               (counted on the host; the device-side minibatch counter stays untouched).  The agent-level entries draw with the
+ *               count of the conversation the last mmg_sender_forward(t = 0, train = 0) began.
+ * Gradients: d z / d lz = 1, so every backward entry works unchanged on the tape's noisy messages -- the REINFORCE step (continuous
+ * mode updates the receiver alone), mmg_exchange_vjp, mmg_exchange_vjp_channel (exact here, no surrogate: the gradient crosses the
+ * channel unchanged), the per-call VJPs and mmg_vjp_input_grads.  mmg_dp_train_step[s], mmg_eval_steps, the corruption mask and the
+ * training controls work on a noise handle.  A flip setting on the same (continuous) handle keeps doing nothing.
+ * Kernels: a noise handle runs k_conversation_noise (the generic per-sample family: -> k_bwd_conv -> k_dC -> k_wgrad; the agent-level
+ * entries too) or, for the small agents with many classes, k_conversation_mc3_noise with that family's backward; the register-resident,
+ * pair (mc3p), sample-tile and wide-receiver conversations form no noise.  Host only: the kernel selection is re-run only when the
+ * noisy STATE changes, so the call may precede every minibatch to anneal the sigmas; it resets the evaluation count.  Clearing
+ * restores the original selection.
+ * Returns 0, or negative (the setting before stays): a sigma that is negative, infinite or NaN; use_binary == 1
+ * (mmg_set_message_flipout is the binary counterpart); an attention handle; a handle with a sender variant (mmg_set_sender_variant
+ * refuses a noise handle likewise). */
+int mmg_set_message_noise(mmg_handle* h, float sigma_sen, float sigma_rec, int noise_dev, uint64_t eval_seed);
+
 /* Training controls of a live handle: which agents the REINFORCE step updates, and the values of the learning rate and of the entropy
  * weights (model.py:1307-1330 with optimizer.step() of a frozen agent not called; the reference has no such switches).  The calls
  * enqueue nothing and synchronise nothing, and the kernel family of the handle stays.  mmg_set_learning_rate and mmg_set_entropy change
@@ -490,7 +521,7 @@ int mmg_degraded(const mmg_handle* h);
  *                  then one line with the caps it probed, in MMG_CAP_* order.
  *   mmg_plan_for:  the same text for a config and caller-supplied caps (n_caps == MMG_PLAN_CAPS), under the environment of the
  *                  call: no handle, no buffers, no GPU.  flags: bit 0 = no in-launch waits (what MMG_NO_ROLES=1 or a recovery
- *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set, bit 3 = messages are relaxed, bits 4-7 = bit 4 + MMG_AGENT_* set: that agent is frozen (mmg_set_trainable; its jobs leave k_wgrad's table: "gemm tiles", "blocks").  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
+ *                  selects), bit 1 = message flips are set, bit 2 = a sender variant is set, bit 3 = messages are relaxed, bits 4-7 = bit 4 + MMG_AGENT_* set: that agent is frozen (mmg_set_trainable; its jobs leave k_wgrad's table: "gemm tiles", "blocks"), bit 8 = Gaussian message noise is set (the text then has one more line, in front of the caps).  cfg->cu_budget lowers caps[MMG_CAP_N_CU] as it lowers the device's.
  * Both return 0, or negative (out too small: about 2 KB are needed; a config the library refuses). */
 enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP_RC_PERSIST, MMG_CAP_MC, MMG_CAP_MC3, MMG_CAP_MC3P,
        MMG_CAP_GAME, MMG_CAP_WGRAD_OPT, MMG_CAP_WGRAD, MMG_PLAN_CAPS };

@@ -54,7 +54,7 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_attn_param_table", "mmg_attn_workspace_bytes", "mmg_attn_tape_table", "mmg_attn_create", "mmg_set_desc_set",
            "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
            "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation",
-           "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls"]
+           "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls", "mmg_set_message_noise"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
@@ -66,6 +66,7 @@ VATTN_MAX_CHANNELS = 4096      # feat_dim of the map
 PLAN_CAPS = ("n_cu", "split", "persist", "rc_bwd", "rc_persist", "mc", "mc3", "mc3p", "game", "wgrad_opt", "wgrad")
 PLAN_NO_ROLES, PLAN_FLIPS, PLAN_VARIANT, PLAN_RELAX = 1, 2, 4, 8        # flags of mmg_plan_for
 PLAN_FROZEN_SHIFT = 4                   # ... and agent_mask(frozen agents) << PLAN_FROZEN_SHIFT: the plan with those agents frozen
+PLAN_NOISE = 256                        # ... and Gaussian message noise is set (bits 4-7 are the frozen agents')
 MIX = {"sum": 0, "prod": 1}             # mmg_set_sender_variant's mix (include/mmg.h: MMG_MIX_SUM, MMG_MIX_PROD)
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
@@ -120,6 +121,7 @@ def load():
     lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
     lib.mmg_set_sender_variant.restype = i32; lib.mmg_set_sender_variant.argtypes = [vp, i32, i32, i32]
     lib.mmg_set_message_relaxation.restype = i32; lib.mmg_set_message_relaxation.argtypes = [vp, C.c_float, C.c_float, i32]
+    lib.mmg_set_message_noise.restype = i32; lib.mmg_set_message_noise.argtypes = [vp, C.c_float, C.c_float, i32, u64]
     lib.mmg_set_trainable.restype = i32; lib.mmg_set_trainable.argtypes = [vp, i32]
     lib.mmg_set_learning_rate.restype = i32; lib.mmg_set_learning_rate.argtypes = [vp, C.c_float]
     lib.mmg_set_entropy.restype = i32; lib.mmg_set_entropy.argtypes = [vp, C.c_float, C.c_float, C.c_float]

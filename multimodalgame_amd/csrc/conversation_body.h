@@ -1,4 +1,4 @@
-// conversation_body.h -- the text of k_conversation.  NOT a header of its own: kernels_fwd.h includes it twice, with MMG_CONV_ATTN 0 for
+// conversation_body.h -- the text of k_conversation.  NOT a header of its own: kernels_fwd.h includes it four times, with MMG_CONV_ATTN 0 for
 // k_conversation<NT, FLIP, VAR, RELAX> -- token for token the kernel every plain handle has always run, so its instantiations keep their symbols,
 // arguments and code -- and with MMG_CONV_ATTN 1 for k_conversation_attn<NT>, the instantiation of an attention handle (mmg_attn_create;
 // model.py:344-410, 444-445): the receiver attends over the words of every description with its GRU state as the query.  `at` carries the
@@ -13,17 +13,25 @@
 // Per step, in front of the tanh site:
 //   t == 0: alpha = 1 / N;   t >= 1: q = attn_W_w(w);  beta[i] = attn_U(tanh(q + HX[i] + HG));  alpha = softmax_i beta
 //   x_attn = sum_i alpha[i] x[:, i];   h_x = image_layer(x_attn)        -- h_x is per STEP here (tape: vattn_hx), tape.hx is not read
+// A fourth inclusion, with MMG_CONV_NOISE 1, is k_conversation_noise<NT>, the instantiation of a continuous handle with Gaussian message noise
+// (mmg_set_message_noise): noise_msg at both message sites of the continuous branch, in front of corrupt_msg.  A kernel of its own name, so
+// that k_conversation<NT, FLIP, VAR, RELAX> keeps its symbols as well as its code.
 #if MMG_CONV_VATTN
 template <int NT>
 __global__ __launch_bounds__(NT) void k_conversation_vattn(Dims dm, Params P, Tape tp, ConvArgs ar, VattnArgs va) {
-    constexpr bool FLIP = false, VAR = false, RELAX = false;
+    constexpr bool FLIP = false, VAR = false, RELAX = false, NOISE = false;
 #elif MMG_CONV_ATTN
 template <int NT>
 __global__ __launch_bounds__(NT) void k_conversation_attn(Dims dm, Params P, Tape tp, ConvArgs ar, AttnArgs at) {
-    constexpr bool FLIP = false, VAR = false, RELAX = false;
+    constexpr bool FLIP = false, VAR = false, RELAX = false, NOISE = false;
+#elif MMG_CONV_NOISE
+template <int NT>
+__global__ __launch_bounds__(NT) void k_conversation_noise(Dims dm, Params P, Tape tp, ConvArgs ar) {
+    constexpr bool FLIP = false, VAR = false, RELAX = false, NOISE = true;
 #else
 template <int NT, bool FLIP = false, bool VAR = false, bool RELAX = false>
 __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp, ConvArgs ar) {
+    constexpr bool NOISE = false;
 #endif
     constexpr int GU = NT == 512 ? 8 : 4;               // row passes per load batch of gemv_rows
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -203,6 +211,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                         lpv = zz * l1 + (1.f - zz) * l0;           // model.py:908-910
                         nev = p * l1 + (1.f - p) * l0;             // model.py:919-922
                     }
+                    if (NOISE && !binary) zz = noise_msg(ar, false, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, zz);   // the channel sits inside the agent: before the mask
                     zz = corrupt_msg(ar, n, zz);                   // model.py:813-820 (evaluation only)
                     s.z[n] = zz; s.lp[n] = lpv; s_ne[n] = nev;
                     tp.z[row * W + n] = zz;
@@ -453,6 +462,7 @@ __global__ __launch_bounds__(NT) void k_conversation(Dims dm, Params P, Tape tp,
                     lpv = wv * l1 + (1.f - wv) * l0;
                     nev = p * l1 + (1.f - p) * l0;
                 }
+                if (NOISE && !binary) wv = noise_msg(ar, true, (uint32_t)((t * dm.Bg + gb) * W + n), mb_counter, wv);
                 s.w[n] = wv; s.lp[n] = lpv; s_ne[n] = nev;
                 tp.w[row * W + n] = wv;
             }

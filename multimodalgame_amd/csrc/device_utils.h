@@ -320,6 +320,20 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t c0, uint
     }
     return (float)(x0 >> 8) * (1.0f / 16777216.0f);
 }
+// ... the same block, its first two output words (kernels_fwd.h: noise_msg forms a normal draw from them; tests/noise_ref.py)
+__device__ __forceinline__ void philox_pair(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t& o0, uint32_t& o1) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1;
+        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
+        x0 = y0; x1 = y1; x2 = y2; x3 = y3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    o0 = x0; o1 = x1;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Dependencies between workgroup ROLES of one launch.  Several small kernels of the minibatch are latency

@@ -68,7 +68,7 @@ struct LaunchPlan {
 // What select_paths decided (host_select.h): which kernels serve this handle's shape on this device, their LDS sizes, the co-residency budgets, the
 // family and the launch plan.  Filled in three steps -- shape_pass (pure: everything up to the candidates that wait for a budget, and `ask`),
 // probe_device (`caps`), decide (pure: the rest) -- and printed by plan_text.  Constant until the next selection (mmg_create; error_gate after a
-// timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation when the routing changes).
+// timed-out dependency; mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation / mmg_set_message_noise when the routing changes).
 struct Selection {
     int conv_smem = 0, conv_smem_agent = 0, conv_threads = 0, bwd_smem = 0, prep_smem = 0, prep_cpb = 1;
     int vattn_bwd_smem = 0;      // dynamic LDS of k_vattn_bwd (a visual-attention handle)
@@ -84,6 +84,8 @@ struct Selection {
     bool vattn = false;          // a visual-attention handle (mmg_vattn_create): the generic per-sample family with k_conversation_vattn serves it, nothing else
     bool relax = false;          // relaxed messages are set (mmg_set_message_relaxation): the generic per-sample family with k_conversation<NT, false, false, RELAX>
                                  // serves the handle, nothing else; its backward pass is mmg_exchange_vjp_channel (k_vjp_channel_relax) only
+    bool noise = false;          // Gaussian message noise is set on a continuous handle (mmg_set_message_noise): k_conversation_noise<NT> and, where the shape has it,
+                                 // k_conversation_mc3_noise serve it, nothing else; every backward / VJP kernel reads the noisy messages from the tape
     int variant = 0;             // the sender variant in effect (mmg_set_sender_variant; SV_* bits, SV_IGNORE_REC on a binary handle only): != 0: the generic
                                  // per-sample family with k_conversation<NT, false, VAR> / k_bwd_conv<MANY, VAR> serves the handle, nothing else
     bool use_fast = false;       // debugging switches, read once at mmg_create: MMG_NO_FAST=1 forces the generic kernels,
@@ -174,6 +176,12 @@ struct mmg_handle {
     float flip_p_sen = 0.f, flip_p_rec = 0.f;
     uint64_t flip_eval_seed = 0;
     uint32_t flip_evals = 0;
+    // mmg_set_message_noise: additive Gaussian noise on continuous messages (both sigmas 0: not set).  Host state; noise_args copies it into the
+    // launch arguments of every forward entry.  noise_evals: evaluation conversations enqueued since the setter call (their Philox counter)
+    float noise_sigma_sen = 0.f, noise_sigma_rec = 0.f;
+    bool noise_dev = false;
+    uint64_t noise_eval_seed = 0;
+    uint32_t noise_evals = 0;
     // mmg_set_sender_variant: SV_* bits as the caller set them (layout.h).  Host state; what is in effect on this handle is sel.variant, which the
     // forward entries copy into ConvArgs::sender_var and the backward / sender-VJP launches pass as sv
     int sender_var = 0;

@@ -35,7 +35,7 @@ static bool merge_stats(const mmg_handle* h) {
 static Family select_family(const Selection& s, const Dims& d) {
     const bool forced = s.tile_ok && s.tile_force;
     // (D = 30: own instantiation, other D <= 32: capacity 32; V = 100 likewise, other V % 4 == 0: at run time)
-    const bool fast = !forced && s.use_fast && d.H == 256 && d.W == 32 && d.R == 64 && (d.V == 100 || fast_wide_v(d.V)) && d.D <= 32 && d.T <= 16;
+    const bool fast = !forced && s.use_fast && !s.noise && d.H == 256 && d.W == 32 && d.R == 64 && (d.V == 100 || fast_wide_v(d.V)) && d.D <= 32 && d.T <= 16;
     const bool mc = s.mc_ok && !forced && (d.B <= 2048 || !s.tile_ok);
     return (s.tile_ok && !fast && !mc) ? FAM_TILE : mc ? FAM_MC : fast ? FAM_FAST : FAM_GENERIC;
 }
@@ -142,7 +142,11 @@ static void plan_launches(mmg_handle* h) {
         p.conv_fn = s.conv_threads == 512 ? k_conversation<512, false, false, true> : k_conversation<256, false, false, true>;
         p.agent_fn = k_conversation<256, false, false, true>;
     }
-    p.conv_name = s.vattn ? "k_conversation_vattn" : wide ? "k_conversation_wv" : "k_conversation";     // (the profiling scope says which sender ran)
+    if (s.noise) {                               // Gaussian message noise: the NOISE instantiations (shape_pass has cleared every other conversation kernel but mc3)
+        p.conv_fn = s.conv_threads == 512 ? k_conversation_noise<512> : k_conversation_noise<256>;
+        p.agent_fn = k_conversation_noise<256>;
+    }
+    p.conv_name = s.vattn ? "k_conversation_vattn" : s.noise ? "k_conversation_noise" : wide ? "k_conversation_wv" : "k_conversation";     // (the profiling scope says which sender ran)
     p.bwd_name = wide ? "k_bwd_conv_wv" : "k_bwd_conv";
     // ---- baselines (training minibatch that did not run all rows) ----
     // Fused step: the baselines' live-row pass (k_baselines3's body) as workgroup roles of the backward launch, beside the sample
@@ -211,7 +215,7 @@ static void plan_launches(mmg_handle* h) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation change the
+// Path selection: which kernels serve this handle's shape on this device.  Runs at mmg_create, when mmg_set_message_flipout / mmg_set_sender_variant / mmg_set_message_relaxation / mmg_set_message_noise change the
 // routing, and again when the library falls back to launches WITHOUT in-launch waits (h->no_roles: after a timed-out dependency, for a CU
 // budget / CU mask that cannot hold the role launches, or MMG_NO_ROLES=1).  Four steps, in this order:
 //   read_switches   the environment, once per selection -- never on the per-minibatch path, and nowhere else in the library
@@ -241,10 +245,10 @@ static Switches read_switches() {
 }
 
 // Pure.  Everything Dims, the switches and the handle's flags (no_roles; flips: message flips are set; variant: the SV_* bits of
-// mmg_set_sender_variant; relax: relaxed messages are set; err_word: the pinned error word exists)
+// mmg_set_sender_variant; relax: relaxed messages are set; noise: Gaussian message noise is set; err_word: the pinned error word exists)
 // settle alone.  A capability that also needs a co-residency budget (tile_split, tile_persist, mc_ok) leaves here as a CANDIDATE: its
 // preconditions hold and s.ask names the occupancy it waits for; decide() confirms or clears it.
-static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool relax, bool err_word,
+static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, bool no_roles, bool flips, int variant, bool relax, bool noise, bool err_word,
                       Selection& s, int attn_dim = 0, int n_words = 0, VattnDims vd = VattnDims()) {
     s = Selection();
     // visual attention: the generic per-sample family with the sender's VATTN instantiation; every other family is cleared below
@@ -263,6 +267,11 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // many-class, sample-tile and wide-receiver conversations
     s.relax = relax && d.use_binary;
     if (s.relax && (s.flip || s.variant || s.attn || s.vattn)) return fail("relaxed messages with message flips, a sender variant or attention");
+    // Gaussian noise on continuous messages (binary ones take none: the setter refuses them): k_conversation_noise forms it and, for the small
+    // agents with many classes, k_conversation_mc3_noise -- the register-resident conversation, the sample tiles, the wide receiver and the pair
+    // kernel (mc3p) do not, so they are cleared below and in select_family; mc stays a candidate and decide() keeps it only with mc3
+    s.noise = noise && !d.use_binary;
+    if (s.noise && (s.variant || s.attn || s.vattn)) return fail("message noise with a sender variant or attention");
     s.use_fast = !w[SW_NO_FAST] && !s.variant && !s.relax && !s.attn && !s.vattn; s.merge_roles = !w[SW_NO_MERGE] && !no_roles;
     s.sw_merge_prep = !w[SW_NO_MERGE_PREP] && !no_roles;
     s.sw_merge_bas = s.merge_roles;
@@ -312,7 +321,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     // (the sample tiles keep a [16, V] mixture tile and V-wide split-K staging in LDS: audited and tested up to V = 256, the
     //  limit before MMG_MAX_WV; wider descriptions take the register-resident small agents or the per-sample kernels)
     // (message flips: k_conversation_fast3 and k_conversation form them, the sample tiles and the wide receiver do not)
-    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.relax && !s.attn && !s.vattn;
+    s.tile_ok = aligned && d.V <= 256 && (s.tile_smem <= 160 * 1024 || s.rc_fwd) && !w[SW_NO_TILE] && !s.flip && !s.variant && !s.relax && !s.attn && !s.vattn && !s.noise;
     s.tile_force = w[SW_TILE];
     // many classes, small agents, fewer than 64 tiles: a workgroup per SAMPLE fills the chip (256 samples = 256 CUs) and
     // beats 16 tiles + class helpers (measured at D = 1000, B = 256: 557 us against 1 010 us per minibatch; B = 2048:
@@ -351,7 +360,7 @@ static int shape_pass(const mmg_config& cfg, const Dims& d, const Switches& w, b
     ask[MMG_CAP_MC] = s.mc_ok;
     ask[MMG_CAP_MC3] = s.mc_ok && !d.use_binary;
     // two tiles per workgroup (kernels_mc3p.h): from 512 samples on, where the one-tile kernel needs several rounds of workgroups
-    ask[MMG_CAP_MC3P] = ask[MMG_CAP_MC3] && mc3p_shape(d.B, d.T, d.D) && !w[SW_NO_MC3P];
+    ask[MMG_CAP_MC3P] = ask[MMG_CAP_MC3] && mc3p_shape(d.B, d.T, d.D) && !w[SW_NO_MC3P] && !s.noise;
     // fused step of the small Adaptive agents (kernels_game.h)
     ask[MMG_CAP_GAME] = s.use_fast && s.merge_roles && s.sw_merge_prep && s.sw_merge_bas && d.H == 256 && d.W == 32 && d.R == 64 && d.V == 100 &&
                         d.D <= 32 && d.T <= 15 && d.B <= 64 && d.use_binary && !d.fixed && (d.K + 63) / 64 <= 8 && d.K <= 512 &&
@@ -399,7 +408,8 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     if (s.tile_ok && s.tile_smem > 48 * 1024 && !s.rc_fwd) raise_lds(s.tile_smem, k_conv_tile<256>, k_conv_tile<512>);
     occupancy(MMG_CAP_MC, k_conversation_mc<256, 32, 64, 100, 64>, 512, 0);
     if (s.ask[MMG_CAP_MC3]) raise_lds(mc3_lds_bytes(), k_conversation_mc3<256, 32, 64, 100, 64>);
-    occupancy(MMG_CAP_MC3, k_conversation_mc3<256, 32, 64, 100, 64>, 256, mc3_lds_bytes());
+    if (s.ask[MMG_CAP_MC3] && s.noise) raise_lds(mc3_lds_bytes(), k_conversation_mc3_noise<256, 32, 64, 100, 64>);
+    occupancy(MMG_CAP_MC3, s.noise ? k_conversation_mc3_noise<256, 32, 64, 100, 64> : k_conversation_mc3<256, 32, 64, 100, 64>, 256, mc3_lds_bytes());
     if (s.ask[MMG_CAP_MC3P]) raise_lds(mc3p_lds_bytes(d.T), k_conversation_mc3p<256, 32, 64, 100, 64>);
     occupancy(MMG_CAP_MC3P, k_conversation_mc3p<256, 32, 64, 100, 64>, 256, mc3p_lds_bytes(d.T));
     raise_lds(fast3_lds_bytes(), k_conversation_fast3<256, 32, 64, 100, false>, k_conversation_fast3<256, 32, 64, 100, true>);
@@ -414,6 +424,7 @@ static int probe_device(const mmg_config& cfg, const Dims& d, Selection& s) {
     if (s.conv_smem > 48 * 1024 && s.flip) raise_lds(s.conv_smem, k_conversation<256, true>, k_conversation<512, true>);
     if (s.conv_smem > 48 * 1024 && s.variant) raise_lds(s.conv_smem, k_conversation<256, false, true>, k_conversation<512, false, true>);
     if (s.conv_smem > 48 * 1024 && s.relax) raise_lds(s.conv_smem, k_conversation<256, false, false, true>, k_conversation<512, false, false, true>);
+    if (s.conv_smem > 48 * 1024 && s.noise) raise_lds(s.conv_smem, k_conversation_noise<256>, k_conversation_noise<512>);
     if (s.conv_smem > 48 * 1024 && s.attn) raise_lds(s.conv_smem, k_conversation_attn<256>, k_conversation_attn<512>);
     if (s.bwd_smem > 48 * 1024 && s.attn) raise_lds(s.bwd_smem, k_bwd_conv_attn);
     if (s.conv_smem > 48 * 1024 && s.vattn) raise_lds(s.conv_smem, k_conversation_vattn<256>, k_conversation_vattn<512>);
@@ -469,6 +480,7 @@ static int decide(mmg_handle* h, const Switches& w) {
         if (mc_budget < 16) s.mc_ok = false;
         s.mc3_ok = s.mc_ok && !d.use_binary && budget_of(MMG_CAP_MC3) >= (s.mc_xcd ? 128 : 16);
         s.mc3p_ok = s.mc3_ok && s.mc_xcd && s.ask[MMG_CAP_MC3P] && budget_of(MMG_CAP_MC3P) >= 128;
+        if (s.noise && !s.mc3_ok) s.mc_ok = false;       // (k_conversation_mc forms no noise: the generic family instead)
     }
     if (s.ask[MMG_CAP_GAME]) {
         // every spinning role must be resident together with the sample roles (the sample roles wait for the statistics roles,
@@ -512,7 +524,8 @@ static int decide(mmg_handle* h, const Switches& w) {
 
 static int shape_pass(mmg_handle* h, const Switches& w) {
     h->no_roles = h->no_roles || w.roles_off();
-    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->relax_tau_sen > 0.f, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words, h->vd);
+    return shape_pass(h->cfg, h->dm, w, h->no_roles, h->flip_sen || h->flip_rec, h->sender_var, h->relax_tau_sen > 0.f,
+                      h->noise_sigma_sen > 0.f || h->noise_sigma_rec > 0.f, h->d_err != nullptr, h->sel, h->attn_dim, h->n_words, h->vd);
 }
 static int select_paths(mmg_handle* h) {
     const Switches w = read_switches();
@@ -555,6 +568,8 @@ static int plan_text(const mmg_handle* h, char* out, int out_bytes) {
          p.mc_grid, s.mc_xcd, (int)s.mc3_ok, (int)s.mc3p_ok, (int)p.mc3p_wins, p.mc3p_grid, (int)p.merge_prep, p.nprep_hx, (int)p.fwd_basehx, (int)p.bas_defer_ok, (int)p.bas_pending_ok, (int)p.bas_kernel);
     line("mmg_create: backward: row_map %d zero_dead %d merged_send %d pre_bands %d receiver %d (0 sample, 1 tile, 2 rc) n_dbar %d class roles %d k_dC %d (0 none, 1 tile, 2 plain) mc groups %d\n",
          (int)p.row_map, (int)p.zero_dead, (int)p.merged_send, p.pre_bands, (int)p.bwd_rec, p.n_dbar, p.n_class, (int)p.dc, p.mc_ngroup);
+    if (s.noise) line("mmg_create: message noise: %s serves the conversation, k_conversation_noise the agent-level entries\n",
+                      s.family == FAM_MC ? "k_conversation_mc3_noise" : "k_conversation_noise");
     const int32_t* c = s.caps;
     line("mmg_create: caps n_cu %d split %d persist %d rc_bwd %d rc_persist %d mc %d mc3 %d mc3p %d game %d wgrad_opt %d wgrad %d\n",
          c[MMG_CAP_N_CU], c[MMG_CAP_SPLIT], c[MMG_CAP_PERSIST], c[MMG_CAP_RC_BWD], c[MMG_CAP_RC_PERSIST], c[MMG_CAP_MC], c[MMG_CAP_MC3], c[MMG_CAP_MC3P],

@@ -385,6 +385,10 @@ struct ConvArgs {
     float flip_pz, flip_pw;    // flip probabilities of the sender's / the receiver's message bits
     uint32_t flip_c1;          // evaluation: conversations enqueued on the handle since the setter call
     uint64_t flip_key;         // Philox key of the flip draws: the call's seed (training) / the setter's eval_seed
+    // mmg_set_message_noise (continuous messages only) travels in the SAME five fields: flips act on binary handles and noise on continuous
+    // ones, so the host fills one set per call (mmg.hip: flip_args / noise_args) and only the NOISE instantiations read them as noise --
+    // flip_on: bit 0 the sender's message is noisy, bit 1 the receiver's, bit 2 an evaluation conversation's draws (streams 9 / 10 and
+    // flip_c1; else 7 / 8 and the minibatch counter); flip_pz / flip_pw: sigma_sen / sigma_rec; flip_key: the key.  ConvArgs keeps its size
     // mmg_set_message_relaxation: read by the RELAX instantiations only, in training conversations only.  The temperatures of the sender's
     // z and of the receiver's w; relax_hard: the message is the bit (straight-through), else the soft value
     float relax_tau_z, relax_tau_w;
@@ -421,6 +425,23 @@ __device__ __forceinline__ float flip_msg(const ConvArgs& ar, bool rec, uint32_t
     const float u = philox_uniform(ar.flip_key, e, ev ? ar.flip_c1 : mb, (ev ? 5u : 3u) + (rec ? 1u : 0u));
     return fabsf(z - ((u < (rec ? ar.flip_pw : ar.flip_pz)) ? 1.f : 0.f));
 }
+
+// Additive Gaussian noise (mmg_set_message_noise) on entry e = (t * B_global + b_global) * W + j of a CONTINUOUS message: v + sigma n,
+// n the Box-Muller normal of the first two words of the element's Philox block (device_utils.h: philox_pair) --
+// u1 = ((x0 >> 8) + 1) 2^-24 in (0, 1], u2 = (x1 >> 8) 2^-24 in [0, 1), n = sqrt(-2 ln u1) cos(2 pi u2), |n| <= 5.77.  v_cos_f32 takes
+// its input in turns: the cosine is one instruction on u2.  Call it where the message is formed, BEFORE corrupt_msg, the tape and
+// anything another consumer reads.  rec: the receiver's message (bit 1, streams 8 / 10), else the sender's (bit 0, streams 7 / 9).
+// mb: the minibatch counter of the kernel's Bernoulli draws.  The setting rides in the flip fields (ConvArgs).  noise_term is the draw
+// alone, sigma n (0 where that message is clean): it depends on no activation, so a kernel may form it ahead of the message.
+__device__ __forceinline__ float noise_term(const ConvArgs& ar, bool rec, uint32_t e, uint32_t mb) {
+    if (!(ar.flip_on & (rec ? 2 : 1))) return 0.f;
+    const bool ev = (ar.flip_on & 4) != 0;
+    uint32_t x0, x1;
+    philox_pair(ar.flip_key, e, ev ? ar.flip_c1 : mb, (ev ? 9u : 7u) + (rec ? 1u : 0u), x0, x1);
+    const float u1 = (float)((x0 >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(x1 >> 8) * (1.0f / 16777216.0f);
+    return (rec ? ar.flip_pw : ar.flip_pz) * (sqrtf(-2.f * logf(u1)) * __builtin_amdgcn_cosf(u2));
+}
+__device__ __forceinline__ float noise_msg(const ConvArgs& ar, bool rec, uint32_t e, uint32_t mb, float v) { return v + noise_term(ar, rec, e, mb); }
 
 struct ConvSmem {
     float *hx, *a, *c, *z, *w, *lp, *ne, *h, *hn, *A, *g, *g2, *gi, *gh, *y, *yout, *dbar, *red, *misc;
@@ -480,6 +501,13 @@ __host__ __device__ inline int conv_vattn_smem_floats(const Dims& d, int nthread
 #define MMG_CONV_VATTN 1
 #include "conversation_body.h"
 #undef MMG_CONV_VATTN
+#undef MMG_CONV_ATTN
+
+// Gaussian message noise (mmg_set_message_noise): the continuous handle's instantiation, k_conversation_noise<NT>
+#define MMG_CONV_ATTN 0
+#define MMG_CONV_NOISE 1
+#include "conversation_body.h"
+#undef MMG_CONV_NOISE
 #undef MMG_CONV_ATTN
 
 // out[(b, i), n] = sum_c x[b, c, i] Wm[n, c] + bias[n] over the M = B * NF rows (b, i): x is the feature map as the caller holds it,

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
@@ -425,6 +426,7 @@ extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_ca
     h->d_err = reinterpret_cast<uint32_t*>(base);           // (as a created handle has one; h_err stays NULL: nothing to release)
     h->no_roles = (flags & 1) != 0; h->flip_sen = (flags & 2) != 0; h->sender_var = (flags & 4) ? SV_PROD : 0;
     if (flags & 8) h->relax_tau_sen = h->relax_tau_rec = 1.f;
+    if (flags & 256) h->noise_sigma_sen = h->noise_sigma_rec = 1.f;      // bit 8: Gaussian message noise (mmg_set_message_noise)
     h->train_mask = 15 & ~(flags >> 4);                     // bits 4-7: frozen agents (mmg_set_trainable's mask, inverted)
     const Switches w = read_switches();
     if (shape_pass(h, w)) return -1;
@@ -509,6 +511,17 @@ static void flip_args(mmg_handle* h, ConvArgs& ar, uint64_t seed, int train, boo
     if (!train) ar.flip_c1 = new_conv ? h->flip_evals++ : (h->flip_evals ? h->flip_evals - 1u : 0u);
 }
 
+// Gaussian message noise of this call (mmg_set_message_noise), by value and in the flip fields (kernels_fwd.h: ConvArgs; a handle's flips
+// act on binary messages and its noise on continuous ones, so one of the two fills them): training conversations always, evaluation ones
+// under noise_dev.  new_conv as for flip_args.
+static void noise_args(mmg_handle* h, ConvArgs& ar, uint64_t seed, int train, bool new_conv) {
+    if (!h->sel.noise || (!train && !h->noise_dev)) return;
+    ar.flip_on = (h->noise_sigma_sen > 0.f ? 1 : 0) | (h->noise_sigma_rec > 0.f ? 2 : 0) | (train ? 0 : 4);
+    ar.flip_pz = h->noise_sigma_sen; ar.flip_pw = h->noise_sigma_rec;
+    ar.flip_key = train ? seed : h->noise_eval_seed;
+    if (!train) ar.flip_c1 = new_conv ? h->noise_evals++ : (h->noise_evals ? h->noise_evals - 1u : 0u);
+}
+
 // Relaxed messages of this call (mmg_set_message_relaxation), by value; only the RELAX instantiations read them, in training conversations
 static void relax_args(const mmg_handle* h, ConvArgs& ar) {
     if (!h->sel.relax) return;
@@ -589,10 +602,12 @@ static int launch_conv_tile(mmg_handle* h, hipStream_t st, ConvArgs ar) {
 // FAM_MC.  lean: the training-minimal continuous pass, the only one the pair kernel serves
 static int launch_conv_mc(mmg_handle* h, hipStream_t st, ConvArgs ar) {
     const Selection& s = h->sel; const LaunchPlan& p = s.plan;
-    Scope sc(h, st, "k_conversation_mc");
+    Scope sc(h, st, s.noise ? "k_conversation_mc3_noise" : "k_conversation_mc");
     ar.per = s.mc_per; ar.l2_handoff = (s.mc_xcd && h->xcd_rule_ok) ? 1 : 0;
     if (p.mc3p_wins && ar.lean)      // two sample tiles per workgroup, half a step apart (kernels_mc3p.h)
         hipLaunchKernelGGL((k_conversation_mc3p<256, 32, 64, 100, 64>), dim3(p.mc3p_grid), dim3(256), mc3p_lds_bytes(h->dm.T), st, h->dm, h->P, h->tp, ar, p.mc_ntile, ar.y_last_only);
+    else if (s.noise)                // (decide() keeps the family for a noise handle only with mc3)
+        hipLaunchKernelGGL((k_conversation_mc3_noise<256, 32, 64, 100, 64>), dim3(p.mc_grid), dim3(256), mc3_lds_bytes(), st, h->dm, h->P, h->tp, ar, p.mc_ntile, s.mc_xcd, ar.y_last_only);
     else if (s.mc3_ok)
         hipLaunchKernelGGL((k_conversation_mc3<256, 32, 64, 100, 64>), dim3(p.mc_grid), dim3(256), mc3_lds_bytes(), st, h->dm, h->P, h->tp, ar, p.mc_ntile, s.mc_xcd, ar.y_last_only);
     else
@@ -661,6 +676,7 @@ static int exchange_forward_impl(mmg_handle* h, const float* d_x, const int64_t*
     ar.lean = (mode == TAPE_MINIMAL && !d.use_binary) ? 1 : 0;
     if (h->corrupt_on) { ar.corrupt_on = 1; memcpy(ar.corrupt, h->corrupt, sizeof(ar.corrupt)); }
     flip_args(h, ar, seed, train, true);
+    noise_args(h, ar, seed, train, true);
     ar.sender_var = s.variant;
     relax_args(h, ar);
     h->fwd = ForwardState();
@@ -776,6 +792,8 @@ extern "C" int mmg_set_sender_variant(mmg_handle* h, int mix, int ignore_code, i
     if (want && refuse_attn(h, "mmg_set_sender_variant")) return -1;
     if (want && (h->flip_sen || h->flip_rec))
         return fail("mmg_set_sender_variant: the handle has message flips (mmg_set_message_flipout); flips and a variant do not combine");
+    if (want && (h->noise_sigma_sen > 0.f || h->noise_sigma_rec > 0.f))
+        return fail("mmg_set_sender_variant: the handle has message noise (mmg_set_message_noise); noise and a variant do not combine");
     if (want && h->relax_tau_sen > 0.f)
         return fail("mmg_set_sender_variant: the handle has relaxed messages (mmg_set_message_relaxation); the joint VJP does not form the variants");
     const int old_var = h->sender_var;
@@ -820,6 +838,39 @@ extern "C" int mmg_set_message_relaxation(mmg_handle* h, float tau_sen, float ta
         h->relax_tau_sen = o_sen; h->relax_tau_rec = o_rec; h->relax_hard = o_hard;
         select_paths(h);
         return fail("mmg_set_message_relaxation: %s", why.c_str());
+    }
+    if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
+        HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
+        HIP_OK(hipMemcpy(h->d_jt, &h->jt, sizeof(JobTable), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// Gaussian message noise (include/mmg.h): host state; re-runs the selection only when the noisy state itself changes, since a noise handle is
+// served by k_conversation_noise / k_conversation_mc3_noise only (host_select.h) -- a call that only moves the sigmas selects nothing.
+extern "C" int mmg_set_message_noise(mmg_handle* h, float sigma_sen, float sigma_rec, int noise_dev, uint64_t eval_seed) {
+    if (!h) return fail("NULL handle");
+    if (!(sigma_sen >= 0.f) || !(sigma_rec >= 0.f) || std::isinf(sigma_sen) || std::isinf(sigma_rec))          // (NaN fails the compares)
+        return fail("mmg_set_message_noise: sigma_sen = %g, sigma_rec = %g: a standard deviation is finite and not negative (both 0 clears the setting)",
+                    (double)sigma_sen, (double)sigma_rec);
+    const bool on = sigma_sen > 0.f || sigma_rec > 0.f;
+    if (on) {
+        if (h->dm.use_binary)
+            return fail("mmg_set_message_noise: continuous messages only (use_binary = 1: mmg_set_message_flipout is the noisy channel of binary messages)");
+        if (refuse_attn(h, "mmg_set_message_noise")) return -1;
+        if (h->sender_var) return fail("mmg_set_message_noise: the handle has a sender variant (mmg_set_sender_variant); noise and a variant do not combine");
+    }
+    const float o_sen = h->noise_sigma_sen, o_rec = h->noise_sigma_rec; const bool o_dev = h->noise_dev;
+    const uint64_t o_seed = h->noise_eval_seed; const uint32_t o_evals = h->noise_evals;
+    h->noise_sigma_sen = sigma_sen; h->noise_sigma_rec = sigma_rec; h->noise_dev = on && noise_dev != 0;
+    h->noise_eval_seed = eval_seed; h->noise_evals = 0u;
+    if (on == h->sel.noise) return 0;                    // same routing: nothing to select
+    const JobTable old = h->jt;
+    if (select_paths(h)) {
+        const std::string why = g_err;
+        h->noise_sigma_sen = o_sen; h->noise_sigma_rec = o_rec; h->noise_dev = o_dev; h->noise_eval_seed = o_seed; h->noise_evals = o_evals;
+        select_paths(h);
+        return fail("mmg_set_message_noise: %s", why.c_str());
     }
     if (memcmp(&old, &h->jt, sizeof(JobTable)) != 0) {
         HIP_OK(hipDeviceSynchronize());                  // (rare: nothing may read the old table while the new one lands)
@@ -1237,9 +1288,10 @@ extern "C" int mmg_sender_forward(mmg_handle* h, const float* d_x, const float* 
     ar.x = d_x; ar.u_z = d_u_z ? d_u_z - (size_t)t * d.B * d.W : nullptr; ar.seed = seed; ar.train = train; ar.run_all = 1;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 1; ar.w_in = d_w;
     flip_args(h, ar, seed, train, false);
+    noise_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
     relax_args(h, ar);
-    if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
+    if (ar.flip_on & 4 && t == 0) ar.flip_c1 = h->sel.noise ? h->noise_evals++ : h->flip_evals++;      // (an evaluation conversation begins at the sender's step 0)
     if (h->sel.vattn) hipLaunchKernelGGL(h->sel.plan.agent_vattn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->va);
     else hipLaunchKernelGGL(h->sel.plan.agent_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar);
     if (launch_check("k_conversation(sender)")) return -1;
@@ -1271,6 +1323,7 @@ extern "C" int mmg_receiver_forward(mmg_handle* h, const float* d_z, const float
     ar.u_s = d_u_s ? d_u_s - offB : nullptr; ar.u_w = d_u_w ? d_u_w - offW : nullptr;
     ar.t_begin = t; ar.t_end = t + 1; ar.phases = 2; ar.h_state = d_h_z; ar.sprod_state = d_s_prob_prod; ar.sprod_first = first;
     flip_args(h, ar, seed, train, false);
+    noise_args(h, ar, seed, train, false);
     ar.sender_var = h->sel.variant;
     relax_args(h, ar);
     if (h->sel.attn) hipLaunchKernelGGL(h->sel.plan.agent_attn_fn, dim3(d.B), dim3(MMG_BLOCK), h->sel.conv_smem_agent, st, h->dm, h->P, h->tp, ar, h->at);

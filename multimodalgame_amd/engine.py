@@ -249,6 +249,27 @@ class Engine(object):
         _lib.check(self.lib.mmg_set_message_relaxation(self.handle, tau_sen, tau_rec, int(bool(hard))))
         self.relaxation = (tau_sen, tau_rec, bool(hard))
 
+    noise = None                   # (sigma_sen, sigma_rec, dev) while set_message_noise holds
+
+    def set_message_noise(self, sigma_sen=None, sigma_rec=None, dev=False, eval_seed=0):
+        """Additive Gaussian noise on CONTINUOUS messages, an AWGN channel (include/mmg.h: mmg_set_message_noise): the sender's
+        message of step t becomes logits + sigma_sen * n, the receiver's logits + sigma_rec * n, n standard normal from the
+        library's Philox streams 7 / 8 (evaluation: 9 / 10).  None or 0 = that message stays clean; both clears the setting.
+        dev: evaluation conversations are noisy too (their draws are keyed by eval_seed and a count of the evaluation
+        conversations since this call).  The noisy value is the message everything downstream reads, and the gradient crosses it
+        unchanged, so forward, train_step(s), dp_train_step(s), eval_steps, sender_forward / receiver_forward and every VJP work
+        on such an engine.  Continuous messages only; not together with attention or a sender variant.  Host only; the library
+        re-selects its kernels only when the noisy state changes, so a training loop may call this before every minibatch to
+        anneal the sigmas."""
+        sig = [0.0 if v is None else float(v) for v in (sigma_sen, sigma_rec)]
+        for name, v in zip(("sigma_sen", "sigma_rec"), sig):
+            if not 0.0 <= v < float("inf"):                                # (NaN fails both compares)
+                raise ValueError("%s = %r: a standard deviation is finite and not negative" % (name, v))
+        on = sig[0] > 0.0 or sig[1] > 0.0
+        _lib.check(self.lib.mmg_set_message_noise(self.handle, sig[0], sig[1], int(bool(dev) and on),
+                                                  C.c_uint64(int(eval_seed) & 0xFFFFFFFFFFFFFFFF)))
+        self.noise = (sig[0], sig[1], bool(dev)) if on else None
+
     # ------------------------------------------------------------------ training controls
     def set_trainable(self, agents):
         """The agents the REINFORCE step updates from the next minibatch on (include/mmg.h: mmg_set_trainable): a collection of agent

@@ -290,6 +290,13 @@ class Game(object):
     Evaluation conversations stay discrete.  Message flips, sender variants, attention, train_step(s) and the agent modules' own
     autograd nodes are not available with it and raise; bs / br of a relaxed exchange are plain tensors (the baselines are
     REINFORCE machinery: mmg_exchange_vjp refuses a relaxed handle).
+    noise_sen / noise_rec (a standard deviation, None: off) and noise_dev: additive Gaussian noise on CONTINUOUS messages, the
+    continuous twin of the flips (Engine.set_message_noise) -- the sender's / the receiver's message is logits + sigma * n, in
+    training conversations always, in evaluation ones under noise_dev (keyed by the game's seed); the noisy value is what the other
+    agent, the message lists of exchange() and every gradient see.  autograd, channel_grad (exact here: the gradient crosses the
+    channel unchanged), input_grad and the agent modules' own nodes work with it; set_noise() anneals the sigmas between
+    minibatches.  Binary messages raise ValueError, attention and sender variants NotImplementedError.  The setting is NOT stored
+    in checkpoints (controls_state() / save()): a resumed run states it again.
     Description attention (model.py:267-271, 344-410) is read from the module: Receiver(..., desc_attn=True, desc_attn_dim=A).  The
     receiver then attends over the words of every description: exchange() takes exchange_args["desc_set"] / ["desc_set_lens"] as
     the reference does, Receiver.forward its desc_set / desc_set_lens arguments, and set_desc_set() states the pair for the entries
@@ -307,7 +314,7 @@ class Game(object):
 
     def __init__(self, sender, receiver, baseline_sen, baseline_rec, flags=None, device=None, seed=0, autograd=False,
                  channel_grad=False, input_grad=False, flipout_sen=None, flipout_rec=None, flipout_dev=False,
-                 sender_mix="sum", ignore_code=False, ignore_receiver=False, relax=None):
+                 sender_mix="sum", ignore_code=False, ignore_receiver=False, relax=None, noise_sen=None, noise_rec=None, noise_dev=False):
         fl = flags if flags is not None else _flags.FLAGS
         _flags.check_supported(fl)                    # -desc_attn, -sender_mix prod|mou, -flipout_*, -ignore_*, ... raise
         self.modules = dict(sender=sender, receiver=receiver, baseline_sen=baseline_sen, baseline_rec=baseline_rec)
@@ -364,6 +371,8 @@ class Game(object):
         self.relax = relax_setting(relax)
         if self.relax:
             self._check_relax(self.autograd, self.channel_grad)
+        self._noise_dev = bool(noise_dev)
+        self.noise = self._noise_setting(noise_sen, noise_rec, noise_dev)
         self.trainable = tuple(_lib.AGENTS)           # freeze() / unfreeze(): the agents train_step(s) updates
         self._agent_steps = None      # per-agent optimizer steps restored before any engine exists (load_controls)
         self.engines = {}
@@ -406,6 +415,41 @@ class Game(object):
                          ("visual attention (Sender(use_attn=True))", self.vattn)):
             if on:
                 raise NotImplementedError("relaxed messages with %s are not available" % name)
+
+    def _noise_setting(self, sigma_sen, sigma_rec, dev):
+        """(sigma_sen, sigma_rec, dev) of Gaussian message noise, or None; raises for what a noise game cannot be."""
+        sig = []
+        for name, v in (("noise_sen", sigma_sen), ("noise_rec", sigma_rec)):
+            v = 0.0 if v is None else float(v)
+            if not 0.0 <= v < float("inf"):                                # (NaN fails both compares)
+                raise ValueError("%s = %r: a standard deviation is finite and not negative" % (name, v))
+            sig.append(v)
+        if not (sig[0] > 0.0 or sig[1] > 0.0):
+            return None
+        if self.cfg["use_binary"]:
+            raise ValueError("message noise is for continuous messages (use_binary=False): flipout_sen / flipout_rec are the noisy "
+                             "channel of binary ones")
+        for name, on in (("a sender variant (sender_mix / ignore_code / ignore_receiver)", self.sender_variant),
+                         ("description attention (Receiver(desc_attn=True))", self.attn_dim),
+                         ("visual attention (Sender(use_attn=True))", self.vattn)):
+            if on:
+                raise NotImplementedError("message noise with %s is not available" % name)
+        return (sig[0], sig[1], bool(dev))
+
+    def set_noise(self, sigma_sen=None, sigma_rec=None):
+        """The standard deviations of the message noise from now on -- what a training loop calls between minibatches to anneal
+        them -- for every engine of the game (Engine.set_message_noise: host only, no kernel is re-selected while the game stays
+        noisy; the evaluation draws start over from count 0).  None, None (or zeros): back to the clean channel.  noise_dev stays
+        what the game was created with."""
+        self.noise = self._noise_setting(sigma_sen, sigma_rec, self._noise_dev)
+        for eng in self.engines.values():
+            self._apply_noise(eng)
+
+    def _apply_noise(self, eng):
+        if self.noise:
+            eng.set_message_noise(self.noise[0], self.noise[1], dev=self.noise[2], eval_seed=self.seed)
+        elif getattr(eng, "noise", None):
+            eng.set_message_noise(None, None)
 
     def _refuse_relaxed_step(self, who):
         if self.relax:
@@ -642,6 +686,7 @@ class Game(object):
                 eng.set_sender_variant(*self.sender_variant)
             if self.relax:
                 eng.set_message_relaxation(*self.relax)
+            self._apply_noise(eng)
             if set(self.trainable) != set(_lib.AGENTS):
                 eng.set_trainable(self.trainable)
             if self._agent_steps:

@@ -51,13 +51,15 @@ def parse(asm, count=()):
 def digests(asm):
     """{kernel symbol: SHA-256 of its assembly text up to .Lfunc_end}.  Block labels and loop comments carry the index of the
     function in the module (BB<n>_<block>), which moves whenever a host edit changes the order templates are first used in:
-    normalised away."""
+    normalised away, and with it the padding between a block label and its comment (the comment column is fixed, so the
+    padding shrinks when the index gains a digit)."""
     out = {}
     parts = re.split(r"^(_Z[\w$.]+):\s*(?:;.*)?$", asm, flags=re.M)
     for i in range(1, len(parts) - 1, 2):
         name, body = parts[i], parts[i + 1]
         if re.search(r"; NumVgprs: (\d+)", body):
             text = re.sub(r"BB\d+_", "BB_", body.split(".Lfunc_end")[0])
+            text = re.sub(r"^(\.LBB_\d+:)[ \t]+;", r"\1 ;", text, flags=re.M)
             out[name] = hashlib.sha256(text.encode()).hexdigest()
     return out
 
