@@ -661,7 +661,13 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_wgrad(const JobTable* __restrict_
     // and the job table are fetched once per workgroup instead of once per tile, and no tile waits for a slot; the other
     // workgroups (column sums, the special and the spare block) follow them.  bid: the block index of the un-strided launch.
     const int bid = (gt_stride > 0 && (int)blockIdx.x >= gt_stride) ? (int)blockIdx.x - gt_stride + hd.gemm_tiles : (int)blockIdx.x;
-    const uint32_t oepoch = OPT ? wo.counter[3] + 1u : 0u;          // (the norm role bumps the counters when every block has read them)
+    // The epoch of this launch's pairs is the launch epoch this minibatch ENDS with: the one its forward launch committed (k_prep / the
+    // closing role of k_conversation_fast3), or, behind k_game_fast, which commits none, the one the closing role below moves to.  Every
+    // fused step moves the launch epoch exactly once, so no two k_wgrad<OPT> launches of a handle tag their pairs alike.  (With
+    // counter[3] + 1 on both routes, a one-launch step right behind a step of the other route -- a handle whose message flips were
+    // cleared -- found that step's sums of squares and clip coefficients "fresh" and updated with them.)
+    const uint32_t oepoch = OPT ? wo.counter[3] + (uint32_t)wo.oa.bump_mb : 0u;     // (bump_mb: 1 behind k_game_fast, else 0)
+    // (the closing role bumps the counters when every block has read them)
     const uint32_t ostep = OPT ? wo.counter[1] + 1u : 0u;
     if (OPT && bid > hd.n_wblocks) {
         // ---- a norm role: ONE PER AGENT (round 6; one workgroup for all four polled 8 pairs per lane, ~0.9 us per poll round).  It
