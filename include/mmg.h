@@ -528,6 +528,15 @@ enum { MMG_CAP_N_CU = 0, MMG_CAP_SPLIT, MMG_CAP_PERSIST, MMG_CAP_RC_BWD, MMG_CAP
 int mmg_plan_text(const mmg_handle* h, char* out, int out_bytes);
 int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_caps, int flags, char* out, int out_bytes);
 
+/* The window arithmetic of k_game_fast's baseline roles (host only, additive; for tests).  The live rows of a minibatch are cut
+ * into windows of 16; window w is the (w / nslots)-th window of slot w % nslots.  The kernel takes both from a reciprocal of
+ * nslots (1..64) instead of dividing; these run the kernel's own inline functions over a range:
+ *   mmg_game_window_split:  kw[w] = w / nslots and slot[w] = w % nslots as the kernel forms them, w = 0 .. n - 1;
+ *   mmg_game_window_counts: count[nw] = windows of `slot` in a minibatch of nw windows, nw = 0 .. n - 1.
+ * n <= 64 * nslots + 1.  Both return 0, or negative (an argument out of range). */
+int mmg_game_window_split(int nslots, int n, int32_t* kw, int32_t* slot);
+int mmg_game_window_counts(int nslots, int slot, int n, int32_t* count);
+
 /* Agent-level entry points (one exchange step), mirroring the reference modules.  Forward only: their backward pass is
  * mmg_sender_vjp / mmg_receiver_vjp / mmg_baseline_vjp below, from the caller's copies of the call's inputs and outputs.
  *   sender:   x[B,F], w[B,W] (ignored when t==0), t -> message[B,W], probs[B,W] (NULL if continuous),

@@ -54,7 +54,8 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_attn_param_table", "mmg_attn_workspace_bytes", "mmg_attn_tape_table", "mmg_attn_create", "mmg_set_desc_set",
            "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
            "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation",
-           "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls", "mmg_set_message_noise"]
+           "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls", "mmg_set_message_noise",
+           "mmg_game_window_split", "mmg_game_window_counts"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
@@ -152,6 +153,8 @@ def load():
     lib.mmg_degraded.restype = i32; lib.mmg_degraded.argtypes = [vp]
     lib.mmg_plan_text.restype = i32; lib.mmg_plan_text.argtypes = [vp, C.c_char_p, i32]
     lib.mmg_plan_for.restype = i32; lib.mmg_plan_for.argtypes = [cfgp, C.POINTER(C.c_int32), i32, i32, C.c_char_p, i32]
+    lib.mmg_game_window_split.restype = i32; lib.mmg_game_window_split.argtypes = [i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mmg_game_window_counts.restype = i32; lib.mmg_game_window_counts.argtypes = [i32, i32, i32, C.POINTER(C.c_int32)]
     lib.mmg_log_snapshot_count.restype = i64; lib.mmg_log_snapshot_count.argtypes = [cfgp, i32, i32]
     lib.mmg_log_snapshot.restype = i32; lib.mmg_log_snapshot.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.mmg_sender_forward.restype = i32
@@ -237,6 +240,25 @@ def plan_for(cfg, caps, flags=0):
     arr = (C.c_int32 * len(caps))(*caps)
     check(load().mmg_plan_for(C.byref(cfg), arr, len(caps), flags, buf, len(buf)))
     return buf.value.decode()
+
+
+def game_window_split(nslots, n):
+    """(w / nslots, w % nslots) for w = 0 .. n - 1 as k_game_fast's baseline roles form them (game_windows.h).  Host only.
+    This entry and mmg_game_window_counts exist for tests/test_game_windows_cpu.py alone: they expose a detail of one kernel, no
+    caller should build on them, and they go when the kernel stops cutting its rows into slot windows."""
+    import numpy as np
+    kw, slot = np.empty(n, np.int32), np.empty(n, np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(load().mmg_game_window_split(nslots, n, kw.ctypes.data_as(i32p), slot.ctypes.data_as(i32p)))
+    return kw, slot
+
+
+def game_window_counts(nslots, slot, n):
+    """Windows of `slot` in a minibatch of nw windows, nw = 0 .. n - 1, as the kernel forms them.  Host only."""
+    import numpy as np
+    count = np.empty(n, np.int32)
+    check(load().mmg_game_window_counts(nslots, slot, n, count.ctypes.data_as(C.POINTER(C.c_int32))))
+    return count
 
 
 def plan_caps(text):

@@ -263,6 +263,9 @@ __device__ __forceinline__ void loss_coefficients(const Dims& dm, const double* 
 // Split form of loss_coefficients for kernels that want the statistics loads in flight with everything else:
 // coef_load() (call first) fetches this thread's share, coef_compute() turns it into cw / ce / cb in LDS.
 struct CoefRegs { double s5[5]; double nsum; };
+// (k, t) = (i / T, i % T) of a thread i < 4 T by three compares: `/` by the run-time T is a ~35-instruction sequence around
+// v_rcp_iflag_f32, and coef_lds_regs / coef_compute run between the statistics' arrival and the reverse recurrence
+__device__ __forceinline__ void coef_kt(int i, int T, int& k, int& t) { k = (i >= T) + (i >= 2 * T) + (i >= 3 * T); t = i - k * T; }
 
 // CC: the statistics were written by other workgroups of THIS launch (write-through stores): agent-scope loads, so that the
 // caller's role_wait needs no acquire fence (= no L2 invalidate on the recurrence's critical path)
@@ -273,7 +276,8 @@ __device__ __forceinline__ CoefRegs coef_load(const Dims& dm, const double* __re
     CoefRegs c;
     const int T = dm.T;
     const int i = min((int)threadIdx.x, 4 * T - 1);
-    const int k = i / T, t = i - k * T;
+    int k, t;
+    coef_kt(i, T, k, t);
     const int ks = (k < 3) ? k : 2;
 #pragma unroll
     for (int j = 0; j < 5; ++j) c.s5[j] = ld(&st[stat_stream(T, ks, t, j)]);
@@ -293,7 +297,8 @@ __device__ __forceinline__ CoefRegs coef_lds_regs(const Dims& dm, const float* s
     CoefRegs r;
     const int T = dm.T;
     const int i = min((int)threadIdx.x, 4 * T - 1);
-    const int k = i / T, t = i - k * T;
+    int k, t;
+    coef_kt(i, T, k, t);
     const int ks = (k < 3) ? k : 2;
     const float* e = sv + (ks * T + t) * 9;
     r.s5[0] = (double)e[0];
@@ -315,7 +320,8 @@ __device__ __forceinline__ CoefRegs coef_lds_regs(const Dims& dm, const float* s
 __device__ __forceinline__ void coef_compute(const Dims& dm, const CoefRegs& c, LossCoef lc) {
     const int T = dm.T, i = threadIdx.x;
     if (i < 4 * T) {
-        const int k = i / T, t = i - k * T;
+        int k, t;
+        coef_kt(i, T, k, t);
         const double n = c.s5[0];
         const float nf = (float)n, nsf = (float)c.nsum;
         if (k < 3) {

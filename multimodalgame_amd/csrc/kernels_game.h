@@ -31,6 +31,7 @@
 // kernel; MMG_NO_GAME=1 (read at mmg_create) keeps the two-launch path, and both are compared (tests/test_hip_safety.py).
 #pragma once
 #include "device_utils.h"
+#include "game_windows.h"
 #include "kernels_fast.h"
 #include "kernels_fast3.h"
 #include "layout.h"
@@ -95,7 +96,7 @@ __device__ __forceinline__ void frag_load_cc(float4 (&f)[MAXQ], const float* __r
 // Partial scores stay per 64-unit block: the statistics roles add the same npb terms in the same order.
 template <int UB>
 __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params& P, const Tape& tp, int role, int n_roles, uint32_t epoch) {
-    __shared__ int s_rid[64 * 16];                       // live-row ids of this role's windows, 16 per window (-1: none)
+    __shared__ int s_rid[64 * 16];                       // live rows of this role's windows, 16 per window: game_row_pack (-1: none)
     __shared__ int s_nwin;
     __shared__ float s_part[UB][4][16];
     const int B = dm.B, H = dm.H, W = dm.W, R = dm.R, K = dm.K, T = dm.T;
@@ -120,6 +121,9 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
         if (!which) frag_load(w_st[u], wrow + W, nv[u], R, q);
     }
     for (int k = threadIdx.x; k < 64 * 16; k += blockDim.x) s_rid[k] = -1;
+    // (no division by the run-time nslots behind the wait: its reciprocal is formed here, while the conversations run -- game_windows.h)
+    const GameWinDiv wd = game_win_div(nslots);
+    const unsigned long long below = (1ull << lane) - 1ull;
     __syncthreads();
     if (wave == 0) {
         MMG_GT(3584 + 4 * role);
@@ -129,13 +133,14 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
         for (int t = 0; t < T; ++t) {
             const bool act = (lane < B) && (t <= ts);
             const unsigned long long m = __ballot(act);
-            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            const int w = pos >> 4;
-            if (act && (w % nslots) == slot && (w / nslots) < 64) s_rid[(w / nslots) * 16 + (pos & 15)] = t * B + lane;
+            const int pos = base + __popcll(m & below);
+            int kw, sl;
+            game_win_split(wd, pos >> 4, kw, sl);         // window pos / 16 of the minibatch: the kw-th of slot sl
+            if (act && sl == slot && kw < GAME_WIN_PER_SLOT) s_rid[kw * 16 + (pos & 15)] = game_row_pack(t, B, lane);
             base += __popcll(m);
         }
         const int nw = (base + 15) >> 4;                  // windows of the minibatch; mine: slot, slot + nslots, ...
-        if (lane == 0) s_nwin = nw > slot ? (nw - slot + nslots - 1) / nslots : 0;
+        if (lane == 0) s_nwin = game_win_count(wd, nw, slot);
     }
     __syncthreads();
     if (threadIdx.x == 0) { MMG_GT(5120 + 8 * role + 0); }
@@ -149,7 +154,7 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
     unsigned long long ubA[UB][4], ubB[UB][4];
     auto request = [&](int kw, float4 (&xm_)[4], float4 (&xt_)[4], unsigned long long (&ub_)[UB][4]) {
         const int* rw = s_rid + kw * 16;
-        const int rid = rw[i];
+        const int rid = game_row_id(rw[i]);
         const bool xv = rid >= 0;
         const size_t rr = (size_t)(xv ? rid : 0);
         frag_load_cc(xm_, (which ? tp.zr : tp.z) + rr * W, xv, W, q);
@@ -158,16 +163,16 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
 #pragma unroll
             for (int u = 0; u < UB; ++u)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { const int o = rw[q * 4 + r]; ub_[u][r] = ld_ll(tp.basell, (size_t)((o >= 0 ? o : 0) % B) * K + min(n[u], K - 1)); }
+                for (int r = 0; r < 4; ++r) { const int o = rw[q * 4 + r]; ub_[u][r] = ld_ll(tp.basell, (size_t)(o >= 0 ? game_row_sample(o) : 0) * K + min(n[u], K - 1)); }
         }
     };
     auto window = [&](int kw, float4 (&xm_)[4], float4 (&xt_)[4], unsigned long long (&ub_)[UB][4],
                       float4 (&xmN)[4], float4 (&xtN)[4], unsigned long long (&ubN)[UB][4]) {
         const int* rid_w = s_rid + kw * 16;
         if (kw + 1 < nwin) request(kw + 1, xmN, xtN, ubN);
-        int orow[4];
+        int orow[4], osmp[4];                             // the row ids, and their samples (0: no row)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) orow[r] = rid_w[q * 4 + r];
+        for (int r = 0; r < 4; ++r) { const int o = rid_w[q * 4 + r]; orow[r] = game_row_id(o); osmp[r] = o >= 0 ? game_row_sample(o) : 0; }
         f32x4 acc[UB];
 #pragma unroll
         for (int u = 0; u < UB; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -184,7 +189,7 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
                     for (int u = 0; u < UB; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            ub_[u][r] = ld_ll(tp.basell, (size_t)((orow[r] >= 0 ? orow[r] : 0) % B) * K + min(n[u], K - 1));
+                            ub_[u][r] = ld_ll(tp.basell, (size_t)osmp[r] * K + min(n[u], K - 1));
                             fresh = fresh && ll_fresh(ub_[u][r], epoch);
                         }
                     if (!__any(!fresh)) break;
@@ -218,10 +223,11 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
         if (threadIdx.x == 0 && kw == 0) { MMG_GT(5120 + 8 * role + 3); }
         if (threadIdx.x < 16 * UB) {
             const int u = threadIdx.x >> 4, rw = threadIdx.x & 15;
-            if (rid_w[rw] >= 0) {
+            const int rid = game_row_id(rid_w[rw]);
+            if (rid >= 0) {
                 const float v = (s_part[u][0][rw] + s_part[u][1][rw]) + (s_part[u][2][rw] + s_part[u][3][rw]);
-                part[(size_t)rid_w[rw] * npb + byi0 + u] = v;
-                st_ll(tp.partll, ((size_t)(which ? 0 : 1) * T * B + (size_t)rid_w[rw]) * npb + byi0 + u, v, epoch);
+                part[(size_t)rid * npb + byi0 + u] = v;
+                st_ll(tp.partll, ((size_t)(which ? 0 : 1) * T * B + (size_t)rid) * npb + byi0 + u, v, epoch);
             }
         }
         __syncthreads();
@@ -306,7 +312,6 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
     const int tgt = (int)ar.target[b];
     int t_done = T, w_done = T;                           // steps executed / steps whose receiver message was formed
     {   // ============================================================ forward pass (kernels_fast3.h, MERGED, training, binary)
-        for (int i = tid; i < L::uz; i += NT) lds[i] = 0.f;     // the tape slots: rows this conversation never writes read as zeros
         if (inject) {
             for (int i = tid; i < T * W; i += NT) {
                 const int t = i / W, j = i - t * W;
@@ -373,19 +378,24 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         float dsc[(32 * V + NT - 1) / NT];               // the caller's description matrix -> LDS (below, with the park stores)
 #pragma unroll
         for (int k = 0; k < (32 * V + NT - 1) / NT; ++k) { const int i = tid + NT * k; dsc[k] = (i < Dr * V) ? ar.desc[min(i, Dr * V - 1)] : 0.f; }
-        const float bs = P.p[R_S_B][0];
+        const float bs = P.p[R_S_B][0], by2 = P.p[R_Y2_B][0];
         float dd[8];
-        if (tid < W) s_sig[tid] = fsigmoid(P.p[S_CODE_BIAS][tid]);
+        // (loaded by every thread, used below with the park stores: a load inside `if (tid < W)` is waited for at the join, and that
+        //  wait drained every weight load of wave 0 in front of its Philox draws)
+        const float cbias = P.p[S_CODE_BIAS][min(tid, W - 1)];
         const size_t i_hw = prepll_hw0(dm) + tid, i_hx = prepll_hx(dm) + (size_t)b * H + tid;
         const size_t i_cd = prepll_cd(dm) + (size_t)min(d5, Dr - 1) * R + r5 * 8, i_dd = prepll_dd(dm) + u3;
         unsigned long long u[18];
-        auto load_pairs = [&]() {
-            u[0] = ld_ll(tp.prepll, i_hw); u[1] = ld_ll(tp.prepll, i_hx);
+        auto load_pairs_cd = [&]() {
 #pragma unroll
             for (int k = 0; k < 8; ++k) u[2 + k] = ld_ll(tp.prepll, i_cd + k);
 #pragma unroll
             for (int k = 0; k < 8; ++k) u[10 + k] = ld_ll(tp.prepll, i_dd + (size_t)min(q3 * 8 + k, Dr - 1) * R);
         };
+        auto load_pairs = [&]() { u[0] = ld_ll(tp.prepll, i_hw); u[1] = ld_ll(tp.prepll, i_hx); load_pairs_cd(); };
+        // the tape slots: rows this conversation never writes read as zeros -- 16 bytes a store, behind the weight loads' issue
+        static_assert(L::uz % 4 == 0, "the tape slots are filled as float4");
+        for (int i = tid; i < L::uz / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!inject) {                                   // Philox draws of the whole conversation, while the weight loads are in flight
             for (int i = tid; i < T * W; i += NT) {
                 const int t = i / W, j = i - t * W;
@@ -399,41 +409,37 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         for (int i = 0; i < 12; ++i) s_park[i * NT + tid] = whh_tmp[i];
 #pragma unroll
         for (int k = 0; k < (32 * V + NT - 1) / NT; ++k) { const int i = tid + NT * k; if (i < 32 * V) s_desc[i] = dsc[k]; }
+        if (tid < W) s_sig[tid] = fsigmoid(cbias);
         if (tid == 0) { MMG_GT(2048 + 16 * b + 14); }
-        {
-            int spins = 0;
-            for (;;) {
-                load_pairs();
-                bool fresh = true;
-#pragma unroll
-                for (int k = 0; k < 18; ++k) fresh = fresh && ll_fresh(u[k], epoch);
+        // The prep roles' pairs, all 18 in ONE burst (loads return in order: hw0 and h_x first).  Step 0 needs only hw0 / h_x until
+        // its P5, so those two are awaited alone -- a counted wait, the other 16 stay in flight -- and the Cd / Dd pairs are checked
+        // where P5 first reads them (below, behind step 0's P1-P4): they land while those four phases run.
 #ifdef MMG_TIMING
-                if (tid == 0) tp.dbg2[2048 + 16 * b + 15] = (long long)(spins + 1);
+        // (timing builds: both stamps are STORED behind the Cd / Dd pairs' check -- that check's wait drains every store in flight)
+        long long gt_loop = 0; int gt_polls = 0;
 #endif
-                if (!__any(!fresh)) break;
-                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(tp.sync + MMG_SYNC_ERR, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        load_pairs();
+        {
+            bool fresh = ll_fresh(u[0], epoch) && ll_fresh(u[1], epoch);
+            int spins = 0;
+            if (__any(!fresh)) {                         // (not yet: the two alone; this arm waits for everything in flight)
+                for (;;) {
+                    if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(tp.sync + MMG_SYNC_ERR, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                    u[0] = ld_ll(tp.prepll, i_hw); u[1] = ld_ll(tp.prepll, i_hx);
+                    fresh = ll_fresh(u[0], epoch) && ll_fresh(u[1], epoch);
+                    if (!__any(!fresh)) break;
+                }
             }
+#ifdef MMG_TIMING
+            gt_polls = spins + 1;
+#endif
         }
         const float hw0 = ll_value(u[0]), hx = ll_value(u[1]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { ncd[k] = -ll_value(u[2 + k]); dd[k] = (q3 * 8 + k < Dr) ? ll_value(u[10 + k]) : 0.f; }
         float cy5;
-        {
-            float part = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) part = fmaf(w2[k], -ncd[k], part);
-            cy5 = dpp_group_sum<8>(part) + P.p[R_Y2_B][0];
-        }
-        // Cd of this minibatch for the reverse pass's output step (the column of Cd a unit needs is read back from here)
-        if (d5 < Dr) {
-            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8) = make_float4(-ncd[0], -ncd[1], -ncd[2], -ncd[3]);
-            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8 + 4) = make_float4(-ncd[4], -ncd[5], -ncd[6], -ncd[7]);
-        }
-        // what the reverse pass would otherwise have to LOAD behind its 120 KB of weight fragments (a load's first use drains every
-        // load and store in flight on this chip): y2 / s weights and the description matrix, parked in LDS while the weights stream in
-        if (d5 == 0) { *reinterpret_cast<float4*>(s_w2s + r5 * 8) = make_float4(w2[0], w2[1], w2[2], w2[3]); *reinterpret_cast<float4*>(s_w2s + r5 * 8 + 4) = make_float4(w2[4], w2[5], w2[6], w2[7]); }
-        if (tid < 16) *reinterpret_cast<float4*>(s_w2s + R + tid * 4) = ws4;
-        MMG_STAMP(1); if (tid == 0) { MMG_GT(2048 + 16 * b + 1); }
+#ifdef MMG_TIMING
+        gt_loop = (long long)wall_clock64();             // "pairs held / loop start"
+#endif
+        MMG_STAMP(1);
         if (tid < R) s_h[tid] = 0.f;
         if (tid < W) s_w[tid] = dm.first_rec;
         if (tid == 0) s_mask[0] = 1.f;
@@ -441,11 +447,13 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         float ghp_r = 0.f, ghp_u = 0.f, ghn = b_hn;
         __syncthreads();
         MMG_STAMP(2);
-        for (int t = 0; t < T; ++t) {
+        // P1-P4 of a step: written once, run for step 0 in front of the Cd / Dd pairs' check and for every later step at the END of
+        // the loop body below (the loop is rotated: no branch is added to its steady-state body)
+        auto p1_to_p4 = [&](const int t, const bool first) __attribute__((always_inline)) {
             MMG_STAMP(8 + 10 * t + 9);
             // ===== P1 sender: a = tanh(h_x + code_layer(c))
             {
-                const float hw = (t > 0) ? bc + dot4p<W / 4>(wc, s_w + t * W, 4) : hw0;
+                const float hw = first ? hw0 : bc + dot4p<W / 4>(wc, s_w + t * W, 4);
                 s_a[t * H + tid] = ftanh(hx + hw);
             }
             __syncthreads(); MMG_STAMP(8 + 10 * t + 0);
@@ -486,6 +494,41 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
                 if (half4 == 0) { if (row4 < R) { s_A[row4] = acc; s_Astep[t * R + row4] = acc; } else s_gh[row4 - R] = acc; }
             }
             __syncthreads(); MMG_STAMP(8 + 10 * t + 3);
+        };
+        p1_to_p4(0, true);
+        {   // the Cd / Dd pairs, in flight since the burst above: fresh?  (else: spin on the sixteen)
+            for (int spins = 0;;) {
+                bool fresh = true;
+#pragma unroll
+                for (int k = 2; k < 18; ++k) fresh = fresh && ll_fresh(u[k], epoch);
+                if (!__any(!fresh)) break;
+                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(tp.sync + MMG_SYNC_ERR, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                load_pairs_cd();
+            }
+        }
+#ifdef MMG_TIMING
+        if (tid == 0) { tp.dbg2[2048 + 16 * b + 1] = gt_loop; tp.dbg2[2048 + 16 * b + 15] = (long long)gt_polls; }
+#endif
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { ncd[k] = -ll_value(u[2 + k]); dd[k] = (q3 * 8 + k < Dr) ? ll_value(u[10 + k]) : 0.f; }
+        {
+            float part = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) part = fmaf(w2[k], -ncd[k], part);
+            cy5 = dpp_group_sum<8>(part) + by2;
+        }
+        // Cd of this minibatch for the reverse pass's output step (the column of Cd a unit needs is read back from here; the barrier
+        // behind P5 is between these stores and every reader)
+        if (d5 < Dr) {
+            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8) = make_float4(-ncd[0], -ncd[1], -ncd[2], -ncd[3]);
+            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8 + 4) = make_float4(-ncd[4], -ncd[5], -ncd[6], -ncd[7]);
+        }
+        // what the reverse pass would otherwise have to LOAD behind its 120 KB of weight fragments (a load's first use drains every
+        // load and store in flight on this chip): y2 / s weights and the description matrix, parked in LDS while the weights stream in
+        if (d5 == 0) { *reinterpret_cast<float4*>(s_w2s + r5 * 8) = make_float4(w2[0], w2[1], w2[2], w2[3]); *reinterpret_cast<float4*>(s_w2s + r5 * 8 + 4) = make_float4(w2[4], w2[5], w2[6], w2[7]); }
+        if (tid < 16) *reinterpret_cast<float4*>(s_w2s + R + tid * 4) = ws4;
+        for (int t = 0;;) {
+            const float* hn = s_h + (t + 1) * R;
             // ===== P5 class logits | stop head (lane 240 keeps it) | hidden-side product of the r gate for the next step
             {
                 const float4 a0 = *reinterpret_cast<const float4*>(s_A + r5 * 8), a1 = *reinterpret_cast<const float4*>(s_A + r5 * 8 + 4);
@@ -548,6 +591,8 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
                 if (k2 == 0) { s_w[(t + 1) * W + m2] = wv; s_pw[t * W + m2] = ps; }
             }
             __syncthreads(); MMG_STAMP(8 + 10 * t + 6);
+            if (++t == T) break;
+            p1_to_p4(t, false);
         }
         __syncthreads();
         MMG_STAMP(3); if (tid == 0) { MMG_GT(2048 + 16 * b + 2); }

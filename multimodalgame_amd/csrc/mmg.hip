@@ -436,6 +436,27 @@ extern "C" int mmg_plan_for(const mmg_config* cfg, const int32_t* caps, int n_ca
     return plan_text(h, out, out_bytes);
 }
 
+// The index arithmetic of k_game_fast's baseline roles (game_windows.h), as the kernel calls it, over a whole range at once.
+static int game_window_args(const char* who, int nslots, int n) {
+    if (nslots < 1 || nslots > GAME_WIN_MAX_SLOTS) return fail("%s: nslots must be 1..%d", who, GAME_WIN_MAX_SLOTS);
+    if (n < 0 || n > GAME_WIN_PER_SLOT * nslots + 1) return fail("%s: n must be 0..%d * nslots + 1", who, GAME_WIN_PER_SLOT);
+    return 0;
+}
+extern "C" int mmg_game_window_split(int nslots, int n, int32_t* kw, int32_t* slot) {
+    if (game_window_args("mmg_game_window_split", nslots, n)) return -1;
+    if (!kw || !slot) return fail("mmg_game_window_split: NULL output");
+    const GameWinDiv d = game_win_div(nslots);
+    for (int w = 0; w < n; ++w) { int k, s; game_win_split(d, w, k, s); kw[w] = k; slot[w] = s; }
+    return 0;
+}
+extern "C" int mmg_game_window_counts(int nslots, int slot, int n, int32_t* count) {
+    if (game_window_args("mmg_game_window_counts", nslots, n)) return -1;
+    if (slot < 0 || slot >= nslots || !count) return fail("mmg_game_window_counts: slot must be 0..nslots - 1, count not NULL");
+    const GameWinDiv d = game_win_div(nslots);
+    for (int nw = 0; nw < n; ++nw) count[nw] = game_win_count(d, nw, slot);
+    return 0;
+}
+
 extern "C" int mmg_set_profiling(mmg_handle* h, int enabled) {
     if (!h) return fail("NULL handle");
     h->profiling = enabled != 0; h->timers_used = 0;
