@@ -15,6 +15,8 @@
  *   mmg_train_steps        <- n iterations of the epoch loop's body, model.py:1218-1240 (batches of misc.py:257-302)
  *   mmg_eval_steps         <- n iterations of eval_dev's loop body: exchange(train = False) + the per-batch
  *                             accuracy / confusion / length / Hamming arithmetic   model.py:620-691
+ *   mmg_eval_steps_profile <- the same, plus per batch the counts behind the -binary_only dump's analysis (rank of the target,
+ *                             stop step and both messages per sample and step)    binary_vectors.py:24-46, 89-141
  *   mmg_dp_train_step[s]   <- the same block on one rank of a data-parallel job (statistics + gradient
  *                             all-reduce; couplings model.py:912-915, 947-961, 1310)
  *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (sender_mix=sum; the attention branch on a handle of mmg_vattn_create)
@@ -433,6 +435,36 @@ int     mmg_vattn_reset_state(mmg_handle* h);
 int64_t mmg_eval_acc_count(const mmg_config* cfg);
 int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
                    int64_t* d_acc, int32_t* d_len, int64_t* d_batch, void* stream);
+
+/* The communication profile of a dev evaluation: mmg_eval_steps with the same arguments and the same results in d_acc / d_len /
+ * d_batch, plus ONE more reduction launch per batch (k_eval_profile, behind k_eval_reduce on the same stream) that adds integer
+ * counts to d_prof.  It stands for the reference's -binary_only dump (binary_vectors.py:24-46: per sample and step the rank of the
+ * target, :92-99, the stop bit and mask, :129-132, and both agents' messages, :101-126) and for what is derived from that file:
+ * accuracy against conversation length, conversation length per class, per-class message codes.  The conversations are those of
+ * mmg_eval_steps (model.py:620-640: train = 0, every sample runs all steps), so a corruption mask, flipout_dev flips and noise_dev
+ * noise are counted as the receiver saw them.
+ * Per sample b, with n_b and tsel[b] as above and c = d_target[b]: the sample is LIVE at step t iff t <= tsel[b], and
+ *   rank_t[b] = #{d : y[min(t, tsel[b]), b, d] > y[min(t, tsel[b]), b, c]},  t = 0 .. T - 1
+ * -- the rank of the target had every conversation been cut after t + 1 steps (a sample that stopped earlier keeps its own
+ * answer); strict > on the fp32 logits, so rank_{T-1} is the rank mmg_eval_steps' hit is formed from.
+ *   d_prof: mmg_eval_profile_count() = 4 + 2 D T + 2 D + 2 T D W int64, ZEROED BY THE CALLER before the first batch of an evaluation
+ *   and added to atomically (integers only: bit-reproducible); handles of different batch sizes may share one.  In this order:
+ *     head [4]            [0] batches added | [1] samples with a valid target | [2] samples with a target outside [0, D) | [3] 0
+ *     steps [D, T]        samples of class c whose output step is l
+ *     rank [T, D]         samples with rank_t[b] = r
+ *     class_hits [D]      samples of class c with rank_{T-1}[b] < min(top_k, D)
+ *     class_ranksum [D]   sum over the samples of class c of rank_{T-1}[b]
+ *     msg_sen [T, D, W]   samples of class c, live at t, with lrintf(z[t, b, j]) == 1 (the sender's messages)
+ *     msg_rec [T, D, W]   the same over the receiver's messages w
+ *   A target outside [0, D) counts in head[2] only.  msg_sen / msg_rec are the per-class code book; their denominator, the samples
+ *   of class c that are live at t, is sum_{l >= t} steps[c, l].  Continuous messages (use_binary == 0): both message blocks are
+ *   left untouched.
+ * No host synchronisation, the minibatch counter is not touched, the tape of the last batch stays valid.  Returns 0, or negative
+ * for what mmg_eval_steps refuses and for d_prof == NULL (mmg_eval_steps is the entry without a profile).
+ * mmg_eval_profile_count: host only; negative for a config the library refuses. */
+int64_t mmg_eval_profile_count(const mmg_config* cfg);
+int mmg_eval_steps_profile(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                           int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream);
 
 /* Per-rank partial sums of every batch statistic the losses need (counts, sums and squared sums
  * of reward-minus-baseline per stream and step, ...) into the f64 tape array "stats".  With more

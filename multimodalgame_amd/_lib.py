@@ -55,7 +55,7 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
            "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation",
            "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls", "mmg_set_message_noise",
-           "mmg_game_window_split", "mmg_game_window_counts"]
+           "mmg_game_window_split", "mmg_game_window_counts", "mmg_eval_profile_count", "mmg_eval_steps_profile"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
@@ -72,6 +72,9 @@ MIX = {"sum": 0, "prod": 1}             # mmg_set_sender_variant's mix (include/
 
 # the accumulator of mmg_eval_steps (include/mmg.h): EVAL_ACC_HEAD scalars -- hits, batches, samples, 0 -- then conf [D, D], seen [D]
 EVAL_ACC_HEAD = 4
+# the accumulator of mmg_eval_steps_profile: EVAL_PROF_HEAD scalars -- batches, samples with a valid target, samples without, 0 --
+# then steps [D, T], rank [T, D], class_hits [D], class_ranksum [D], msg_sen [T, D, W], msg_rec [T, D, W]
+EVAL_PROF_HEAD = 4
 
 
 def load():
@@ -118,6 +121,8 @@ def load():
     lib.mmg_train_steps.restype = i32; lib.mmg_train_steps.argtypes = [vp, fp, vp, i64, fp, u64, vp]
     lib.mmg_eval_acc_count.restype = i64; lib.mmg_eval_acc_count.argtypes = [cfgp]
     lib.mmg_eval_steps.restype = i32; lib.mmg_eval_steps.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp]
+    lib.mmg_eval_profile_count.restype = i64; lib.mmg_eval_profile_count.argtypes = [cfgp]
+    lib.mmg_eval_steps_profile.restype = i32; lib.mmg_eval_steps_profile.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp, vp]
     lib.mmg_set_message_corruption.restype = i32; lib.mmg_set_message_corruption.argtypes = [vp, vp, i32]
     lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
     lib.mmg_set_sender_variant.restype = i32; lib.mmg_set_sender_variant.argtypes = [vp, i32, i32, i32]

@@ -132,4 +132,102 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_eval_reduce(Dims dm, Tape tp, con
     if (lane == 0 && hits) eval_add(acc, hits);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_eval_profile -- the communication profile of a dev evaluation: what the reference's -binary_only dump stores per sample and
+// step (the rank of the target, the stop bit, both messages; binary_vectors.py:24-46, 89-141) and what its notebook and the
+// paper's figures derive from that dump (accuracy against conversation length, conversation length per class, per-class message
+// codes), reduced on the device into INTEGER counts.  One launch behind k_eval_reduce of mmg_eval_steps_profile, on the same
+// stream; it reads only the plain tape arrays mask, z, w, y and the targets, so it serves every handle kind.
+//
+// Per sample b: tsel[b] and n as k_eval_reduce derives them; c = target[b]; the sample is LIVE at step t iff t <= tsel[b];
+//   rank_t[b] = #{d : y[min(t, tsel[b]), b, d] > y[min(t, tsel[b]), b, c]}   for t = 0 .. T - 1
+// (the rank of the target had every conversation been cut after t + 1 steps; a sample that stopped earlier keeps its own answer;
+// strict > on the fp32 logits, so rank_{T-1} is the rank k_eval_reduce's hit is formed from).
+//
+// Accumulator prof (int64, caller-owned and caller-zeroed, shared by every batch -- of any batch size -- of one evaluation;
+// eval_profile_count() entries, integer atomics only):
+//   head [4]                [0] batches added, [1] samples with a valid target, [2] samples with a target outside [0, D), [3] 0
+//   steps [D, T]            samples of class c whose output step is l
+//   rank [T, D]             samples with rank_t[b] = r
+//   class_hits [D]          samples of class c with rank_{T-1}[b] < min(top_k, D)
+//   class_ranksum [D]       sum over the samples of class c of rank_{T-1}[b]
+//   msg_sen [T, D, W]       samples of class c, live at t, with lrintf(z[t, b, j]) == 1
+//   msg_rec [T, D, W]       the same over w
+// A sample with a target outside [0, D) counts in head[2] only.  Continuous messages (use_binary == 0): msg_sen / msg_rec are
+// not touched.  The denominator of the code book -- the samples of class c live at t -- is sum_{l >= t} steps[c, l].
+//
+// grid = eval_sample_blocks(B) workgroups of 256 threads, a wave per sample: lanes over the steps for tsel, lanes over the classes
+// for each of the tsel + 1 distinct ranks (lane t keeps rank_t, so the T adds into rank[] are one atomic per lane), lanes over the
+// W bits of every live step for the code book.  No LDS beyond the step flags, no workgroup waits for another one.
+// ---------------------------------------------------------------------------------------------
+#define MMG_EVAL_PROF_HEAD 4
+__host__ __device__ inline int64_t eval_profile_count(int D, int T, int W) {
+    return MMG_EVAL_PROF_HEAD + 2 * (int64_t)D * T + 2 * (int64_t)D + 2 * (int64_t)T * D * W;
+}
+
+__global__ __launch_bounds__(MMG_BLOCK) void k_eval_profile(Dims dm, Tape tp, const int64_t* __restrict__ target, int top_k,
+                                                            int64_t* __restrict__ prof, int n_sample_blocks) {
+    __shared__ int s_alive[64];                        // [t]: some sample is alive after step t (T <= 64)
+    const int T = dm.T, B = dm.B, D = dm.D, W = dm.W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int blk = blockIdx.x;
+    if (blk >= n_sample_blocks) return;
+    // ---- n of the batch, as k_eval_reduce forms it
+    if (tid < 64) s_alive[tid] = 0;
+    __syncthreads();
+    if (!dm.fixed)
+        for (int i = tid; i < T * B; i += MMG_BLOCK)
+            if (tp.mask[(size_t)B + i]) s_alive[i / B] = 1;
+    __syncthreads();
+    int n = T;
+    if (!dm.fixed)
+        for (int t = T - 1; t >= 0; --t)
+            if (s_alive[t] == 0) n = t + 1;
+    if (blk == 0 && tid == 0) eval_add(prof, 1);
+    int64_t* p_steps = prof + MMG_EVAL_PROF_HEAD;
+    int64_t* p_rank = p_steps + (int64_t)D * T;
+    int64_t* p_hits = p_rank + (int64_t)T * D;
+    int64_t* p_rsum = p_hits + D;
+    int64_t* p_sen = p_rsum + D;
+    int64_t* p_rec = p_sen + (int64_t)T * D * W;
+    const int kk = top_k < D ? top_k : D;
+    int n_valid = 0, n_invalid = 0;
+    for (int b = blk * (MMG_BLOCK / 64) + wave; b < B; b += n_sample_blocks * (MMG_BLOCK / 64)) {
+        const int64_t tg = target[b];
+        if (!(tg >= 0 && tg < D)) { ++n_invalid; continue; }       // (wave-uniform)
+        ++n_valid;
+        // lanes over the steps (T <= 64): the output step
+        const int live = (lane >= 1 && lane < n && tp.mask[(size_t)lane * B + b] != 0) ? 1 : 0;
+        const int tsel = dm.fixed ? T - 1 : eval_wave_sum(live);
+        // lanes over the classes, once per live step: lane t keeps rank_t, the lanes behind the output step keep its rank
+        int mine = 0, above = 0;
+        for (int t = 0; t <= tsel; ++t) {
+            const float* yr = tp.y + ((size_t)t * B + b) * D;
+            const float yt = yr[tg];
+            above = 0;
+            for (int d = lane; d < D; d += 64) above += yr[d] > yt ? 1 : 0;
+            above = eval_wave_sum(above);
+            if (lane == t) mine = above;
+        }
+        if (lane > tsel) mine = above;                               // (above: rank_{tsel} = rank_{T-1}, on every lane)
+        if (lane < T) eval_add(p_rank + (int64_t)lane * D + mine, 1);
+        if (lane == 0) {
+            eval_add(p_steps + tg * T + tsel, 1);
+            if (above < kk) eval_add(p_hits + tg, 1);
+            if (above) eval_add(p_rsum + tg, above);
+        }
+        // lanes over the bits of every live step: the per-class code book
+        if (dm.use_binary)
+            for (int t = 0; t <= tsel; ++t) {
+                const size_t row = ((size_t)t * B + b) * W;
+                const int64_t slot = ((int64_t)t * D + tg) * W;
+                for (int j = lane; j < W; j += 64) {
+                    if (lrintf(tp.z[row + j]) == 1) eval_add(p_sen + slot + j, 1);
+                    if (lrintf(tp.w[row + j]) == 1) eval_add(p_rec + slot + j, 1);
+                }
+            }
+    }
+    if (lane == 0 && n_valid) eval_add(prof + 1, n_valid);
+    if (lane == 0 && n_invalid) eval_add(prof + 2, n_invalid);
+}
+
 }  // namespace mmg

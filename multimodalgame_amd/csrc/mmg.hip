@@ -725,14 +725,22 @@ extern "C" int mmg_exchange_forward(mmg_handle* h, const float* d_x, const int64
 // (train = 0, run-all: no Philox draw, the minibatch counter stays) and behind each one k_eval_reduce (kernels_eval.h), which
 // adds the batch's hits / confusion matrix / classes seen to the caller's accumulator and writes its conversation lengths,
 // step count and Hamming counts.  Not a minibatch start: no error gate, and nothing here waits inside a launch.
+// mmg_eval_steps_profile: the same call with one more reduction launch per batch, k_eval_profile, which adds the batch's
+// communication profile (per-step ranks, output steps per class, the per-class code book) to a second accumulator.
 // ---------------------------------------------------------------------------------------------
 extern "C" int64_t mmg_eval_acc_count(const mmg_config* cfg) {
     if (validate(cfg)) return -1;
     return eval_acc_count(cfg->n_classes);
 }
 
-extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
-                              int64_t* d_acc, int32_t* d_len, int64_t* d_batch, void* stream) {
+extern "C" int64_t mmg_eval_profile_count(const mmg_config* cfg) {
+    if (validate(cfg)) return -1;
+    return eval_profile_count(cfg->n_classes, cfg->max_exchange, cfg->w_dim);
+}
+
+// d_prof != NULL (mmg_eval_steps_profile): one k_eval_profile launch behind every k_eval_reduce; NULL: the launches of mmg_eval_steps alone
+static int eval_steps_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                           int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream) {
     if (!h) return fail("NULL handle");
     if (!d_x || !d_target || !d_desc || !d_acc || !d_len || !d_batch) return fail("mmg_eval_steps: x / target / desc / acc / len / batch must not be NULL");
     if (top_k < 1) return fail("mmg_eval_steps: top_k must be >= 1 (got %d)", top_k);
@@ -743,12 +751,29 @@ extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_
     for (int64_t i = 0; i < n; ++i) {
         const int64_t* tgt = d_target + (size_t)i * d.B;
         if (exchange_forward_impl(h, d_x + (size_t)i * x_stride(h), tgt, d_desc, nullptr, nullptr, nullptr, 0, 0, TAPE_ALL, stream, false, i)) return -1;
-        Scope sc(h, st, "k_eval_reduce");
-        hipLaunchKernelGGL(k_eval_reduce, dim3(nsb + 2 * d.T), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_acc,
-                           d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
-        if (launch_check("k_eval_reduce")) return -1;
+        {
+            Scope sc(h, st, "k_eval_reduce");
+            hipLaunchKernelGGL(k_eval_reduce, dim3(nsb + 2 * d.T), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_acc,
+                               d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
+            if (launch_check("k_eval_reduce")) return -1;
+        }
+        if (!d_prof) continue;
+        Scope sc(h, st, "k_eval_profile");
+        hipLaunchKernelGGL(k_eval_profile, dim3(nsb), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_prof, nsb);
+        if (launch_check("k_eval_profile")) return -1;
     }
     return 0;
+}
+
+extern "C" int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                              int64_t* d_acc, int32_t* d_len, int64_t* d_batch, void* stream) {
+    return eval_steps_impl(h, d_x, d_target, n, d_desc, top_k, d_acc, d_len, d_batch, nullptr, stream);
+}
+
+extern "C" int mmg_eval_steps_profile(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                                      int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream) {
+    if (!d_prof) return fail("mmg_eval_steps_profile: prof must not be NULL (mmg_eval_steps is the entry without a profile)");
+    return eval_steps_impl(h, d_x, d_target, n, d_desc, top_k, d_acc, d_len, d_batch, d_prof, stream);
 }
 
 // The evaluation mask of -bit_flip (include/mmg.h): host state only; exchange_forward_impl copies it into the launch arguments.

@@ -382,15 +382,29 @@ class Engine(object):
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         return torch.zeros(n, dtype=torch.int64, device=self.device)
 
-    def eval_steps(self, x, target, desc, n, top_k, acc, lens=None, batch=None, corrupt_mask=None):
+    def eval_profile(self):
+        """A zeroed communication profile for eval_steps(prof=...) (include/mmg.h: mmg_eval_profile_count int64 -- the head,
+        steps [D, T], rank [T, D], class_hits [D], class_ranksum [D], msg_sen / msg_rec [T, D, W]; commstats.parse_profile names
+        the blocks).  Engines of the same class count, step count and message width may share one."""
+        n = int(self.lib.mmg_eval_profile_count(C.byref(self.cfg)))
+        if n < 0:
+            raise _lib.MmgError(self.lib.mmg_last_error().decode())
+        return torch.zeros(n, dtype=torch.int64, device=self.device)
+
+    def eval_steps(self, x, target, desc, n, top_k, acc, lens=None, batch=None, corrupt_mask=None, prof=None):
         """n consecutive evaluation conversations (x [n * B, F], target [n * B]), each followed by the library's reduction launch
         (include/mmg.h: mmg_eval_steps): hits / confusion counts / classes seen are ADDED to `acc` (eval_acc()); returns
         (lens [n * B] int32: conversation lengths, batch [n, 1 + 2 T] int64: executed steps | Hamming counts of the sender's
         and of the receiver's messages per step -- float64 bits with continuous messages).  No host synchronisation; the
-        minibatch counter is untouched; the tape holds the last batch.  corrupt_mask: as forward()."""
+        minibatch counter is untouched; the tape holds the last batch.  corrupt_mask: as forward().
+        prof (eval_profile()): the call is mmg_eval_steps_profile -- the same results, and one more launch per batch ADDS the
+        batch's communication profile to `prof`."""
         B, T = self.cfg.batch, self.cfg.max_exchange
         assert x.size(0) >= n * B and target.size(0) >= n * B
         assert acc.dtype == torch.int64 and acc.numel() == _lib.EVAL_ACC_HEAD + self.cfg.n_classes * (self.cfg.n_classes + 1)
+        if prof is not None:
+            D, W = self.cfg.n_classes, self.cfg.w_dim
+            assert prof.dtype == torch.int64 and prof.is_contiguous() and prof.numel() == _lib.EVAL_PROF_HEAD + 2 * D * T + 2 * D + 2 * T * D * W
         if lens is None:
             lens = torch.empty(n * B, dtype=torch.int32, device=self.device)
         if batch is None:
@@ -401,9 +415,12 @@ class Engine(object):
         if corrupt_mask is not None:
             self.set_message_corruption(corrupt_mask)
         try:
-            _lib.check(self.lib.mmg_eval_steps(
-                self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n), self._ptr(desc, torch.float32),
-                int(top_k), self._ptr(acc, torch.int64), self._ptr(lens, torch.int32), self._ptr(batch, torch.int64), self._stream()))
+            args = (self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n), self._ptr(desc, torch.float32),
+                    int(top_k), self._ptr(acc, torch.int64), self._ptr(lens, torch.int32), self._ptr(batch, torch.int64))
+            if prof is None:
+                _lib.check(self.lib.mmg_eval_steps(*args, self._stream()))
+            else:
+                _lib.check(self.lib.mmg_eval_steps_profile(*args, self._ptr(prof, torch.int64), self._stream()))
         finally:
             if corrupt_mask is not None:
                 self.set_message_corruption(None)

@@ -5,6 +5,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import commstats
 from . import flags as _flags
 from . import misc
 from .engine import Engine, steps_from_counter
@@ -223,30 +224,45 @@ class FlatOptimizer(object):
 class EvalAccumulator(object):
     """What one dev evaluation adds up ON THE DEVICE (Game.eval_steps; include/mmg.h: mmg_eval_steps): the library's int64
     accumulator -- hits, the [D, D] confusion counts, the classes seen -- shared by the engines of every batch size, and per
-    call the conversation lengths and the per-batch step count / Hamming counts.  fetch() copies everything to the host ONCE."""
+    call the conversation lengths and the per-batch step count / Hamming counts.  fetch() copies everything to the host ONCE.
+    profile=True: the accumulator also owns ONE communication profile (include/mmg.h: mmg_eval_steps_profile) that the engines of
+    all batch sizes add to; fetch() returns it, parsed into its named blocks (commstats.parse_profile), under "profile"."""
 
-    def __init__(self, n_classes, top_k):
-        self.n_classes, self.top_k = int(n_classes), int(top_k)
+    def __init__(self, n_classes, top_k, profile=False):
+        self.n_classes, self.top_k, self.profile = int(n_classes), int(top_k), bool(profile)
         self.acc = None                                # created by the first engine that adds to it
+        self.prof, self.prof_dims = None, None         # profile=True: the flat profile and its (D, T, W), likewise
         self.parts = []                                # (B, n, T, binary, lens [n * B] i32, batch [n, 1 + 2 T] i64)
 
     def add(self, eng, data, target, desc, n, corrupt_mask=None):
         if self.acc is None:
             self.acc = eng.eval_acc()
-        lens, batch = eng.eval_steps(data, target, desc, n, self.top_k, self.acc, corrupt_mask=corrupt_mask)
+        if self.profile and self.prof is None:
+            self.prof, self.prof_dims = eng.eval_profile(), (eng.cfg.n_classes, eng.cfg.max_exchange, eng.cfg.w_dim)
+        lens, batch = eng.eval_steps(data, target, desc, n, self.top_k, self.acc, corrupt_mask=corrupt_mask,
+                                     **(dict(prof=self.prof) if self.profile else {}))
         self.parts.append((eng.cfg.batch, int(n), eng.cfg.max_exchange, bool(eng.cfg.use_binary), lens, batch))
 
     def fetch(self):
         """dict(hits, batches, samples, conf [D, D], seen [D], lens [samples] int64 in dataset order, n [batches],
         sizes [batches], ham_sen / ham_rec [batches] float64 = sum_{t < n} ham[t] / (B n): the reference's per-batch mean
-        Hamming distance, model.py:675-691) -- one device -> host copy."""
+        Hamming distance, model.py:675-691) -- one device -> host copy.  profile=True: and "profile", the parsed communication
+        profile (None when nothing was added), which rides in the same copy."""
         D = self.n_classes
         if self.acc is None:
             z = np.zeros(0)
-            return dict(hits=0, batches=0, samples=0, conf=np.zeros((D, D), np.int64), seen=np.zeros(D, np.int64),
-                        lens=np.zeros(0, np.int64), n=np.zeros(0, np.int64), sizes=np.zeros(0, np.int64), ham_sen=z, ham_rec=z)
+            out = dict(hits=0, batches=0, samples=0, conf=np.zeros((D, D), np.int64), seen=np.zeros(D, np.int64),
+                       lens=np.zeros(0, np.int64), n=np.zeros(0, np.int64), sizes=np.zeros(0, np.int64), ham_sen=z, ham_rec=z)
+            if self.profile:
+                out["profile"] = None
+            return out
         lens = torch.cat([p[4] for p in self.parts]).to(torch.int64)           # (one conversion for all batches, not one per batch)
-        flat = torch.cat([self.acc] + [p[5].reshape(-1) for p in self.parts] + [lens]).cpu().numpy()
+        flat = torch.cat([self.acc] + [p[5].reshape(-1) for p in self.parts] + [lens]
+                         + ([self.prof] if self.prof is not None else [])).cpu().numpy()
+        prof = None
+        if self.prof is not None:
+            prof = commstats.parse_profile(flat[flat.size - self.prof.numel():], *self.prof_dims)
+            flat = flat[:flat.size - self.prof.numel()]
         H = _lib.EVAL_ACC_HEAD
         out = dict(hits=int(flat[0]), batches=int(flat[1]), samples=int(flat[2]), conf=flat[H:H + D * D].reshape(D, D),
                    seen=flat[H + D * D:H + D * D + D])
@@ -262,6 +278,8 @@ class EvalAccumulator(object):
                 hr.append(float(ham[i, T:T + k].astype(np.float64).sum()) / (float(B) * k))
         out.update(lens=flat[o:], n=np.asarray(ns, np.int64), sizes=np.asarray(sizes, np.int64),
                    ham_sen=np.asarray(hs, np.float64), ham_rec=np.asarray(hr, np.float64))
+        if self.profile:
+            out["profile"] = prof
         return out
 
 
@@ -896,8 +914,8 @@ class Game(object):
                     **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         return eng
 
-    def eval_accumulator(self, n_classes, top_k):
-        return EvalAccumulator(n_classes, top_k)
+    def eval_accumulator(self, n_classes, top_k, profile=False):
+        return EvalAccumulator(n_classes, top_k, profile=profile)
 
     def eval_steps(self, data, target, desc, n, acc, corrupt_mask=None, data_context=None):
         """n consecutive dev batches (data [n * B, F], target [n * B], as train_steps lays them out) evaluated by ONE library

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import commstats
 from . import flags as _flags
 from .agents import Baseline, Receiver, Sender
 from .flags import FLAGS
@@ -75,6 +76,15 @@ def _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k):
             hl.append((per_step * live).sum(1) / n.to(torch.float32))       # [NB]: mean over the executed steps (model.py:679, 684)
 
 
+def _eval_profile_reduce(groups, prof, top_k):
+    """The torch form's communication profile: commstats.tape_profile of every dev batch stacked in `groups`, added to the flat
+    int64 array `prof` (the counts k_eval_profile adds in the library form, csrc/kernels_eval.h)."""
+    for g in groups.values():
+        for mask, z, w, y, tgt in zip(g["mask"], g["z"], g["w"], g["y"], g["target"]):
+            prof += commstats.tape_profile(mask.cpu().numpy(), z.cpu().numpy(), w.cpu().numpy(), y.cpu().numpy(), tgt.cpu().numpy(),
+                                           top_k, bool(FLAGS.fixed_exchange), bool(FLAGS.use_binary))
+
+
 def corrupt_mask_from_flags():
     """The [W, 1] mask of -bit_flip -corrupt_region (misc.build_mask; model.py:813-820), or None without -bit_flip.  A region
     outside the W-bit message raises ValueError here, where the reference fails at its first dev evaluation."""
@@ -86,7 +96,7 @@ def corrupt_mask_from_flags():
         raise ValueError(str(e))
 
 
-def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels, conf_mat_path, device, dump=None):
+def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels, conf_mat_path, device, dump=None, profile=None):
     """model.py:580-722 ON THE DEVICE: deterministic conversations on the dev set, top-k accuracy (nominal batch size in the
     denominator, line 667), confusion matrix, conversation length and Hamming statistics.
 
@@ -108,7 +118,13 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
 
     dump: optional dict that receives the last batch's engine (the dev sample dump of model.py:1463-1518 reads its tape).
     Under -bit_flip every batch's conversation runs with the sender's messages corrupted (model.py:637-638, 813-820): the
-    accuracy and the sender's Hamming statistic are those of the corrupted messages."""
+    accuracy and the sender's Hamming statistic are those of the corrupted messages.
+    profile: optional dict that receives the evaluation's communication profile, parsed into its named blocks (commstats.py:
+    per-step rank histograms, output steps per class, per-class hits and rank sums, the per-class code book of both agents'
+    messages; commstats.summarise() turns it into accuracy against conversation length, per-class statistics and the information
+    every message bit carries).  The library form adds it on the device with one more launch per batch (include/mmg.h:
+    mmg_eval_steps_profile), the torch form reduces the tape slices it copies anyway; the return value, the confusion matrix file
+    and the log lines are the same with and without it."""
     W = FLAGS.rec_w_dim
     corrupt_mask = corrupt_mask_from_flags()
     n_cls = desc.size(0)
@@ -121,6 +137,7 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     groups = {}                                        # batch size -> dict of lists
     acc = dict(correct=None, conf_flat=None, seen=None)
     conv_lens, ham_sen, ham_rec = [], [], []
+    prof = np.zeros(commstats.profile_count(n_cls, T, W), np.int64) if profile is not None else None
     pending = 0
     for batch in load_hdf5(dev_file, batch_size, epoch, shuffle, truncate_final_batch=True, map_labels=map_labels,
                            feats=(FLAGS.img_feat,), device=device):
@@ -128,7 +145,7 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         _bs = target.size(0)
         total += float(batch_size)                                           # model.py:667: the NOMINAL batch size
         if eng is None and hasattr(game.engine_for(_bs, n_cls), "eval_steps") and not os.environ.get("MMG_EVAL_TORCH"):
-            dacc = game.eval_accumulator(n_cls, top_k)
+            dacc = game.eval_accumulator(n_cls, top_k, **({} if profile is None else dict(profile=True)))
         if dacc is not None:
             eng = game.eval_steps(data, target, desc, 1, dacc, corrupt_mask=corrupt_mask)
             continue
@@ -140,6 +157,8 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         g["y"].append(tp["y"].view(T, _bs, -1).clone()); g["target"].append(target.view(-1))
         pending += 1
         if pending >= EVAL_FLUSH_BATCHES:              # bound the stacked tape copies (a 1000-class dev set of 50k samples would hold GBs)
+            if profile is not None:
+                _eval_profile_reduce(groups, prof, top_k)
             _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
             groups, pending = {}, 0
     # ---- ONE copy to the host
@@ -147,7 +166,11 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         r = dacc.fetch()
         correct_h, conf_full, occ = r["hits"], r["conf"], np.nonzero(r["seen"] > 0)[0]
         cl, hs, hr = r["lens"].astype(np.float64), r["ham_sen"], r["ham_rec"]
+        if profile is not None and r["profile"] is not None:
+            prof = np.concatenate([v.reshape(-1) for v in [r["profile"]["head"]] + [r["profile"][k] for k in commstats.BLOCKS]])
     else:
+        if profile is not None:
+            _eval_profile_reduce(groups, prof, top_k)
         _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
         correct, conf_flat, seen = acc["correct"], acc["conf_flat"], acc["seen"]
         correct_h = int(correct.item()) if correct is not None else 0
@@ -162,6 +185,9 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
                  hamming_sen_mean=hs.mean(), hamming_rec_mean=hr.mean())
     if dump is not None:
         dump["engine"] = eng
+    if profile is not None:
+        profile.clear()
+        profile.update(commstats.parse_profile(prof, n_cls, T, W))
     return correct_h / total, extra
 
 
