@@ -317,8 +317,12 @@ __device__ __forceinline__ CoefRegs coef_lds_regs(const Dims& dm, const float* s
 // (on the recurrence's critical path in the register-resident backward: f64 only where it matters -- the variance's cancellation;
 //  the counts are small integers and the results are fp32 coefficients, so their reciprocals, the square root and the quotient run
 //  in fp32: four f64 divisions and an f64 sqrt -- software sequences of ~20 dependent f64 instructions each -- were 0.6 us here)
-__device__ __forceinline__ void coef_compute(const Dims& dm, const CoefRegs& c, LossCoef lc) {
-    const int T = dm.T, i = threadIdx.x;
+//
+// The body once, over the three kernel-argument reads besides T (entropy weight and switch of stream k, the fixed-length switch):
+// lam_of / has_of / fixed_of are called where the values are used, so a caller that passes reads of `dm` compiles as it did.
+template <class Lam, class Has, class Fixed>
+__device__ __forceinline__ void coef_compute_with(int T, Lam lam_of, Has has_of, Fixed fixed_of, const CoefRegs& c, LossCoef lc) {
+    const int i = threadIdx.x;
     if (i < 4 * T) {
         int k, t;
         coef_kt(i, T, k, t);
@@ -326,11 +330,11 @@ __device__ __forceinline__ void coef_compute(const Dims& dm, const CoefRegs& c, 
         const float nf = (float)n, nsf = (float)c.nsum;
         if (k < 3) {
             const int len = (k == 1) ? T - 1 : T;
-            const float lam = (k == 0) ? dm.es : (k == 1) ? dm.erec : dm.esen;
-            const bool has = (k == 0) ? dm.has_es : (k == 1) ? dm.has_erec : dm.has_esen;
+            const float lam = lam_of(k);
+            const bool has = has_of(k);
             float cw = 0.f, ce = 0.f;
             if (n > 0 && c.nsum > 0) {
-                const float c_over_n = dm.fixed ? 1.f / ((float)len * nf) : 1.f / nsf;
+                const float c_over_n = fixed_of() ? 1.f / ((float)len * nf) : 1.f / nsf;
                 float denom = 1.f;
                 if (n > 1) {                                            // model.py:914-915
                     double rn = (double)(1.f / nf);
@@ -347,11 +351,30 @@ __device__ __forceinline__ void coef_compute(const Dims& dm, const CoefRegs& c, 
             lc.cw[k * T + t] = cw; lc.ce[k * T + t] = ce;
         } else {
             float cb = 0.f;
-            if (n > 0 && c.nsum > 0) cb = 2.f * (dm.fixed ? 1.f / ((float)T * nf) : 1.f / nsf);
+            if (n > 0 && c.nsum > 0) cb = 2.f * (fixed_of() ? 1.f / ((float)T * nf) : 1.f / nsf);
             lc.cb[t] = cb;
         }
     }
     __syncthreads();
+}
+__device__ __forceinline__ void coef_compute(const Dims& dm, const CoefRegs& c, LossCoef lc) {
+    coef_compute_with(dm.T, [&](int k) { return (k == 0) ? dm.es : (k == 1) ? dm.erec : dm.esen; },
+                      [&](int k) -> bool { return (k == 0) ? dm.has_es : (k == 1) ? dm.has_erec : dm.has_esen; }, [&]() { return dm.fixed; }, c, lc);
+}
+// CoefConst: the same three values of THIS thread (stream k of coef_kt) in two registers, for a kernel that fetches them IN FRONT
+// of its wait for the statistics and pins them there: selected by the thread's stream they are vector loads from the argument
+// segment, and read inside coef_compute they stand behind the wait (k_game_fast's common tail).  sw: bit 0 = has, bit 1 = fixed.
+struct CoefConst { float lam; int sw; };
+__device__ __forceinline__ CoefConst coef_const(const Dims& dm) {
+    int k, t;
+    coef_kt(min((int)threadIdx.x, 4 * dm.T - 1), dm.T, k, t);
+    CoefConst cc;
+    cc.lam = (k == 0) ? dm.es : (k == 1) ? dm.erec : dm.esen;
+    cc.sw = (((k == 0) ? dm.has_es : (k == 1) ? dm.has_erec : dm.has_esen) ? 1 : 0) | (dm.fixed ? 2 : 0);
+    return cc;
+}
+__device__ __forceinline__ void coef_compute(int T, const CoefConst& cc, const CoefRegs& c, LossCoef lc) {
+    coef_compute_with(T, [&](int) { return cc.lam; }, [&](int) -> bool { return (cc.sw & 1) != 0; }, [&]() { return (cc.sw & 2) != 0; }, c, lc);
 }
 
 // d loss / d logit of one Bernoulli unit: REINFORCE term + entropy term (Appendix A.4)

@@ -79,6 +79,17 @@ struct GameLds {
 };
 __host__ __device__ inline int game_lds_bytes() { return GameLds::total * 4; }
 
+// A kernel-argument pointer held in SGPRs from this point on: behind the empty `asm` the compiler cannot load it again where it is
+// used (a scalar-cache trip of its own there).  The pointer goes through the asm as a GLOBAL one -- a generic pointer out of an asm
+// is stored through with flat_store, which also counts on the LDS counter.
+template <class T>
+__device__ __forceinline__ T* pin_arg(T* p) {
+    typedef __attribute__((address_space(1))) T G;
+    G* g = (G*)p;
+    asm volatile("" : "+s"(g));
+    return (T*)g;
+}
+
 // 16 bytes of a row another role of this launch wrote through (agent-scope loads, device_utils.h)
 template <int MAXQ>
 __device__ __forceinline__ void frag_load_cc(float4 (&f)[MAXQ], const float* __restrict__ row, bool valid, int K, int q) {
@@ -99,7 +110,7 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
     __shared__ int s_rid[64 * 16];                       // live rows of this role's windows, 16 per window: game_row_pack (-1: none)
     __shared__ int s_nwin;
     __shared__ float s_part[UB][4][16];
-    const int B = dm.B, H = dm.H, W = dm.W, R = dm.R, K = dm.K, T = dm.T;
+    int B = dm.B, H = dm.H, W = dm.W, R = dm.R, K = dm.K, T = dm.T;      // (pinned below, in front of the wait)
     const int npb = (K + 63) / 64, cpw = npb / UB;       // unit-block groups per baseline
     const int combo = role % (2 * cpw), slot = role / (2 * cpw), nslots = n_roles / (2 * cpw);
     const int which = combo / cpw, byi0 = (combo - which * cpw) * UB;
@@ -122,7 +133,16 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
     }
     for (int k = threadIdx.x; k < 64 * 16; k += blockDim.x) s_rid[k] = -1;
     // (no division by the run-time nslots behind the wait: its reciprocal is formed here, while the conversations run -- game_windows.h)
-    const GameWinDiv wd = game_win_div(nslots);
+    GameWinDiv wd = game_win_div(nslots);
+    // ... and every kernel argument the role reads behind that wait is in SGPRs in front of it: the tape pointers selected by
+    // `which` were scalar loads from computed argument addresses, issued behind the barrier that follows the row list
+    float* const hid = pin_arg(which ? tp.hid_s : tp.hid_r);
+    float* const part = pin_arg(which ? tp.bs_part : tp.br_part);
+    const float* const xmsg = pin_arg(which ? tp.zr : tp.z);
+    const float* const xst = pin_arg(tp.h);
+    const float* const basell = pin_arg(tp.basell);
+    float* const partll = pin_arg(tp.partll);
+    asm volatile("" : "+s"(B), "+s"(H), "+s"(W), "+s"(R), "+s"(K), "+s"(T), "+s"(wd.mul));     // (wd.mul: the division's last steps were sunk behind the wait)
     const unsigned long long below = (1ull << lane) - 1ull;
     __syncthreads();
     if (wave == 0) {
@@ -145,8 +165,6 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
     __syncthreads();
     if (threadIdx.x == 0) { MMG_GT(5120 + 8 * role + 0); }
     const int nwin = s_nwin;
-    float* hid = which ? tp.hid_s : tp.hid_r;
-    float* part = which ? tp.bs_part : tp.br_part;
     // Two-stage pipeline over the role's windows: the rows (and the sender baseline's basehx pairs) of window kw + 1 are requested
     // BEFORE window kw's products, so a second window costs its MFMAs and stores, not another trip to memory (a trained pair
     // talks for ~7 steps: 440 live rows, 28 windows on 16 slots).
@@ -157,13 +175,13 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
         const int rid = game_row_id(rw[i]);
         const bool xv = rid >= 0;
         const size_t rr = (size_t)(xv ? rid : 0);
-        frag_load_cc(xm_, (which ? tp.zr : tp.z) + rr * W, xv, W, q);
-        if (!which) frag_load_cc(xt_, tp.h + (rr + B) * R, xv, R, q);
+        frag_load_cc(xm_, xmsg + rr * W, xv, W, q);
+        if (!which) frag_load_cc(xt_, xst + (rr + B) * R, xv, R, q);
         if (which) {
 #pragma unroll
             for (int u = 0; u < UB; ++u)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { const int o = rw[q * 4 + r]; ub_[u][r] = ld_ll(tp.basell, (size_t)(o >= 0 ? game_row_sample(o) : 0) * K + min(n[u], K - 1)); }
+                for (int r = 0; r < 4; ++r) { const int o = rw[q * 4 + r]; ub_[u][r] = ld_ll(basell, (size_t)(o >= 0 ? game_row_sample(o) : 0) * K + min(n[u], K - 1)); }
         }
     };
     auto window = [&](int kw, float4 (&xm_)[4], float4 (&xt_)[4], unsigned long long (&ub_)[UB][4],
@@ -189,7 +207,7 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
                     for (int u = 0; u < UB; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            ub_[u][r] = ld_ll(tp.basell, (size_t)osmp[r] * K + min(n[u], K - 1));
+                            ub_[u][r] = ld_ll(basell, (size_t)osmp[r] * K + min(n[u], K - 1));
                             fresh = fresh && ll_fresh(ub_[u][r], epoch);
                         }
                     if (!__any(!fresh)) break;
@@ -227,7 +245,7 @@ __device__ __forceinline__ void game_baseline_role(const Dims& dm, const Params&
             if (rid >= 0) {
                 const float v = (s_part[u][0][rw] + s_part[u][1][rw]) + (s_part[u][2][rw] + s_part[u][3][rw]);
                 part[(size_t)rid * npb + byi0 + u] = v;
-                st_ll(tp.partll, ((size_t)(which ? 0 : 1) * T * B + (size_t)rid) * npb + byi0 + u, v, epoch);
+                st_ll(partll, ((size_t)(which ? 0 : 1) * T * B + (size_t)rid) * npb + byi0 + u, v, epoch);
             }
         }
         __syncthreads();
@@ -518,11 +536,10 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
             cy5 = dpp_group_sum<8>(part) + by2;
         }
         // Cd of this minibatch for the reverse pass's output step (the column of Cd a unit needs is read back from here; the barrier
-        // behind P5 is between these stores and every reader)
-        if (d5 < Dr) {
-            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8) = make_float4(-ncd[0], -ncd[1], -ncd[2], -ncd[3]);
-            *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8 + 4) = make_float4(-ncd[4], -ncd[5], -ncd[6], -ncd[7]);
-        }
+        // behind P5 is between these stores and every reader).  All 32 rows: the rows d5 >= Dr hold the clamped pair loads' copy of row
+        // Dr - 1, so that the output step reads its column without a mask on the class (dy is zero there)
+        *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8) = make_float4(-ncd[0], -ncd[1], -ncd[2], -ncd[3]);
+        *reinterpret_cast<float4*>(s_cd + d5 * R + r5 * 8 + 4) = make_float4(-ncd[4], -ncd[5], -ncd[6], -ncd[7]);
         // what the reverse pass would otherwise have to LOAD behind its 120 KB of weight fragments (a load's first use drains every
         // load and store in flight on this chip): y2 / s weights and the description matrix, parked in LDS while the weights stream in
         if (d5 == 0) { *reinterpret_cast<float4*>(s_w2s + r5 * 8) = make_float4(w2[0], w2[1], w2[2], w2[3]); *reinterpret_cast<float4*>(s_w2s + r5 * 8 + 4) = make_float4(w2[4], w2[5], w2[6], w2[7]); }
@@ -605,6 +622,11 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
     const int wv = tid >> 6, fi = lane & 15, fq = lane >> 4;
     // ================================================================ epilogue 0: the rows the BASELINE roles multiply -- z_t, z_r
     // (= w_{t-1}), h_{t+1} of the live steps -- written through first thing; once they have completed: pair A, gamell[b] = t*
+    // (the repack blocks' "through" pairs ride along: requested here, checked behind the wait these stores need anyway -- the
+    //  fragment loads below then start without a trip of their own; and so do the loss coefficients' switches of the tail, vector
+    //  loads from the argument segment that otherwise stand behind the statistics wait)
+    const unsigned long long u_rep0 = ld_ll(tp.gamell, (size_t)B + (lane & 7));
+    CoefConst cc = coef_const(dm);
     {
         float4 vh[2];
 #pragma unroll
@@ -624,6 +646,8 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         if (tid == 0) __hip_atomic_store(&tp.tstar[b], tstar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the write-through stores above have completed
+    const bool rep_fresh = !__any(!ll_fresh(u_rep0, epoch));                  // (wave-uniform; nearly always: written ~20 us ago)
+    asm volatile("" : "+v"(cc.lam), "+v"(cc.sw));                             // (held from here: not loaded again at their use)
     __syncthreads();
     if (tid == 0) st_ll(tp.gamell, (size_t)b, (float)tstar, epoch);           // pair A: "the rows of sample b are through"
     MMG_STAMP(120); if (tid == 0) { MMG_GT(2048 + 16 * b + 3); }
@@ -707,10 +731,13 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
     constexpr int K4 = NT / R;
     const int k4 = tid / K4, p4 = tid % K4;
     float whhT[3 * R / K4], wwF[W / 4], whF[R / 4], wbF[4][W / 4], y1T[R / K4];
-    unsigned long long u_rep;
     // (a load's first use drains every load AND store in flight -- the waitcnt pass of the compiler treats mixed loads / stores as
     //  out of order on this chip -- so between here and the first sweep NOTHING reads a global value: y2 / s weights and the
     //  description matrix come from LDS, parked there by the forward prologue)
+    // (the output step's kernel arguments -- wave 0 read them one scalar-cache trip after the other between epilogue 2 and dA)
+    int Bg_ = dm.Bg; asm volatile("" : "+s"(Bg_));
+    float* const p_dy = pin_arg(tp.dy); float* const p_dysum = pin_arg(tp.dysum); float* const p_hstar = pin_arg(tp.hstar);
+    float* const p_dA = pin_arg(tp.dA); float* const p_Astar = pin_arg(tp.Astar);
     const float wsk = s_w2s[R + k4];
     const float w2_mine = s_w2s[min(tid, R - 1)];
     constexpr int NTILE_V = (V + 15) / 16;
@@ -720,10 +747,14 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         // workgroup that fetched tape.wrep before the repack was through would park the PREVIOUS minibatch's fragments in this
         // XCD's L2 for every later sample role of the XCD, whose own pair check then passes.  Nothing is in flight
         // here (the vmcnt(0) above), and the sweeps these fragments feed run in the shadow of the statistics chain.
-        u_rep = ld_ll(tp.gamell, (size_t)B + (lane & 7));
-        for (int spins = 0; __any(!ll_fresh(u_rep, epoch)); ) {
-            u_rep = ld_ll(tp.gamell, (size_t)B + (lane & 7));
-            if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(tp.sync + MMG_SYNC_ERR, 9u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        // The pairs were requested in front of epilogue 0 and checked behind its wait (rep_fresh): only a wave that did not find
+        // all eight fresh there polls here.
+        if (!rep_fresh) {
+            unsigned long long u_rep = ld_ll(tp.gamell, (size_t)B + (lane & 7));
+            for (int spins = 0; __any(!ll_fresh(u_rep, epoch)); ) {
+                u_rep = ld_ll(tp.gamell, (size_t)B + (lane & 7));
+                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(tp.sync + MMG_SYNC_ERR, 9u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+            }
         }
         const float4* wr = reinterpret_cast<const float4*>(tp.wrep) + tid;
         float4 q[MMG_REPACK_F4];
@@ -773,9 +804,17 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
                 const int nt = wv + 4 * uu;
                 if (nt >= NTILE_V) break;                                            // (wave-uniform)
                 const int n = nt * 16 + fi;
+                // the tile's eight B operands in flight together, in front of the MFMAs (a read under `d < Dr && n < V` was waited for
+                // alone in front of each one).  The rows d >= Dr of s_desc are zeros (forward prologue): only n is masked, by a select
+                const float* dcol = s_desc + fq * V + min(n, V - 1);
+                float bv[8];
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bv[ks] = dcol[4 * ks * V];
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bv[ks] = (n < V) ? bv[ks] : 0.f;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < 8; ++ks) { const int d = 4 * ks + fq; acc = mfma16(a[ks], (d < Dr && n < V) ? s_desc[min(d, Dr - 1) * V + min(n, V - 1)] : 0.f, acc); }
+                for (int ks = 0; ks < 8; ++ks) acc = mfma16(a[ks], bv[ks], acc);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { const int t = 4 * fq + r; if (t < w_done && n < V) tp.dbar[((size_t)t * B + b) * V + n] = acc[r]; }
             }
@@ -801,15 +840,27 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
     const float rs_ = s_sb[min(tid, TMAX - 1)], rps_ = s_ps[min(tid, TMAX - 1)];
     LossCoef lc; lc.cw = s_coef; lc.ce = s_coef + 3 * T; lc.cb = s_coef + 6 * T;
     // ---- output step t*: NLL seed dy, A* (kept by the forward pass), dA; dy / A* released to the class roles
-    const float dy_mine = (tid < Dr) ? (s_sm[min(tid, 31)] - (tid == tgt ? 1.f : 0.f)) / (float)dm.Bg : 0.f;
-    output_seed<R, true>(dy_mine, t_h + (tstar + 1) * R, s_dy, tp.dy, tp.dysum, tp.hstar, Dr, b, tid);
+    const float dy_mine = (tid < Dr) ? (s_sm[min(tid, 31)] - (tid == tgt ? 1.f : 0.f)) / (float)Bg_ : 0.f;
+    output_seed<R, true>(dy_mine, t_h + (tstar + 1) * R, s_dy, p_dy, p_dysum, p_hstar, Dr, b, tid);
     __syncthreads();
     if (tid < R) {
+        // The unit's Cd column and the dy row, every LDS read in flight together (one wave runs this: written as a conditional
+        // read per class it was ~60 dependent LDS trips).  No mask on d: s_dy[d] is +0 for d >= Dr (output_seed) and all 32 rows of
+        // s_cd are written (forward prologue), so a class beyond Dr adds +0 whatever its compare says.  Same sum order d = 0 .. D - 1.
         const float a = s_Astep[tstar * R + tid];
+        float cdv[D]; float4 dyv[8];
+#pragma unroll
+        for (int d = 0; d < D; ++d) cdv[d] = s_cd[d * R + tid];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dyv[j] = *reinterpret_cast<const float4*>(s_dy + 4 * j);
         float acc = 0.f;
 #pragma unroll
-        for (int d = 0; d < D; ++d) acc += (d < Dr && a + s_cd[d * R + tid] > 0.f) ? s_dy[d] : 0.f;
-        output_dA<R, true>(a, acc, w2_mine, s_dA, tp.dA, tp.Astar, b, tid);
+        for (int d = 0; d < D; ++d) {
+            const float4 v = dyv[d >> 2];
+            const float dyd = (d & 3) == 0 ? v.x : (d & 3) == 1 ? v.y : (d & 3) == 2 ? v.z : v.w;
+            acc += (a + cdv[d] > 0.f) ? dyd : 0.f;
+        }
+        output_dA<R, true>(a, acc, w2_mine, s_dA, p_dA, p_Astar, b, tid);
     }
     // ---- everything that does not depend on the carried dh, for ALL steps at once, on the two seed BASES (kernels_fast.h)
     MMG_GSTAMP(8); if (tid == 0) { MMG_GT(2048 + 16 * b + 5); }
@@ -838,6 +889,13 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         u_st0 = ld_ll(tp.statll, i_st0); u_st1 = ld_ll(tp.statll, i_st1);
         u_bs = ld_ll(tp.statll, statll_bs(dm) + so); u_br = ld_ll(tp.statll, statll_br(dm) + so);
     };
+    // Every kernel argument the tail behind the statistics reads -- the gradient-tape pointers; the loss coefficients' switches are
+    // held since epilogue 0 -- in registers NOW (copies by value, pinned: the compiler otherwise loads each one where it is used, a scalar-cache trip this
+    // workgroup has not made before, three to four of them in series between "pairs fresh" and the first reverse step)
+    float* const p_dls = pin_arg(tp.dls); float* const p_dbs = pin_arg(tp.dbs); float* const p_dbr = pin_arg(tp.dbr);
+    float* const p_dlw = pin_arg(tp.dlw); float* const p_dlz = pin_arg(tp.dlz); float* const p_dgpre = pin_arg(tp.dgpre);
+    float* const p_dpre = pin_arg(tp.dpre); float* const p_dhx = pin_arg(tp.dhx);
+    float* const p_dgi = pin_arg(tp.dgi); float* const p_dgh = pin_arg(tp.dgh);
     load_stat_pairs(); asm volatile("" ::: "memory");      // (the loads stay ahead of the sweep's LDS reads)
     sweep_wh<R, G::SR>(s_G1, s_G2, whF, s_dhin, s_H2, wv, fi, fq);
     MMG_GSTAMP(11); if (tid == 0) { MMG_GT(2048 + 16 * b + 7); }
@@ -855,16 +913,16 @@ __global__ __launch_bounds__(256, 1) void k_game_fast(Dims dm, Params P, Tape tp
         MMG_GSTAMP(12); if (tid == 0) { MMG_GT(2048 + 16 * b + 8); }
         const CoefRegs creg = coef_lds_regs(dm, s_statv);
         rbs_ = ll_value(u_bs); rbr_ = ll_value(u_br);
-        coef_compute(dm, creg, lc);
+        coef_compute(T, cc, creg, lc);
     }
     MMG_GSTAMP(2); if (tid == 0) { MMG_GT(2048 + 16 * b + 9); }
-    step_scalars<TMAX>(lc.cw, lc.ce, lc.cb, Lrew, rbs_, rbr_, rs_, rps_, true, false, s_cf, s_dls, tp.dls, tp.dbs, tp.dbr, B, T, b, tstar, tid);
+    step_scalars<TMAX>(lc.cw, lc.ce, lc.cb, Lrew, rbs_, rbr_, rs_, rps_, true, false, s_cf, s_dls, p_dls, p_dbs, p_dbr, B, T, b, tstar, tid);
     __syncthreads();
     MMG_GSTAMP(3); if (tid == 0) { MMG_GT(2048 + 16 * b + 10); }
     // ---- the gradient tapes of the live steps: bases x coefficients (stores only; the recurrence below does not wait for them)
-    store_grad_tapes<W, R, H, NT, TMAX>(s_cf, s1w, s2w, s1z, s2z, g1, g2, p1, p2, tp.dlw, tp.dlz, tp.dgpre, tp.dpre, tp.dhx, B, b, tstar, tid, wv, fi, fq);
+    store_grad_tapes<W, R, H, NT, TMAX>(s_cf, s1w, s2w, s1z, s2z, g1, g2, p1, p2, p_dlw, p_dlz, p_dgpre, p_dpre, p_dhx, B, b, tstar, tid, wv, fi, fq);
     // ---- the recurrence: two phases and ONE barrier per step
-    recurrence_one_barrier<R, K4, TMAX>(whhT, t_gru, t_h, s_cf, s_dhin, s_H2, s_dls, s_dAy, wsk, s_dghb, tp.dgi, tp.dgh, B, b, tstar, k4, p4,
+    recurrence_one_barrier<R, K4, TMAX>(whhT, t_gru, t_h, s_cf, s_dhin, s_H2, s_dls, s_dAy, wsk, s_dghb, p_dgi, p_dgh, B, b, tstar, k4, p4,
                                         [&](int slot) { MMG_GSTAMP(slot); });
     MMG_GSTAMP(4); if (tid == 0) { MMG_GT(2048 + 16 * b + 11); tp.dbg2[2048 + 16 * b + 12] = (long long)tstar; }
 }
