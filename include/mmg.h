@@ -17,6 +17,9 @@
  *                             accuracy / confusion / length / Hamming arithmetic   model.py:620-691
  *   mmg_eval_steps_profile <- the same, plus per batch the counts behind the -binary_only dump's analysis (rank of the target,
  *                             stop step and both messages per sample and step)    binary_vectors.py:24-46, 89-141
+ *   mmg_eval_steps_codes   <- the same, plus per sample the packed bits of both messages (the dump's "BinaryVec" records of
+ *                             both agents)                                           binary_vectors.py:101-126
+ *   mmg_code_pair_hist     <- the pairwise analysis of such a dump: Hamming against meaning distance over all pairs of samples
  *   mmg_dp_train_step[s]   <- the same block on one rank of a data-parallel job (statistics + gradient
  *                             all-reduce; couplings model.py:912-915, 947-961, 1310)
  *   mmg_sender_forward     <- Sender.forward                model.py:144-238 (sender_mix=sum; the attention branch on a handle of mmg_vattn_create)
@@ -465,6 +468,54 @@ int mmg_eval_steps(mmg_handle* h, const float* d_x, const int64_t* d_target, int
 int64_t mmg_eval_profile_count(const mmg_config* cfg);
 int mmg_eval_steps_profile(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
                            int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream);
+
+/* Every sample's own code of a dev evaluation: mmg_eval_steps (d_prof == NULL) or mmg_eval_steps_profile (d_prof != NULL) with the
+ * same arguments and the same results in d_acc / d_len / d_batch / d_prof, plus ONE more launch per batch (k_eval_codes, behind
+ * k_eval_reduce and k_eval_profile on the same stream) that WRITES -- nothing is accumulated -- the bits of both agents' messages,
+ * packed 32 to a word: what the reference's -binary_only dump stores per sample and step (binary_vectors.py:101-126: the
+ * "BinaryVec" field of the agent "S" and agent "R" records).  The per-class sums of the profile cannot answer questions about PAIRS of samples (mmg_code_pair_hist below); these
+ * can.  The kernel reads the plain tape (mask, z, w) and the targets only: it serves every handle kind, and a corruption mask or
+ * flipout_dev flips are packed as the receiver saw them.  Binary messages only.
+ * Per sample b of batch i, at row = row0 + i * B + b (so handles of several batch sizes -- the short final dev batch -- fill one
+ * caller-owned buffer in dataset order), with n_b and tsel[b] as above, Wp = (W + 31) / 32:
+ *   d_codes[row][agent][t][k] uint32, agent 0 = the sender's z, 1 = the receiver's w, t < T, k < Wp: bit (j & 31) of word (j >> 5)
+ *     is set iff lrintf(msg[t, b, j]) == 1 and t <= tsel[b].  The steps behind the output step and the padding bits of the last
+ *     word are zero; every word of the row is written, so the buffer need not be zeroed.  mmg_eval_code_words() = 2 T Wp per row.
+ *   d_meta[row][2] int32: tsel[b] | d_target[b], or -1 for a target outside [0, D).
+ * No host synchronisation, the minibatch counter is not touched, the tape of the last batch stays valid.  Returns 0, or negative
+ * for what mmg_eval_steps refuses, a handle with continuous messages (use_binary == 0: there are no bits), d_codes or d_meta NULL,
+ * row0 < 0 and row0 + n * B > cap_rows (the rows the two buffers hold).
+ * mmg_eval_code_words: host only; negative for a config the library refuses and for continuous messages. */
+int64_t mmg_eval_code_words(const mmg_config* cfg);
+int mmg_eval_steps_codes(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                         int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof /* may be NULL */,
+                         uint32_t* d_codes, int32_t* d_meta, int64_t row0, int64_t cap_rows, void* stream);
+
+/* The pair histogram of a set of codes: for every unordered pair i < j of the rows with a valid target, the Hamming distance of
+ * the two codes against the cosine distance of the two rows of a "meaning" matrix, split by whether the two rows share a class.
+ * From it the host forms topographic similarity (the rank correlation of the two distances over all pairs), class separation and
+ * the count of code collisions (multimodalgame_amd/commstats.py: topsim) -- the second-order analysis the -binary_only dump
+ * (binary_vectors.py:24-46) is collected for, O(n_rows^2), on the device.  Handle-free, on the calling thread's current device.
+ *   d_codes [n_rows][2][T][Wp], d_meta [n_rows][2]: as mmg_eval_steps_codes leaves them (padding bits zero).  agent: 0 the sender's
+ *   codes, 1 the receiver's; the steps t0 <= t < t1 are compared.  M = (t1 - t0) * W, K = n_bins.
+ *   d_meaning [n_rows, F] f32 with row stride ld >= F (floats): ANY matrix -- the image features give the image-level measure,
+ *   desc[target] the class-level one.  Its entries must be FINITE: that is the caller's duty (a NaN distance is counted in bin 0).
+ *   d_inv [n_rows] f32: work space; left holding inv[i] = 1 / sqrt(sum_k x_ik^2) in fp32, 0 for a zero row.
+ *   d_hist: mmg_code_pair_hist_count() = 4 + 2 (M + 1) K int64, ZEROED BY THE CALLER, integers only are added (bit-reproducible):
+ *     head [4]                  [0] rows used | [1] rows skipped (meta target -1) | [2] pairs counted = used (used - 1) / 2 | [3] 0
+ *     hist [2][M + 1][K]        hist[p][h][q] = pairs with p = (target_i == target_j),
+ *                               h = sum_{t0 <= t < t1} sum_k popc(code_i[agent][t][k] ^ code_j[agent][t][k]), and q the bin of
+ *                               c = dot(x_i, x_j) * (inv_i * inv_j),  u = (1.f - c) * (0.5f * K),  q = min(K - 1, max(0, (int)floorf(u)))
+ *                               in fp32: identical rows (c = 1 +- ulp) fall into bin 0, opposite rows (u = K) into bin K - 1, a zero
+ *                               row has c = 0.
+ *   Calls on disjoint row sets may add into one histogram (their heads add up too).
+ * Returns 0, or negative with a message for: a NULL pointer; n_rows outside 1..65536; F outside 1..4096; ld < F; n_bins outside
+ * 1..1024; agent not 0 or 1; T or W < 1; not 0 <= t0 < t1 <= T; 2 (M + 1) K > 2^24.  No host synchronisation.
+ * mmg_code_pair_hist_count: host only; M = n_sel_steps * w_dim; negative for the same shape refusals. */
+int64_t mmg_code_pair_hist_count(int n_sel_steps, int w_dim, int n_bins);
+int mmg_code_pair_hist(const uint32_t* d_codes, const int32_t* d_meta, int64_t n_rows, int T, int W,
+                       int agent, int t0, int t1, const float* d_meaning, int F, int64_t ld,
+                       float* d_inv /* [n_rows] work */, int n_bins, int64_t* d_hist, void* stream);
 
 /* Per-rank partial sums of every batch statistic the losses need (counts, sums and squared sums
  * of reward-minus-baseline per stream and step, ...) into the f64 tape array "stats".  With more

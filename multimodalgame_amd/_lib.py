@@ -55,7 +55,8 @@ SYMBOLS = ["mmg_last_error", "mmg_version", "mmg_param_count", "mmg_grad_floats"
            "mmg_vattn_param_count", "mmg_vattn_grad_floats", "mmg_vattn_param_table", "mmg_vattn_workspace_bytes",
            "mmg_vattn_tape_table", "mmg_vattn_create", "mmg_set_data_context", "mmg_vattn_reset_state", "mmg_set_message_relaxation",
            "mmg_set_trainable", "mmg_set_learning_rate", "mmg_set_entropy", "mmg_get_training_controls", "mmg_set_message_noise",
-           "mmg_game_window_split", "mmg_game_window_counts", "mmg_eval_profile_count", "mmg_eval_steps_profile"]
+           "mmg_game_window_split", "mmg_game_window_counts", "mmg_eval_profile_count", "mmg_eval_steps_profile",
+           "mmg_eval_code_words", "mmg_eval_steps_codes", "mmg_code_pair_hist_count", "mmg_code_pair_hist"]
 
 # description attention (include/mmg.h: mmg_attn_create): the supported range
 ATTN_MAX_DIM, ATTN_MAX_WORDS, ATTN_MAX_CLASSES, ATTN_MAX_BATCH = 128, 2048, 128, 512
@@ -75,6 +76,19 @@ EVAL_ACC_HEAD = 4
 # the accumulator of mmg_eval_steps_profile: EVAL_PROF_HEAD scalars -- batches, samples with a valid target, samples without, 0 --
 # then steps [D, T], rank [T, D], class_hits [D], class_ranksum [D], msg_sen [T, D, W], msg_rec [T, D, W]
 EVAL_PROF_HEAD = 4
+# the per-sample codes of mmg_eval_steps_codes: codes [rows, EVAL_CODE_AGENTS, T, code_wp(W)] uint32 (agent 0 the sender, 1 the
+# receiver; EVAL_CODE_BITS message bits to a word), meta [rows, EVAL_CODE_META] int32 (output step, target or -1)
+EVAL_CODE_AGENTS, EVAL_CODE_BITS, EVAL_CODE_META = 2, 32, 2
+EVAL_CODE_SENDER, EVAL_CODE_RECEIVER = 0, 1
+# the histogram of mmg_code_pair_hist: PAIR_HIST_HEAD scalars -- rows used, rows skipped, pairs counted, 0 -- then hist [2, M + 1, bins];
+# its limits: rows, columns of the meaning matrix, bins, 2 (M + 1) bins
+PAIR_HIST_HEAD = 4
+PAIR_MAX_ROWS, PAIR_MAX_F, PAIR_MAX_BINS, PAIR_MAX_SLOTS = 65536, 4096, 1024, 1 << 24
+
+
+def code_wp(w_dim):
+    """Words of a packed W-bit message."""
+    return (int(w_dim) + EVAL_CODE_BITS - 1) // EVAL_CODE_BITS
 
 
 def load():
@@ -123,6 +137,12 @@ def load():
     lib.mmg_eval_steps.restype = i32; lib.mmg_eval_steps.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp]
     lib.mmg_eval_profile_count.restype = i64; lib.mmg_eval_profile_count.argtypes = [cfgp]
     lib.mmg_eval_steps_profile.restype = i32; lib.mmg_eval_steps_profile.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp, vp]
+    lib.mmg_eval_code_words.restype = i64; lib.mmg_eval_code_words.argtypes = [cfgp]
+    lib.mmg_eval_steps_codes.restype = i32
+    lib.mmg_eval_steps_codes.argtypes = [vp, fp, vp, i64, fp, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp]
+    lib.mmg_code_pair_hist_count.restype = i64; lib.mmg_code_pair_hist_count.argtypes = [i32, i32, i32]
+    lib.mmg_code_pair_hist.restype = i32
+    lib.mmg_code_pair_hist.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, fp, i32, i64, fp, i32, vp, vp]
     lib.mmg_set_message_corruption.restype = i32; lib.mmg_set_message_corruption.argtypes = [vp, vp, i32]
     lib.mmg_set_message_flipout.restype = i32; lib.mmg_set_message_flipout.argtypes = [vp, i32, C.c_float, i32, C.c_float, i32, u64]
     lib.mmg_set_sender_variant.restype = i32; lib.mmg_set_sender_variant.argtypes = [vp, i32, i32, i32]

@@ -18,7 +18,10 @@ Flat layout (int64, profile_count(D, T, W) = 4 + 2 D T + 2 D + 2 T D W entries):
   class_ranksum [D]   sum over the samples of class c of rank_{T-1}
   msg_sen [T, D, W]   samples of class c, live at t, whose sender bit j is set at step t
   msg_rec [T, D, W]   the same over the receiver's messages
-A sample whose target is outside [0, D) counts in head[2] only.  Continuous messages leave msg_sen / msg_rec zero."""
+A sample whose target is outside [0, D) counts in head[2] only.  Continuous messages leave msg_sen / msg_rec zero.
+
+The second half of the module is the PAIRWISE analysis (mmg_eval_steps_codes, mmg_code_pair_hist): pack_codes, pair_hist_np and
+topsim() -- topographic similarity, class separation, collisions; its layouts stand in front of it."""
 import numpy as np
 
 HEAD = 4
@@ -129,3 +132,159 @@ def summarise(profile, top_k):
             out["code_" + name] = code
             out["mi_" + name] = np.where(N_t[:, None] > 0, _entropy_bits(np.nan_to_num(q)) - cond, np.nan)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Pairwise code analysis (include/mmg.h: mmg_eval_steps_codes, mmg_code_pair_hist; csrc/kernels_eval.h: k_eval_codes,
+# csrc/kernels_pairs.h): every sample's own code, the joint histogram of (same class?, Hamming distance of two codes, cosine
+# distance of two meanings) over all unordered pairs of samples, and what is read off it -- topographic similarity, class
+# separation, collisions.  The codes are the bits the -binary_only dump stores per sample and step (binary_vectors.py:101-126).
+#
+#   codes [rows, 2, T, Wp] uint32   agent 0 the sender's z, 1 the receiver's w; Wp = (W + 31) // 32; bit (j & 31) of word (j >> 5)
+#                                   is set iff rint(msg[t, b, j]) == 1 and t <= tsel[b]; dead steps and padding bits are zero
+#   meta [rows, 2] int32            tsel[b] | target[b], or -1 for a target outside [0, D)
+#   flat histogram, int64, pair_hist_count() = 4 + 2 (M + 1) K entries, M = (t1 - t0) W selected bits, K bins:
+#     head [4]            [0] rows used | [1] rows skipped (meta target -1) | [2] pairs counted = used (used - 1) / 2 | [3] 0
+#     hist [2, M + 1, K]  hist[p, h, q]: pairs i < j of used rows with p = (target_i == target_j), Hamming distance h over the
+#                         selected steps, and q = min(K - 1, max(0, floor((1 - cos(x_i, x_j)) K / 2))); a zero row has cos = 0
+# ---------------------------------------------------------------------------------------------
+CODE_BITS = 32
+PAIR_HEAD = 4
+
+
+def code_words(T, W):
+    """uint32 words of one sample's row of codes: 2 agents x T steps x ceil(W / 32)."""
+    return 2 * int(T) * ((int(W) + CODE_BITS - 1) // CODE_BITS)
+
+
+def pack_codes(mask, z, w, target, fixed, n_classes=None):
+    """(codes [B, 2, T, Wp] uint32, meta [B, 2] int32) of ONE batch from its run-all eval tape: mask [T + 1, B], z / w [T, B, W],
+    target [B] -- what k_eval_codes writes for that batch.  n_classes: targets outside [0, n_classes) become -1 (None: negative
+    targets only)."""
+    mask, target = np.asarray(mask).astype(np.int64), np.asarray(target).astype(np.int64).reshape(-1)
+    z, w = np.asarray(z), np.asarray(w)
+    T, B, W = z.shape
+    if fixed:
+        tsel = np.full(B, T - 1, np.int64)
+    else:
+        dead = np.nonzero(mask[1:].sum(1) == 0)[0]
+        n = int(dead[0]) + 1 if len(dead) else T
+        tsel = mask[1:n].sum(0)
+    Wp = (W + CODE_BITS - 1) // CODE_BITS
+    live = np.arange(T)[:, None] <= tsel[None, :]                               # [T, B]
+    codes = np.zeros((B, 2, T, Wp), np.uint32)
+    shifts = np.arange(CODE_BITS, dtype=np.uint64)
+    for a, msg in enumerate((z, w)):
+        bits = np.zeros((T, B, Wp * CODE_BITS), np.uint64)
+        bits[:, :, :W] = (np.rint(msg) == 1) & live[:, :, None]
+        words = (bits.reshape(T, B, Wp, CODE_BITS) << shifts).sum(3)            # [T, B, Wp]
+        codes[:, a] = words.transpose(1, 0, 2).astype(np.uint32)
+    valid = (target >= 0) & ((target < n_classes) if n_classes is not None else True)
+    meta = np.stack([tsel, np.where(valid, target, -1)], 1).astype(np.int32)
+    return codes, meta
+
+
+def pair_hist_count(n_sel_steps, W, bins):
+    return PAIR_HEAD + 2 * (int(n_sel_steps) * int(W) + 1) * int(bins)
+
+
+def parse_pair_hist(flat, n_sel_steps, W, bins):
+    """The parts of a flat pair histogram: head, used / skipped / pairs, hist [2, M + 1, K] (a view of `flat` where it is a
+    contiguous int64 array; plane 0 the pairs of different classes, plane 1 those of the same class)."""
+    flat = np.asarray(flat, np.int64).reshape(-1)
+    M, K = int(n_sel_steps) * int(W), int(bins)
+    if flat.size != pair_hist_count(n_sel_steps, W, bins):
+        raise ValueError("a pair histogram of %d selected bits and %d bins has %d entries, not %d"
+                         % (M, K, pair_hist_count(n_sel_steps, W, bins), flat.size))
+    return dict(head=flat[:PAIR_HEAD], used=int(flat[0]), skipped=int(flat[1]), pairs=int(flat[2]),
+                hist=flat[PAIR_HEAD:].reshape(2, M + 1, K))
+
+
+def _code_bits(words):
+    """[n, nw] uint32 -> [n, 32 nw] float64 of 0 / 1 (the bit order does not matter for a Hamming distance)."""
+    words = np.ascontiguousarray(words)
+    words = np.ascontiguousarray(words.view(np.uint32) if words.dtype == np.int32 else words, dtype="<u4")     # (int32: torch's view of the words)
+    return np.unpackbits(words.view(np.uint8), axis=1).astype(np.float64)
+
+
+def pair_hist_np(codes, meta, meaning, agent, t0, t1, bins, W=None, block=512):
+    """mmg_code_pair_hist restated: the flat histogram of codes [N, 2, T, Wp] / meta [N, 2] against the cosine distance of the
+    rows of meaning [N, F], with the cosine in float64 (c = dot(x_i, x_j) * (inv_i * inv_j), inv = 1 / sqrt(sum x^2), 0 for a zero
+    row).  W: the message width (default 32 Wp: then M counts the padding bits too).  Rows are walked in blocks of `block`."""
+    codes, meta = np.asarray(codes), np.asarray(meta)
+    N, _, T, Wp = codes.shape
+    W = Wp * CODE_BITS if W is None else int(W)
+    if not (agent in (0, 1) and 0 <= t0 < t1 <= T and bins >= 1):
+        raise ValueError("agent must be 0 or 1, 0 <= t0 < t1 <= T, bins >= 1")
+    M, K = (t1 - t0) * W, int(bins)
+    tgt = meta[:, 1].astype(np.int64)
+    used = np.nonzero(tgt >= 0)[0]
+    n = len(used)
+    flat = np.zeros(pair_hist_count(t1 - t0, W, K), np.int64)
+    flat[:3] = (n, N - n, n * (n - 1) // 2)
+    x = np.asarray(meaning, np.float64)[used]
+    ss = (x * x).sum(1)
+    inv = np.where(ss > 0, 1.0 / np.sqrt(np.where(ss > 0, ss, 1.0)), 0.0)
+    bits = _code_bits(codes[used, agent, t0:t1].reshape(n, -1))
+    ones = bits.sum(1)
+    tg = tgt[used]
+    for i0 in range(0, n, block):
+        i1 = min(i0 + block, n)
+        c = (x[i0:i1] @ x[i0:].T) * (inv[i0:i1, None] * inv[None, i0:])
+        q = np.clip(np.floor((1.0 - c) * (0.5 * K)), 0, K - 1).astype(np.int64)
+        h = np.rint(ones[i0:i1, None] + ones[None, i0:] - 2.0 * (bits[i0:i1] @ bits[i0:].T)).astype(np.int64)
+        p = (tg[i0:i1, None] == tg[None, i0:]).astype(np.int64)
+        keep = np.arange(i1 - i0)[:, None] < np.arange(n - i0)[None, :]          # i < j
+        slot = ((p * (M + 1) + h) * K + q)[keep]
+        flat[PAIR_HEAD:] += np.bincount(slot, minlength=2 * (M + 1) * K)
+    return flat
+
+
+def _midranks(counts):
+    """Mid-ranks (1-based) of the values of a marginal histogram."""
+    counts = np.asarray(counts, np.float64)
+    return np.cumsum(counts) - counts + (counts + 1.0) / 2.0
+
+
+def _weighted_pearson(J, a, b):
+    """Pearson correlation of the row scores a and column scores b under the joint counts J; nan without variance."""
+    n = J.sum()
+    if n <= 0:
+        return float("nan")
+    ra, rb = J.sum(1), J.sum(0)
+    da, db = a - (ra * a).sum() / n, b - (rb * b).sum() / n
+    va, vb = (ra * da * da).sum(), (rb * db * db).sum()
+    if not (va > 0 and vb > 0):
+        return float("nan")
+    return float((J * da[:, None] * db[None, :]).sum() / np.sqrt(va * vb))
+
+
+def topsim(hist):
+    """What is read off a pair histogram (parse_pair_hist()'s dict, or its hist [2, M + 1, K]): dict of
+      n_pairs        the pairs counted
+      spearman       topographic similarity: the mid-rank Spearman correlation of (h, q) over all pairs -- Pearson over the
+                     mid-ranks of the two marginals, weighted by the joint counts (= scipy.stats.spearmanr on the expanded pairs)
+      pearson        h against the bin centres (q + 1/2) 2 / K of the cosine distance
+      hamming_same, hamming_diff    mean Hamming distance of the same-class / different-class pairs
+      separation     P(h_diff > h_same) + 1/2 P(h_diff == h_same) for a random different-class and a random same-class pair
+      collisions     different-class pairs with identical codes (h == 0)
+    each nan where undefined (an empty plane, zero variance)."""
+    H = np.asarray(hist["hist"] if isinstance(hist, dict) else hist, np.float64)
+    if H.ndim != 3 or H.shape[0] != 2:
+        raise ValueError("a pair histogram is [2, M + 1, K]")
+    _, M1, K = H.shape
+    J = H[0] + H[1]
+    hs = np.arange(M1, dtype=np.float64)
+    diff, same = H[0].sum(1), H[1].sum(1)
+    nd, ns = diff.sum(), same.sum()
+    nan = float("nan")
+    sep = nan
+    if nd > 0 and ns > 0:
+        below = np.cumsum(same) - same                                           # same-class pairs with a smaller h
+        sep = float((diff * (below + 0.5 * same)).sum() / (nd * ns))
+    return dict(n_pairs=int(round(J.sum())),
+                spearman=_weighted_pearson(J, _midranks(J.sum(1)), _midranks(J.sum(0))),
+                pearson=_weighted_pearson(J, hs, (np.arange(K) + 0.5) * (2.0 / K)),
+                hamming_same=float((same * hs).sum() / ns) if ns > 0 else nan,
+                hamming_diff=float((diff * hs).sum() / nd) if nd > 0 else nan,
+                separation=sep, collisions=int(round(H[0, 0].sum())))

@@ -230,4 +230,66 @@ __global__ __launch_bounds__(MMG_BLOCK) void k_eval_profile(Dims dm, Tape tp, co
     if (lane == 0 && n_invalid) eval_add(prof + 2, n_invalid);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_eval_codes -- every sample's own code of a dev evaluation: the bits of both agents' messages the -binary_only dump stores per
+// sample and step (binary_vectors.py:101-126), packed 32 to a word, for the pairwise analysis of kernels_pairs.h (which needs every
+// sample's code, not the per-class sums of k_eval_profile).  One launch behind k_eval_reduce (and k_eval_profile) of
+// mmg_eval_steps_codes, on the same stream; it reads only the plain tape arrays mask, z, w and the targets, so it serves every
+// handle kind, and a corruption mask or flipout_dev flips are packed as the receiver saw them.  Binary messages only.
+//
+// Per sample b, WRITTEN (not accumulated) at row = the launch's first row + b; n and tsel[b] as k_eval_reduce derives them:
+//   codes[row][agent][t][k] uint32, agent 0 = the sender's z, 1 = the receiver's w, t < T, k < Wp = eval_code_wp(W):
+//                           bit (j & 31) of word (j >> 5) is set iff lrintf(msg[t, b, j]) == 1 and t <= tsel[b]; the steps behind
+//                           the output step and the padding bits of the last word are zero.  EVERY word of the row is written.
+//   meta[row][2] int32      tsel[b] | target[b], or -1 for a target outside [0, D)
+//
+// grid = eval_sample_blocks(B) workgroups of 256 threads, a wave per sample: lanes over the steps for tsel, then lanes over 64 bits
+// of a message at a time -- the wave's ballot IS the two code words.  No LDS beyond the step flags, no atomics, no workgroup waits
+// for another one.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline int eval_code_wp(int W) { return (W + 31) / 32; }
+__host__ __device__ inline int64_t eval_code_words(int T, int W) { return 2 * (int64_t)T * eval_code_wp(W); }
+
+__global__ __launch_bounds__(MMG_BLOCK) void k_eval_codes(Dims dm, Tape tp, const int64_t* __restrict__ target,
+                                                          uint32_t* __restrict__ codes, int32_t* __restrict__ meta,
+                                                          int n_sample_blocks) {
+    __shared__ int s_alive[64];                        // [t]: some sample is alive after step t (T <= 64)
+    const int T = dm.T, B = dm.B, D = dm.D, W = dm.W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int blk = blockIdx.x;
+    if (blk >= n_sample_blocks) return;
+    // ---- n of the batch, as k_eval_reduce forms it
+    if (tid < 64) s_alive[tid] = 0;
+    __syncthreads();
+    if (!dm.fixed)
+        for (int i = tid; i < T * B; i += MMG_BLOCK)
+            if (tp.mask[(size_t)B + i]) s_alive[i / B] = 1;
+    __syncthreads();
+    int n = T;
+    if (!dm.fixed)
+        for (int t = T - 1; t >= 0; --t)
+            if (s_alive[t] == 0) n = t + 1;
+    const int Wp = eval_code_wp(W);
+    for (int b = blk * (MMG_BLOCK / 64) + wave; b < B; b += n_sample_blocks * (MMG_BLOCK / 64)) {
+        const int live = (lane >= 1 && lane < n && tp.mask[(size_t)lane * B + b] != 0) ? 1 : 0;
+        const int tsel = dm.fixed ? T - 1 : eval_wave_sum(live);
+        if (lane == 0) {
+            const int64_t tg = target[b];
+            meta[(size_t)b * 2] = tsel;
+            meta[(size_t)b * 2 + 1] = (tg >= 0 && tg < D) ? (int32_t)tg : -1;
+        }
+        uint32_t* out = codes + (size_t)b * (2 * T * Wp);
+        for (int a = 0; a < 2; ++a) {
+            const float* msg = a ? tp.w : tp.z;
+            for (int t = 0; t < T; ++t)
+                for (int k0 = 0; k0 < Wp; k0 += 2) {                   // (wave-uniform loops: the ballot sees all 64 lanes)
+                    const int j = k0 * 32 + lane;
+                    const bool bit = t <= tsel && j < W && lrintf(msg[((size_t)t * B + b) * W + j]) == 1;
+                    const unsigned long long word = __ballot(bit);
+                    if (lane == 0) out[((size_t)a * T + t) * Wp + k0] = (uint32_t)word;
+                    if (lane == 1 && k0 + 1 < Wp) out[((size_t)a * T + t) * Wp + k0 + 1] = (uint32_t)(word >> 32);
+                }
+        }
+    }
+}
+
 }  // namespace mmg

@@ -29,6 +29,7 @@
 #include "kernels_vjp.h"
 #include "kernels_eval.h"
 #include "kernels_loss.h"
+#include "kernels_pairs.h"
 #ifdef MMG_ROLE_DIAG
 #include "diag_kernels.h"
 #endif
@@ -738,9 +739,18 @@ extern "C" int64_t mmg_eval_profile_count(const mmg_config* cfg) {
     return eval_profile_count(cfg->n_classes, cfg->max_exchange, cfg->w_dim);
 }
 
-// d_prof != NULL (mmg_eval_steps_profile): one k_eval_profile launch behind every k_eval_reduce; NULL: the launches of mmg_eval_steps alone
+extern "C" int64_t mmg_eval_code_words(const mmg_config* cfg) {
+    if (validate(cfg)) return -1;
+    if (!cfg->use_binary) return fail("mmg_eval_code_words: continuous messages (use_binary == 0) have no bits to pack");
+    return eval_code_words(cfg->max_exchange, cfg->w_dim);
+}
+
+// d_prof != NULL (mmg_eval_steps_profile): one k_eval_profile launch behind every k_eval_reduce; d_codes != NULL (mmg_eval_steps_codes):
+// one k_eval_codes launch behind those, which writes rows [row0 + i B, row0 + (i + 1) B) of d_codes / d_meta; both NULL: the launches
+// of mmg_eval_steps alone
 static int eval_steps_impl(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
-                           int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream) {
+                           int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream,
+                           uint32_t* d_codes = nullptr, int32_t* d_meta = nullptr, int64_t row0 = 0) {
     if (!h) return fail("NULL handle");
     if (!d_x || !d_target || !d_desc || !d_acc || !d_len || !d_batch) return fail("mmg_eval_steps: x / target / desc / acc / len / batch must not be NULL");
     if (top_k < 1) return fail("mmg_eval_steps: top_k must be >= 1 (got %d)", top_k);
@@ -757,10 +767,18 @@ static int eval_steps_impl(mmg_handle* h, const float* d_x, const int64_t* d_tar
                                d_len + (size_t)i * d.B, d_batch + (size_t)i * (1 + 2 * d.T), nsb);
             if (launch_check("k_eval_reduce")) return -1;
         }
-        if (!d_prof) continue;
-        Scope sc(h, st, "k_eval_profile");
-        hipLaunchKernelGGL(k_eval_profile, dim3(nsb), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_prof, nsb);
-        if (launch_check("k_eval_profile")) return -1;
+        if (d_prof) {
+            Scope sc(h, st, "k_eval_profile");
+            hipLaunchKernelGGL(k_eval_profile, dim3(nsb), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt, top_k, d_prof, nsb);
+            if (launch_check("k_eval_profile")) return -1;
+        }
+        if (d_codes) {
+            const size_t row = (size_t)row0 + (size_t)i * d.B;
+            Scope sc(h, st, "k_eval_codes");
+            hipLaunchKernelGGL(k_eval_codes, dim3(nsb), dim3(MMG_BLOCK), 0, st, h->dm, h->tp, tgt,
+                               d_codes + row * (size_t)eval_code_words(d.T, d.W), d_meta + row * 2, nsb);
+            if (launch_check("k_eval_codes")) return -1;
+        }
     }
     return 0;
 }
@@ -774,6 +792,19 @@ extern "C" int mmg_eval_steps_profile(mmg_handle* h, const float* d_x, const int
                                       int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, void* stream) {
     if (!d_prof) return fail("mmg_eval_steps_profile: prof must not be NULL (mmg_eval_steps is the entry without a profile)");
     return eval_steps_impl(h, d_x, d_target, n, d_desc, top_k, d_acc, d_len, d_batch, d_prof, stream);
+}
+
+extern "C" int mmg_eval_steps_codes(mmg_handle* h, const float* d_x, const int64_t* d_target, int64_t n, const float* d_desc, int top_k,
+                                    int64_t* d_acc, int32_t* d_len, int64_t* d_batch, int64_t* d_prof, uint32_t* d_codes, int32_t* d_meta,
+                                    int64_t row0, int64_t cap_rows, void* stream) {
+    if (!h) return fail("NULL handle");
+    if (!h->dm.use_binary) return fail("mmg_eval_steps_codes: continuous messages (use_binary == 0) have no bits to pack");
+    if (!d_codes || !d_meta) return fail("mmg_eval_steps_codes: codes / meta must not be NULL (mmg_eval_steps[_profile] are the entries without codes)");
+    if (row0 < 0) return fail("mmg_eval_steps_codes: row0 must be >= 0 (got %lld)", (long long)row0);
+    if (n > 0 && (n > (INT64_MAX - row0) / h->dm.B || row0 + n * h->dm.B > cap_rows))
+        return fail("mmg_eval_steps_codes: rows [%lld, %lld + %lld * %d) do not fit the %lld rows of codes / meta", (long long)row0,
+                    (long long)row0, (long long)n, h->dm.B, (long long)cap_rows);
+    return eval_steps_impl(h, d_x, d_target, n, d_desc, top_k, d_acc, d_len, d_batch, d_prof, stream, d_codes, d_meta, row0);
 }
 
 // The evaluation mask of -bit_flip (include/mmg.h): host state only; exchange_forward_impl copies it into the launch arguments.
@@ -1742,4 +1773,53 @@ extern "C" int mmg_rec_outp_vjp(const float* d_y, const uint8_t* d_ymask, const 
     hipLaunchKernelGGL(k_rec_outp_vjp, dim3((int)(blocks > 65536 ? 65536 : blocks)), dim3(MMG_BLOCK), 0, (hipStream_t)stream, d_y, d_ymask,
                        d_target, d_doutp, d_dnll, d_dnegent, n_steps, batch, n_classes, d_dy);
     return launch_check("k_rec_outp_vjp");
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pairwise code analysis (kernels_pairs.h): handle-free, on the calling thread's current device.  Two launches: the inverse
+// norms of the meaning rows (and the row counts of the head), then one workgroup per 64 x 64 tile of the upper triangle.
+// ---------------------------------------------------------------------------------------------
+static int pair_shape_ok(const char* who, int64_t M, int W, int K) {
+    if (M < 1 || W < 1) return fail("%s: the selected steps and w_dim must be positive (got %lld, %d)", who, (long long)M, W);
+    if (K < 1 || K > MMG_PAIR_MAX_BINS) return fail("%s: n_bins must be in 1..%d (got %d)", who, MMG_PAIR_MAX_BINS, K);
+    if (M > MMG_PAIR_MAX_SLOTS || pair_hist_slots(M, K) > MMG_PAIR_MAX_SLOTS)
+        return fail("%s: 2 (M + 1) n_bins must be <= 2^24 (M = %lld selected bits, %d bins)", who, (long long)M, K);
+    return 0;
+}
+
+extern "C" int64_t mmg_code_pair_hist_count(int n_sel_steps, int w_dim, int n_bins) {
+    if (n_sel_steps < 1 || w_dim < 1) { fail("mmg_code_pair_hist_count: n_sel_steps and w_dim must be positive (got %d, %d)", n_sel_steps, w_dim); return -1; }
+    const int64_t M = (int64_t)n_sel_steps * w_dim;
+    if (pair_shape_ok("mmg_code_pair_hist_count", M, w_dim, n_bins)) return -1;
+    return pair_hist_count(M, n_bins);
+}
+
+extern "C" int mmg_code_pair_hist(const uint32_t* d_codes, const int32_t* d_meta, int64_t n_rows, int T, int W, int agent, int t0, int t1,
+                                  const float* d_meaning, int F, int64_t ld, float* d_inv, int n_bins, int64_t* d_hist, void* stream) {
+    const char* who = "mmg_code_pair_hist";
+    if (!d_codes || !d_meta || !d_meaning || !d_inv || !d_hist) return fail("%s: codes / meta / meaning / inv / hist must not be NULL", who);
+    if (n_rows < 1 || n_rows > MMG_PAIR_MAX_ROWS) return fail("%s: n_rows must be in 1..%d (got %lld)", who, MMG_PAIR_MAX_ROWS, (long long)n_rows);
+    if (F < 1 || F > MMG_PAIR_MAX_F) return fail("%s: F must be in 1..%d (got %d)", who, MMG_PAIR_MAX_F, F);
+    if (ld < F) return fail("%s: the row stride ld must be >= F (got %lld < %d)", who, (long long)ld, F);
+    if (agent != 0 && agent != 1) return fail("%s: agent must be 0 (sender) or 1 (receiver) (got %d)", who, agent);
+    if (T < 1 || W < 1) return fail("%s: T and W must be positive (got %d, %d)", who, T, W);
+    if (!(0 <= t0 && t0 < t1 && t1 <= T)) return fail("%s: the steps must satisfy 0 <= t0 < t1 <= T (got %d, %d, T = %d)", who, t0, t1, T);
+    const int64_t M = (int64_t)(t1 - t0) * W;
+    if (pair_shape_ok(who, M, W, n_bins)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int Wp = eval_code_wp(W);
+    PairArgs ar;
+    ar.codes = d_codes; ar.meta = d_meta; ar.x = d_meaning; ar.inv = d_inv; ar.hist = d_hist;
+    ar.ld = ld; ar.row_words = eval_code_words(T, W); ar.sel0 = ((int64_t)agent * T + t0) * Wp;
+    ar.n_rows = (int)n_rows; ar.F = F; ar.nw = (t1 - t0) * Wp; ar.M = (int)M; ar.K = n_bins;
+    ar.n_tiles = (int)((n_rows + MMG_PAIR_TILE - 1) / MMG_PAIR_TILE);
+    ar.codes_lds = pair_codes_in_lds(ar.nw) ? 1 : 0;
+    ar.hist_lds = pair_hist_in_lds(ar.nw, pair_hist_slots(M, n_bins)) ? 1 : 0;
+    const size_t dyn = (size_t)pair_code_lds_bytes(ar.nw) + (ar.hist_lds ? (size_t)pair_hist_slots(M, n_bins) * 4 : 0);
+    hipLaunchKernelGGL(k_pair_norms, dim3((unsigned)((n_rows + MMG_BLOCK / 64 - 1) / (MMG_BLOCK / 64))), dim3(MMG_BLOCK), 0, st, d_meaning, ld, F,
+                       d_meta, (int)n_rows, d_inv, d_hist);
+    if (launch_check("k_pair_norms")) return -1;
+    if (dyn > 48 * 1024) HIP_OK(hipFuncSetAttribute((const void*)k_pair_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    hipLaunchKernelGGL(k_pair_hist, dim3((unsigned)((int64_t)ar.n_tiles * (ar.n_tiles + 1) / 2)), dim3(MMG_BLOCK), dyn, st, ar);
+    return launch_check("k_pair_hist");
 }

@@ -391,14 +391,48 @@ class Engine(object):
             raise _lib.MmgError(self.lib.mmg_last_error().decode())
         return torch.zeros(n, dtype=torch.int64, device=self.device)
 
-    def eval_steps(self, x, target, desc, n, top_k, acc, lens=None, batch=None, corrupt_mask=None, prof=None):
+    def eval_codes(self, cap_rows):
+        """(codes [cap_rows, 2, T, Wp] uint32-as-int32, meta [cap_rows, 2] int32) device buffers for eval_steps(codes=...)
+        (include/mmg.h: mmg_eval_steps_codes; mmg_eval_code_words() words per row).  Not zeroed: every word of a row is written.
+        Engines of the same step count and message width may share them (each writes its own rows)."""
+        n = int(self.lib.mmg_eval_code_words(C.byref(self.cfg)))
+        if n < 0:
+            raise _lib.MmgError(self.lib.mmg_last_error().decode())
+        T = self.cfg.max_exchange
+        codes = torch.empty(int(cap_rows), _lib.EVAL_CODE_AGENTS, T, n // (_lib.EVAL_CODE_AGENTS * T), dtype=torch.int32, device=self.device)
+        return codes, torch.empty(int(cap_rows), _lib.EVAL_CODE_META, dtype=torch.int32, device=self.device)
+
+    def code_pair_hist(self, codes, meta, n_rows, agent, steps, meaning, bins):
+        """The pair histogram of the first n_rows rows of (codes, meta) (eval_codes(), filled by eval_steps(codes=...)) against the
+        cosine distance of the rows of `meaning` [>= n_rows, F] float32 (include/mmg.h: mmg_code_pair_hist): agent 0 the sender's
+        codes, 1 the receiver's; steps = (t0, t1) or None for all T; returns the flat int64 device histogram of
+        4 + 2 ((t1 - t0) W + 1) bins entries (commstats.parse_pair_hist names its parts).  Two launches on the current stream, no host
+        synchronisation."""
+        T, W = int(codes.size(2)), self.cfg.w_dim
+        assert codes.dtype == torch.int32 and codes.dim() == 4 and codes.size(1) == _lib.EVAL_CODE_AGENTS and codes.size(3) == _lib.code_wp(W)
+        assert codes.size(0) >= n_rows and meta.size(0) >= n_rows and meaning.dim() == 2 and meaning.size(0) >= n_rows
+        assert meaning.dtype == torch.float32 and meaning.is_cuda and meaning.stride(1) == 1
+        t0, t1 = (0, T) if steps is None else (int(steps[0]), int(steps[1]))
+        n = int(self.lib.mmg_code_pair_hist_count(max(t1 - t0, 0), W, int(bins)))
+        if n < 0:
+            raise _lib.MmgError(self.lib.mmg_last_error().decode())
+        hist = torch.zeros(n, dtype=torch.int64, device=self.device)
+        inv = torch.empty(int(n_rows), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mmg_code_pair_hist(self._ptr(codes, torch.int32), self._ptr(meta, torch.int32), int(n_rows), T, W, int(agent),
+                                               t0, t1, C.c_void_p(meaning.data_ptr()), int(meaning.size(1)), int(meaning.stride(0)),
+                                               self._ptr(inv, torch.float32), int(bins), self._ptr(hist, torch.int64), self._stream()))
+        return hist
+
+    def eval_steps(self, x, target, desc, n, top_k, acc, lens=None, batch=None, corrupt_mask=None, prof=None, codes=None):
         """n consecutive evaluation conversations (x [n * B, F], target [n * B]), each followed by the library's reduction launch
         (include/mmg.h: mmg_eval_steps): hits / confusion counts / classes seen are ADDED to `acc` (eval_acc()); returns
         (lens [n * B] int32: conversation lengths, batch [n, 1 + 2 T] int64: executed steps | Hamming counts of the sender's
         and of the receiver's messages per step -- float64 bits with continuous messages).  No host synchronisation; the
         minibatch counter is untouched; the tape holds the last batch.  corrupt_mask: as forward().
         prof (eval_profile()): the call is mmg_eval_steps_profile -- the same results, and one more launch per batch ADDS the
-        batch's communication profile to `prof`."""
+        batch's communication profile to `prof`.
+        codes = (codes, meta, row0) (eval_codes()): the call is mmg_eval_steps_codes, with or without prof -- the same results, and
+        one more launch per batch WRITES every sample's packed message bits and (output step, target) at rows row0 + i B + b."""
         B, T = self.cfg.batch, self.cfg.max_exchange
         assert x.size(0) >= n * B and target.size(0) >= n * B
         assert acc.dtype == torch.int64 and acc.numel() == _lib.EVAL_ACC_HEAD + self.cfg.n_classes * (self.cfg.n_classes + 1)
@@ -417,7 +451,12 @@ class Engine(object):
         try:
             args = (self.handle, self._ptr(x, torch.float32), self._ptr(target, torch.int64), int(n), self._ptr(desc, torch.float32),
                     int(top_k), self._ptr(acc, torch.int64), self._ptr(lens, torch.int32), self._ptr(batch, torch.int64))
-            if prof is None:
+            if codes is not None:
+                cd, meta, row0 = codes
+                assert cd.size(0) == meta.size(0) and tuple(cd.shape[1:]) == (_lib.EVAL_CODE_AGENTS, T, _lib.code_wp(self.cfg.w_dim))
+                _lib.check(self.lib.mmg_eval_steps_codes(*args, self._ptr(prof, torch.int64), self._ptr(cd, torch.int32),
+                                                         self._ptr(meta, torch.int32), int(row0), int(cd.size(0)), self._stream()))
+            elif prof is None:
                 _lib.check(self.lib.mmg_eval_steps(*args, self._stream()))
             else:
                 _lib.check(self.lib.mmg_eval_steps_profile(*args, self._ptr(prof, torch.int64), self._stream()))

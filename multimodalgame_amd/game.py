@@ -226,22 +226,85 @@ class EvalAccumulator(object):
     accumulator -- hits, the [D, D] confusion counts, the classes seen -- shared by the engines of every batch size, and per
     call the conversation lengths and the per-batch step count / Hamming counts.  fetch() copies everything to the host ONCE.
     profile=True: the accumulator also owns ONE communication profile (include/mmg.h: mmg_eval_steps_profile) that the engines of
-    all batch sizes add to; fetch() returns it, parsed into its named blocks (commstats.parse_profile), under "profile"."""
+    all batch sizes add to; fetch() returns it, parsed into its named blocks (commstats.parse_profile), under "profile".
+    codes=cap_rows: the accumulator also owns every sample's packed message bits and (output step, target), in dataset order
+    (include/mmg.h: mmg_eval_steps_codes; one more launch per batch) -- cap_rows is the capacity the buffers start with; an
+    evaluation that outgrows it gets larger ones (device copies, no host synchronisation).  meaning="data" | "desc": and an [N, F]
+    device matrix of what a sample MEANS, the batches' data rows or the desc[target] rows, for pair_hist().  fetch() is unchanged
+    by both."""
 
-    def __init__(self, n_classes, top_k, profile=False):
+    def __init__(self, n_classes, top_k, profile=False, codes=None, meaning=None):
         self.n_classes, self.top_k, self.profile = int(n_classes), int(top_k), bool(profile)
         self.acc = None                                # created by the first engine that adds to it
         self.prof, self.prof_dims = None, None         # profile=True: the flat profile and its (D, T, W), likewise
         self.parts = []                                # (B, n, T, binary, lens [n * B] i32, batch [n, 1 + 2 T] i64)
+        if meaning not in (None, "data", "desc"):
+            raise ValueError("meaning must be None, 'data' or 'desc' (got %r)" % (meaning,))
+        if meaning is not None and codes is None:
+            raise ValueError("meaning=%r needs codes=cap_rows" % (meaning,))
+        if codes is not None and int(codes) < 1:
+            raise ValueError("codes: the capacity in rows must be >= 1")
+        self.cap_rows = None if codes is None else int(codes)
+        self.meaning_kind = meaning
+        self.codes, self.meta, self.meaning, self.rows = None, None, None, 0      # codes=cap_rows: created by the first engine, likewise
+        self._code_eng = None
+
+    def _room(self, eng, rows, width):
+        """Buffers for `rows` more rows of codes (and of a `width`-wide meaning matrix)."""
+        if self.codes is None:
+            self.cap_rows = max(self.cap_rows, rows)
+            self.codes, self.meta = eng.eval_codes(self.cap_rows)
+            self._code_eng = eng
+        elif tuple(self.codes.shape[1:]) != (_lib.EVAL_CODE_AGENTS, eng.cfg.max_exchange, _lib.code_wp(eng.cfg.w_dim)):
+            raise ValueError("the engines of one evaluation must share max_exchange and w_dim")
+        if self.meaning_kind and self.meaning is None:
+            self.meaning = torch.empty(self.cap_rows, width, dtype=torch.float32, device=self.codes.device)
+        if self.rows + rows > self.cap_rows:
+            self.cap_rows = max(2 * self.cap_rows, self.rows + rows)
+            grown = eng.eval_codes(self.cap_rows) + ((torch.empty(self.cap_rows, width, dtype=torch.float32, device=self.codes.device),)
+                                                     if self.meaning is not None else ())
+            for new, old in zip(grown, (self.codes, self.meta, self.meaning)):
+                new[:self.rows].copy_(old[:self.rows])
+            self.codes, self.meta = grown[0], grown[1]
+            self.meaning = grown[2] if self.meaning is not None else None
 
     def add(self, eng, data, target, desc, n, corrupt_mask=None):
         if self.acc is None:
             self.acc = eng.eval_acc()
         if self.profile and self.prof is None:
             self.prof, self.prof_dims = eng.eval_profile(), (eng.cfg.n_classes, eng.cfg.max_exchange, eng.cfg.w_dim)
-        lens, batch = eng.eval_steps(data, target, desc, n, self.top_k, self.acc, corrupt_mask=corrupt_mask,
-                                     **(dict(prof=self.prof) if self.profile else {}))
+        kw = dict(prof=self.prof) if self.profile else {}
+        rows = int(n) * eng.cfg.batch
+        if self.cap_rows is not None:
+            flat = data.reshape(data.size(0), -1)
+            self._room(eng, rows, flat.size(1) if self.meaning_kind == "data" else desc.size(1))
+            kw["codes"] = (self.codes, self.meta, self.rows)
+        lens, batch = eng.eval_steps(data, target, desc, n, self.top_k, self.acc, corrupt_mask=corrupt_mask, **kw)
         self.parts.append((eng.cfg.batch, int(n), eng.cfg.max_exchange, bool(eng.cfg.use_binary), lens, batch))
+        if self.cap_rows is not None:
+            if self.meaning_kind == "data":
+                self.meaning[self.rows:self.rows + rows].copy_(flat[:rows])
+            elif self.meaning_kind == "desc":          # (a target outside [0, D) is skipped by the histogram: any row does)
+                self.meaning[self.rows:self.rows + rows].copy_(desc.index_select(0, target[:rows].clamp(0, desc.size(0) - 1)))
+            self.rows += rows
+
+    def pair_hist(self, agent=0, steps=None, bins=64, meaning=None):
+        """The pair histogram of the codes collected so far (include/mmg.h: mmg_code_pair_hist; two launches, then ONE copy to the
+        host), parsed by commstats.parse_pair_hist: head / used / skipped / pairs and hist [2, M + 1, bins].  agent: 0 / "sender",
+        1 / "receiver"; steps: (t0, t1) or None for every step; meaning: an [N, F] float32 device matrix to measure against instead
+        of the one the accumulator kept (meaning="data" | "desc")."""
+        if self.cap_rows is None:
+            raise ValueError("pair_hist needs an accumulator created with codes=cap_rows")
+        if self.codes is None or self.rows == 0:
+            raise ValueError("pair_hist: nothing has been added yet")
+        x = self.meaning if meaning is None else meaning
+        if x is None:
+            raise ValueError("pair_hist needs a meaning matrix: EvalAccumulator(meaning='data' | 'desc') or meaning=[N, F]")
+        agent = {"sender": 0, "receiver": 1}.get(agent, agent)
+        T, W = int(self.codes.size(2)), self._code_eng.cfg.w_dim
+        t0, t1 = (0, T) if steps is None else (int(steps[0]), int(steps[1]))
+        flat = self._code_eng.code_pair_hist(self.codes, self.meta, self.rows, agent, (t0, t1), x, bins)
+        return commstats.parse_pair_hist(flat.cpu().numpy(), t1 - t0, W, bins)
 
     def fetch(self):
         """dict(hits, batches, samples, conf [D, D], seen [D], lens [samples] int64 in dataset order, n [batches],
@@ -914,8 +977,8 @@ class Game(object):
                     **({} if corrupt_mask is None else dict(corrupt_mask=corrupt_mask)))
         return eng
 
-    def eval_accumulator(self, n_classes, top_k, profile=False):
-        return EvalAccumulator(n_classes, top_k, profile=profile)
+    def eval_accumulator(self, n_classes, top_k, profile=False, codes=None, meaning=None):
+        return EvalAccumulator(n_classes, top_k, profile=profile, codes=codes, meaning=meaning)
 
     def eval_steps(self, data, target, desc, n, acc, corrupt_mask=None, data_context=None):
         """n consecutive dev batches (data [n * B, F], target [n * B], as train_steps lays them out) evaluated by ONE library

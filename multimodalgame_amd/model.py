@@ -85,6 +85,17 @@ def _eval_profile_reduce(groups, prof, top_k):
                                            top_k, bool(FLAGS.fixed_exchange), bool(FLAGS.use_binary))
 
 
+def _eval_codes_reduce(groups, store, n_cls):
+    """The torch form's per-sample codes: commstats.pack_codes of every dev batch stacked in `groups`, appended to `store`
+    (codes, meta, meaning rows -- what k_eval_codes writes in the library form, csrc/kernels_eval.h; the pair histogram does not
+    depend on the order of the samples)."""
+    for g in groups.values():
+        for mask, z, w, tgt, mean in zip(g["mask"], g["z"], g["w"], g["target"], g["meaning"]):
+            codes, meta = commstats.pack_codes(mask.cpu().numpy(), z.cpu().numpy(), w.cpu().numpy(), tgt.cpu().numpy(),
+                                               bool(FLAGS.fixed_exchange), n_cls)
+            store["codes"].append(codes); store["meta"].append(meta); store["meaning"].append(mean.cpu().numpy())
+
+
 def corrupt_mask_from_flags():
     """The [W, 1] mask of -bit_flip -corrupt_region (misc.build_mask; model.py:813-820), or None without -bit_flip.  A region
     outside the W-bit message raises ValueError here, where the reference fails at its first dev evaluation."""
@@ -96,7 +107,8 @@ def corrupt_mask_from_flags():
         raise ValueError(str(e))
 
 
-def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels, conf_mat_path, device, dump=None, profile=None):
+def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels, conf_mat_path, device, dump=None, profile=None,
+             topsim=None):
     """model.py:580-722 ON THE DEVICE: deterministic conversations on the dev set, top-k accuracy (nominal batch size in the
     denominator, line 667), confusion matrix, conversation length and Hamming statistics.
 
@@ -124,8 +136,23 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     messages; commstats.summarise() turns it into accuracy against conversation length, per-class statistics and the information
     every message bit carries).  The library form adds it on the device with one more launch per batch (include/mmg.h:
     mmg_eval_steps_profile), the torch form reduces the tape slices it copies anyway; the return value, the confusion matrix file
-    and the log lines are the same with and without it."""
+    and the log lines are the same with and without it.
+    topsim: optional dict of settings -- meaning="data" (the image features: the image-level measure, the default) or "desc" (the
+    desc[target] rows: the class-level one), bins=64, steps=None or (t0, t1) -- that comes back holding the pairwise code analysis of
+    the evaluation (binary messages only): "sender" / "receiver" = commstats.topsim() of that agent's codes (topographic similarity,
+    class separation, collisions) and "hist" = {"sender", "receiver"}, the parsed pair histograms (commstats.parse_pair_hist).  The
+    library form collects every sample's code on the device with one more launch per batch (include/mmg.h: mmg_eval_steps_codes) and
+    forms each histogram with two launches (mmg_code_pair_hist); the torch form packs the tape slices it copies anyway
+    (commstats.pack_codes, pair_hist_np).  Return value, confusion matrix file and log lines are the same with and without it."""
     W = FLAGS.rec_w_dim
+    ts = None
+    if topsim is not None:
+        ts = dict(meaning=topsim.get("meaning") or "data", bins=int(topsim.get("bins") or 64), steps=topsim.get("steps"))
+        if ts["meaning"] not in ("data", "desc"):
+            raise ValueError("topsim: meaning must be 'data' or 'desc' (got %r)" % (ts["meaning"],))
+        if not FLAGS.use_binary:
+            raise NotImplementedError("topsim: the pairwise code analysis needs binary messages (-use_binary)")
+    store, pair = dict(codes=[], meta=[], meaning=[]), None
     corrupt_mask = corrupt_mask_from_flags()
     n_cls = desc.size(0)
     T = game.max_exchange
@@ -145,7 +172,8 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         _bs = target.size(0)
         total += float(batch_size)                                           # model.py:667: the NOMINAL batch size
         if eng is None and hasattr(game.engine_for(_bs, n_cls), "eval_steps") and not os.environ.get("MMG_EVAL_TORCH"):
-            dacc = game.eval_accumulator(n_cls, top_k, **({} if profile is None else dict(profile=True)))
+            dacc = game.eval_accumulator(n_cls, top_k, **({} if profile is None else dict(profile=True)),
+                                         **({} if ts is None else dict(codes=max(batch_size, 1024), meaning=ts["meaning"])))
         if dacc is not None:
             eng = game.eval_steps(data, target, desc, 1, dacc, corrupt_mask=corrupt_mask)
             continue
@@ -155,10 +183,15 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         g["mask"].append(tp["mask"].view(T + 1, _bs).clone()); g["s"].append(tp["s"].view(T, _bs).clone())
         g["z"].append(tp["z"].view(T, _bs, W).clone()); g["w"].append(tp["w"].view(T, _bs, W).clone())
         g["y"].append(tp["y"].view(T, _bs, -1).clone()); g["target"].append(target.view(-1))
+        if ts is not None:
+            g.setdefault("meaning", []).append(data.reshape(_bs, -1).to(torch.float32) if ts["meaning"] == "data"
+                                               else desc.to(torch.float32).index_select(0, target.view(-1).to(desc.device).clamp(0, n_cls - 1)))
         pending += 1
         if pending >= EVAL_FLUSH_BATCHES:              # bound the stacked tape copies (a 1000-class dev set of 50k samples would hold GBs)
             if profile is not None:
                 _eval_profile_reduce(groups, prof, top_k)
+            if ts is not None:
+                _eval_codes_reduce(groups, store, n_cls)
             _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
             groups, pending = {}, 0
     # ---- ONE copy to the host
@@ -168,9 +201,18 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
         cl, hs, hr = r["lens"].astype(np.float64), r["ham_sen"], r["ham_rec"]
         if profile is not None and r["profile"] is not None:
             prof = np.concatenate([v.reshape(-1) for v in [r["profile"]["head"]] + [r["profile"][k] for k in commstats.BLOCKS]])
+        if ts is not None and dacc.rows:
+            pair = {name: dacc.pair_hist(agent=name, steps=ts["steps"], bins=ts["bins"]) for name in ("sender", "receiver")}
     else:
         if profile is not None:
             _eval_profile_reduce(groups, prof, top_k)
+        if ts is not None:
+            _eval_codes_reduce(groups, store, n_cls)
+            if store["codes"]:
+                t0, t1 = (0, T) if ts["steps"] is None else (int(ts["steps"][0]), int(ts["steps"][1]))
+                cd, mt, mean = [np.concatenate(store[k]) for k in ("codes", "meta", "meaning")]
+                pair = {name: commstats.parse_pair_hist(commstats.pair_hist_np(cd, mt, mean, a, t0, t1, ts["bins"], W=W), t1 - t0, W, ts["bins"])
+                        for a, name in enumerate(("sender", "receiver"))}
         _eval_reduce(groups, acc, conv_lens, ham_sen, ham_rec, T, W, n_cls, top_k)
         correct, conf_flat, seen = acc["correct"], acc["conf_flat"], acc["seen"]
         correct_h = int(correct.item()) if correct is not None else 0
@@ -188,6 +230,10 @@ def eval_dev(dev_file, batch_size, epoch, shuffle, top_k, game, desc, map_labels
     if profile is not None:
         profile.clear()
         profile.update(commstats.parse_profile(prof, n_cls, T, W))
+    if topsim is not None:
+        topsim.clear()
+        topsim.update(dict(ts, hist=pair, sender=commstats.topsim(pair["sender"]) if pair else None,
+                           receiver=commstats.topsim(pair["receiver"]) if pair else None))
     return correct_h / total, extra
 
 
